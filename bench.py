@@ -2,6 +2,7 @@
 """bench.py -- headline measurement: batched LZ4 block decompress on MI355X through the C ABI.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (... and every secondary measurement after the headline)
 
 A "step" is one pass of the hot path (achip_lz4_decompress_batch) over this rank's batch of
 synthetic blocks (BASELINE.json configs[1]: 262144 x 64 KiB per GPU).  Blocks are independent, so ranks
@@ -12,7 +13,11 @@ Inputs (compressed blocks, offsets) and outputs are resident in HBM before the t
 Synthetic data: the reference's test generator shape (T/snappy/RandomGenerator.java:25-74): 100-byte
 fragments made of max(1, 100*ratio) random bytes repeated; compressed ON THE GPU by the product's own
 bit-exact LZ4 encoder (the oracle is never used to make inputs).  The oracle (oracle/liboracle.so, the C
-restatement of the Java codec) is only timed as the `cpu_baseline` leg on rank 0 at N=1.
+restatement of the Java codec) is only timed as the `cpu_baseline` leg on rank 0 at N=1 (--full).
+
+A plain run sets up, warms up, times the K steps, checks the last step's output bit-exact, writes it when --dump-outputs is given, and
+prints the line.  Everything else -- the per-rank legs (Snappy, Zstd, the mixed corpus batch), the extras (real data, containers, xxHash,
+Zstd streams), the ratio sweep, the host-facing numbers and the CPU baseline -- runs only with --full (each --no-* switch still drops its part).
 
 Prints ONE JSON line on rank 0.
 """
@@ -35,7 +40,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); 6290 GB/s
 def parse_args():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=10)
+    p.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--blocks", type=int, default=262144, help="blocks per GPU (BASELINE configs[1]: 262144)")
     p.add_argument("--block-size", type=int, default=65536)
@@ -49,6 +54,9 @@ def parse_args():
     p.add_argument("--ring-class", type=int, default=-1, help="0 = compact LDS rings, 1 = large")
     p.add_argument("--compress-variant", type=int, default=-1, help="LZ4 / Snappy encoder variant: 4 = many matches per window (the default of both); LZ4 also 0 / 1, Snappy 0 .. 3 (see lz4.compress.variant / snappy.compress.variant)")
     p.add_argument("--ring-pad", type=int, default=-1, help="LDS bytes between the ring pairs of consecutive blocks (multiple of 16)")
+    p.add_argument("--full", action="store_true", help="after the headline, also run the legs, extras, sweep, host-facing numbers and CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step as DIR/*.npy (float64 per-block "
+                   "out_len / status / err_off, float32 output bytes of a fixed seeded sample of blocks; rank 0's shard)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extra", action="store_true")
     p.add_argument("--no-verify", action="store_true", help="DEBUG: skip the bit-exact check (kernel timing aids that leave work out); the line is then not a result")
@@ -500,7 +508,7 @@ def stub_main(args, rank, world, dist):
         dist.all_gather_object(per_rank, elapsed_local)
     # the legs' control plane (reduce_leg's gather, the mixed job's partition over the ranks) with the same memcpy standing in for every kernel
     legs = {}
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         for name in ("snappy", "zstd", "zstd_corpus", "zstd_java_frames", "zstd_java_frames_corpus"):
             t0 = time.perf_counter()
             np.copyto(b, a)
@@ -530,6 +538,9 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1:
+        print("bench.py: --steps must be >= 1", file=sys.stderr)
         return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return relaunch_with_ranks(args.gpus)  # --gpus N means N ranks: started here when no launcher did
@@ -739,6 +750,8 @@ def main():
         assert ok, "decompressed output differs from the plaintext"
     else:
         assert bool((out_len == pool_clen.repeat(reps)).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, dst, dst_off, int(dst_cap[0]), out_len, status, err_off)
 
     twopass_fallback = codec.native.get_stat("decompress.twopass_fallback_blocks") if wl.endswith("decompress") else -1
     mixed_groups = codec.native.get_stat("lz4.decompress.mixed_groups") if wl.endswith("decompress") else -1
@@ -806,7 +819,7 @@ def main():
     # release the headline's buffers first: the legs and the extras allocate batches of the same size
     del src, dst
     torch.cuda.empty_cache()
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         codec.native.set_option("max_src_len_hint", 0)  # the legs' units are not the headline's 64 KiB blocks (whole files, 128 KiB frames)
         # the rest of the metric on EVERY rank: at N > 1 all legs (the extras below are N = 1 only); at N = 1 the extras carry Snappy / Zstd and
         # only the mixed corpus batch (configs[4]) is added here
@@ -836,7 +849,7 @@ def main():
             result["value_zstd_java_frames"] = legs["zstd_java_frames"]["GiBps"]    # the same plaintext in the GPU encoder's (= the Java encoder's) frames
             result["value_zstd_java_frames_corpus"] = legs["zstd_java_frames_corpus"]["GiBps"]
     codec.native.set_option("max_src_len_hint", bs)
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         ex = extras(torch, A, codec, dev, args)
         ex.update(xxhash_extra(torch, A, codec, dev, args))
         ex.update(lz4frame_extra(torch, A, codec, dev, args))
@@ -883,9 +896,9 @@ def main():
             result["value_zstd_stream_corpus"] = ex["zstdstream_corpus"]["decompress_GiBps"]  # frames of several blocks (4 MiB streams), corpus-tiled
         if not args.no_sweep:
             result["sweep_random301"] = sweep_random301(torch, A, codec, dev, args)
-    if rank == 0 and world == 1 and not args.no_host_facing and wl == "lz4_decompress":
+    if rank == 0 and world == 1 and args.full and not args.no_host_facing and wl == "lz4_decompress":
         result.update(host_facing(torch, A, codec, pool_pack, pool_pack_off, pool_clen, pool_plain, bs))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(torch, pool_pack, pool_pack_off, pool_clen, pool_plain, bs, op, wl, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -893,6 +906,27 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(torch, path, dst, dst_off, cap, out_len, status, err_off):
+    """--dump-outputs: the arrays the last timed step handed its caller, for comparing two builds output for output.  Per block (all of them up
+    to 2^19, else a seeded sample; `blocks` names them): out_len, status, err_off.  Output bytes of a seeded sample of blocks (32 MiB as
+    float32), `cap` bytes from each block's dst_off, -1 past its out_len (what lies there is not output).  Same arguments, same files."""
+    os.makedirs(path, exist_ok=True)
+    n = out_len.numel()
+    rng = np.random.default_rng(301)
+    blocks = np.arange(n) if n <= 1 << 19 else np.sort(rng.choice(n, 1 << 19, replace=False))
+    sample = np.sort(rng.choice(n, min(n, max(1, (8 << 20) // cap)), replace=False))
+    sel = torch.from_numpy(blocks).to(out_len.device)
+    arrays = {"blocks": blocks, "out_len": out_len[sel], "status": status[sel], "err_off": err_off[sel], "sample_blocks": sample}
+    pick = torch.from_numpy(sample).to(dst.device)
+    col = torch.arange(cap, device=dst.device)
+    got = dst[dst_off[pick].unsqueeze(1) + col].to(torch.float32)
+    got[col.unsqueeze(0) >= out_len[pick].unsqueeze(1)] = -1.0
+    arrays["sample_bytes"] = got
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if name == "sample_bytes" else np.float64))
 
 
 def host_facing(torch, A, codec, pool_pack, pool_pack_off, pool_clen, pool_plain, bs):

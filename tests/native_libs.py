@@ -1,7 +1,6 @@
-"""ctypes access to the third-party codecs bundled with the reference (build container only).
-
-liblz4 1.10.0 / libsnappy 1.2.1 / libzstd 1.5.6 under
-/root/reference/src/main/resources/aircompressor/linux-amd64 (versions: bin/download.sh:57,79,101).
+"""ctypes access to third-party codecs: the ones bundled with the reference where its checkout is here (liblz4 1.10.0 / libsnappy 1.2.1 /
+libzstd 1.5.6 under /root/reference/src/main/resources/aircompressor/linux-amd64, versions: bin/download.sh:57,79,101), else the
+system's shared libraries (liblz4.so.1, libsnappy.so.1, libzstd.so.1) where the machine has them.
 They are an independent *decode* cross-check (a conformant decoder yields identical plaintext) and
 a generator of diverse zstd frames; they are NOT a compress oracle.
 """
@@ -13,8 +12,18 @@ import numpy as np
 LIBDIR = "/root/reference/src/main/resources/aircompressor/linux-amd64"
 
 
-def available():
-    return os.path.isdir(LIBDIR)
+def _path(name):
+    return os.path.join(LIBDIR, "lib%s.so" % name) if os.path.isdir(LIBDIR) else "lib%s.so.1" % name
+
+
+def available(*names):
+    """True when every named library (default: all three) loads"""
+    try:
+        for name in names or ("lz4", "snappy", "zstd"):
+            _load(name, lazy=name == "lz4")
+        return True
+    except OSError:
+        return False
 
 
 _libs = {}
@@ -22,7 +31,7 @@ _libs = {}
 
 def _load(name, lazy=False):
     if name not in _libs:
-        path = os.path.join(LIBDIR, "lib%s.so" % name)
+        path = _path(name)
         if lazy:  # liblz4.so has dangling LZ4_XXH32* imports: needs RTLD_LAZY
             h = ctypes._dlopen(path, os.RTLD_LAZY)
             _libs[name] = ctypes.CDLL(path, handle=h)

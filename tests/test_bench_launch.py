@@ -25,7 +25,7 @@ def json_lines(text):
 
 
 def test_gpus_2_starts_two_ranks_by_itself_and_prints_one_line():
-    r = run_bench({"ACHIP_BENCH_STUB_DEVICE": "1"}, "--gpus", "2", "--blocks", "4096", "--steps", "3", "--warmup", "1")
+    r = run_bench({"ACHIP_BENCH_STUB_DEVICE": "1"}, "--gpus", "2", "--blocks", "4096", "--steps", "3", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stdout + r.stderr
     lines = json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
@@ -71,7 +71,7 @@ import pytest
 def test_bench_gpus_2_on_one_device():
     """The real thing on a one-GPU box: `python bench.py --gpus 2` with no launcher on the command line, both ranks on cuda:0
     (ACHIP_BENCH_SHARE_DEVICE=1: a path check, labelled as such in the line) -- one line, n_gpus 2, both ranks verified bit-exact."""
-    r = run_bench({"ACHIP_BENCH_SHARE_DEVICE": "1"}, "--gpus", "2", "--blocks", "16384", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--zstd-frames", "4096",
+    r = run_bench({"ACHIP_BENCH_SHARE_DEVICE": "1"}, "--gpus", "2", "--blocks", "16384", "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--zstd-frames", "4096",
                   "--mixed-copies", "1", timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = json_lines(r.stdout)

@@ -1,22 +1,23 @@
-"""Oracle checks that need the reference checkout (build container only; skipped on the GPU box):
-corpus round trips, cross-decoding with the third-party codecs the reference bundles, the
-decoder's literal tables, and the stability of tests/golden/manifest.json."""
-import glob
+"""Oracle checks on the reference's test corpus (tests/golden/corpus_full.bin.xz) and its decoders' literal tables
+(tests/golden/java_tables.json, cut from the Java sources by tools/make_golden.py): corpus round trips, cross-decoding with
+third-party codecs (tests/native_libs.py: the ones the reference bundles, else the system's), the decoder's tables, and the
+stability of tests/golden/manifest.json."""
 import hashlib
 import json
 import os
-import re
 
 import pytest
 
-from tests import common, conftest, oracle_lib
-
-pytestmark = pytest.mark.skipif(not conftest.reference_available(), reason="needs /root/reference")
-REF = conftest.REFERENCE
+from tests import common, native_libs, oracle_lib
 
 
 def corpus_files():
-    return sorted(f for f in glob.glob(os.path.join(REF, "testdata", "**", "*"), recursive=True) if os.path.isfile(f))
+    """[(path under the reference's testdata/, bytes)] -- all 42 files"""
+    return sorted(common.corpus_full().items())
+
+
+def java_tables():
+    return json.load(open(os.path.join(common.GOLDEN, "java_tables.json")))
 
 
 @pytest.fixture(scope="module")
@@ -26,9 +27,9 @@ def o():
 
 def test_manifest_is_current(o):
     manifest = json.load(open(os.path.join(common.GOLDEN, "manifest.json")))
-    for f in corpus_files():
-        rel = os.path.relpath(f, os.path.join(REF, "testdata"))
-        d = open(f, "rb").read()
+    files = corpus_files()
+    assert sorted(manifest) == [rel for rel, _ in files]
+    for rel, d in files:
         assert manifest[rel]["sha256"] == hashlib.sha256(d).hexdigest()
         for codec in ("lz4", "snappy", "zstd"):
             c = o.compress(codec, d)
@@ -36,10 +37,10 @@ def test_manifest_is_current(o):
             assert o.decompress(codec, c, len(d)) == d
 
 
+@pytest.mark.skipif(not native_libs.available(), reason="needs liblz4, libsnappy and libzstd (the reference's bundled copies or the system's)")
 def test_cross_decode_with_bundled_native_codecs(o):
-    from tests import native_libs as nl
-    for f in corpus_files():
-        d = open(f, "rb").read()
+    nl = native_libs
+    for f, d in corpus_files():
         assert nl.lz4_decompress(o.compress("lz4", d), len(d)) == d, f       # our stream, their decoder
         assert o.decompress("lz4", nl.lz4_compress(d), len(d)) == d, f        # their stream, our decoder
         assert nl.snappy_decompress(o.compress("snappy", d), len(d)) == d, f
@@ -50,11 +51,11 @@ def test_cross_decode_with_bundled_native_codecs(o):
             assert nl.zstd_decompress(o.compress("zstd", b), len(b)) == b
 
 
+@pytest.mark.skipif(not native_libs.available("zstd"), reason="needs libzstd (the reference's bundled copy or the system's)")
 def test_zstd_decoder_on_libzstd_frames(o):
-    # T/zstd/TestZstd.java:21-47 exercises the Java decoder on zstd-jni level-3 frames; libzstd 1.5.6 stands in
-    from tests import native_libs as nl
-    for f in corpus_files():
-        d = open(f, "rb").read()
+    # T/zstd/TestZstd.java:21-47 exercises the Java decoder on zstd-jni level-3 frames; libzstd stands in
+    nl = native_libs
+    for f, d in corpus_files():
         for level in (1, 3, 7):
             assert o.decompress("zstd", nl.zstd_compress(d, level), len(d)) == d, (f, level)
         for i in range(0, min(len(d), 4 * 131072), 131072):
@@ -62,14 +63,8 @@ def test_zstd_decoder_on_libzstd_frames(o):
             assert o.decompress("zstd", nl.zstd_compress(b, 3), len(b)) == b
 
 
-def _java_int_array(text, name):
-    m = re.search(name + r"\s*=\s*new\s+\w+\[\]\s*\{(.*?)\};", text, flags=re.S)
-    return [int(x, 16) if x.lower().startswith("0x") else int(x) for x in re.findall(r"0x[0-9a-fA-F]+|\d+", m.group(1))]
-
-
 def test_snappy_op_table_matches_java_source(o):
-    text = open(os.path.join(REF, "src/main/java/io/airlift/compress/v3/snappy/SnappyRawDecompressor.java")).read()
-    table = _java_int_array(text, "opLookupTable")
+    table = java_tables()["snappy_op_lookup_table"]
     assert len(table) == 256
 
     def entry(op):  # the layout restated in oracle/snappy.c and the HIP kernel
@@ -88,13 +83,13 @@ def test_zstd_default_tables_match_java_source(o):
     the reference's own table builder; the result must equal the literal tables in ZstdFrameDecompressor.java:85-113.
     Decoding a frame whose sequences use predefined (BASIC) tables exercises them: offset-before-start.zst uses
     all-BASIC tables and must fail exactly at the corrupted offset, and libzstd frames of tiny inputs use BASIC mode."""
-    from tests import native_libs as nl
+    if not native_libs.available("zstd"):
+        pytest.skip("needs libzstd (the reference's bundled copy or the system's)")
     for n in (20, 60, 200, 1000):
         d = (b"abcdefgh" * 200)[:n] + bytes(range(n % 50))
-        assert o.decompress("zstd", nl.zstd_compress(d, 3), len(d)) == d
-    # and literally: parse the three Java tables and compare with tables dumped through a BASIC-mode decode
-    text = open(os.path.join(REF, "src/main/java/io/airlift/compress/v3/zstd/ZstdFrameDecompressor.java")).read()
-    blocks = re.findall(r"new FiniteStateEntropy\.Table\(\s*(\d+),\s*new int\[\] \{(.*?)\},\s*new byte\[\] \{(.*?)\},\s*new byte\[\] \{(.*?)\}\)", text, flags=re.S)
+        assert o.decompress("zstd", native_libs.zstd_compress(d, 3), len(d)) == d
+    # and literally: the three Java tables against tables dumped through a BASIC-mode decode
+    blocks = java_tables()["zstd_default_fse_tables"]
     assert len(blocks) == 3
     import ctypes
     import subprocess
@@ -114,12 +109,12 @@ def test_zstd_default_tables_match_java_source(o):
         subprocess.run(["gcc", "-O1", "-w", "-o", os.path.join(td, "dump"), os.path.join(td, "dump.c"),
                         os.path.join(common.HERE, "..", "oracle", "xxhash64.c")], check=True)
         lines = subprocess.run([os.path.join(td, "dump")], check=True, capture_output=True, text=True).stdout.strip().split("\n")
-    for k, (log, ns, sym, nb) in enumerate(blocks):
-        nums = lambda s: [int(x) for x in re.findall(r"-?\d+", s)]  # noqa: E731
-        assert int(lines[4 * k]) == int(log)
-        assert nums(lines[4 * k + 1]) == nums(ns)
-        assert nums(lines[4 * k + 2]) == nums(sym)
-        assert nums(lines[4 * k + 3]) == nums(nb)
+    nums = lambda s: [int(x) for x in s.split()]  # noqa: E731
+    for k, t in enumerate(blocks):
+        assert int(lines[4 * k]) == t["log2_size"]
+        assert nums(lines[4 * k + 1]) == t["new_state"]
+        assert nums(lines[4 * k + 2]) == t["symbol"]
+        assert nums(lines[4 * k + 3]) == t["number_of_bits"]
 
 
 def test_random_generator_feeds_codecs(o):

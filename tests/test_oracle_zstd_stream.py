@@ -73,7 +73,7 @@ def test_below_four_mebibytes_the_stream_is_one_chunk_and_above_half_a_mebibyte_
         assert h["single"] == 1 and h["fcs"] == n and h["fhd"] & 4      # window 1 MiB >= n: single segment, content size, checksum
         assert len(blocks) == max(1, (n + 131071) // 131072)
         assert o.decompress("zstd", s, n) == d
-        if n > 0 and native_libs.available():
+        if n > 0 and native_libs.available("zstd"):
             assert native_libs.zstd_decompress(s, n) == d
     # single segment ends where the input outgrows the window
     _, h = blocks_of(o.zstd_stream_compress(corpus((1 << 20) + 1)))
@@ -100,7 +100,7 @@ def test_from_four_mebibytes_on_the_stream_flushes_slides_and_goes_blind_for_sev
         elif full:
             assert t == 2 and seqs >= 1, (i, t, seqs)  # (the tiled corpus: long matches into the earlier copy, or thousands of short ones)
     assert o.decompress("zstd", s, n) == d
-    if native_libs.available():
+    if native_libs.available("zstd"):
         assert native_libs.zstd_decompress(s, n) == d
 
 

@@ -70,6 +70,7 @@ def main():
     json.dump(manifest, open(os.path.join(GOLD, "manifest.json"), "w"), indent=1, sort_keys=True)
     print("golden: %d sample slices (%d bytes), %d corpus files" % (len(index), len(blob), len(manifest)))
     full_corpus(o, sha)
+    java_tables()
 
 
 # T/benchmark/DataSet.java:28-89 (silesia/* and large/E.coli are not in the checkout)
@@ -124,6 +125,23 @@ def stream_manifest(o, sha, files):
         lines.append("%s\t0\t%d\tzstdstream\t%d\t%s" % (name, len(d), len(c), sha(c)))
     open(os.path.join(GOLD, "oracle_stream_manifest.tsv"), "w").write("\n".join(lines) + "\n")
     print("golden: stream manifest %d lines" % len(lines))
+
+
+def java_tables():
+    """tests/golden/java_tables.json: the literal decoding tables of the reference's Java decoders, so that the tests can hold the oracle's
+    and the kernels' tables against them without the checkout -- SnappyRawDecompressor.opLookupTable (256 entries) and the three predefined
+    FSE tables of ZstdFrameDecompressor.java:85-113 (LL, OF, ML: log2 size, newState, symbol, numberOfBits)."""
+    import re
+    java = os.path.join(REF, "src/main/java/io/airlift/compress/v3")
+    nums = lambda s: [int(x, 16) if x.lower().startswith("0x") else int(x) for x in re.findall(r"-?0x[0-9a-fA-F]+|-?\d+", s)]  # noqa: E731
+    text = open(os.path.join(java, "snappy/SnappyRawDecompressor.java")).read()
+    op = nums(re.search(r"opLookupTable\s*=\s*new\s+\w+\[\]\s*\{(.*?)\};", text, flags=re.S).group(1))
+    text = open(os.path.join(java, "zstd/ZstdFrameDecompressor.java")).read()
+    fse = [{"log2_size": int(log), "new_state": nums(ns), "symbol": nums(sym), "number_of_bits": nums(nb)} for log, ns, sym, nb in re.findall(
+        r"new FiniteStateEntropy\.Table\(\s*(\d+),\s*new int\[\] \{(.*?)\},\s*new byte\[\] \{(.*?)\},\s*new byte\[\] \{(.*?)\}\)", text, flags=re.S)]
+    assert len(op) == 256 and len(fse) == 3
+    json.dump({"snappy_op_lookup_table": op, "zstd_default_fse_tables": fse}, open(os.path.join(GOLD, "java_tables.json"), "w"))
+    print("golden: java_tables.json")
 
 
 if __name__ == "__main__":
