@@ -17,98 +17,16 @@
 #include <string>
 #include <vector>
 
-#include "achip_device.h"
+#include "achip_launch.h"
 
-namespace achip {
-hipError_t launch_lz4_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-int lz4_ring_group_for(int32_t nBlocks);
-int snappy_ring_group_for(int32_t nBlocks);
-hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats);
-int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
-// record arena per block of the two-pass decoders (8 bytes per record; lz4_decompress_v7.hip: text-like 64 KiB blocks make 6 000 .. 8 500 LZ4
-// records, 8 500 .. 11 500 Snappy records), and the least it is worth running them with (blocks that do not fit go to the ring decoder)
-constexpr int64_t LZ4_RECORD_BYTES_PER_BLOCK = 98304, LZ4_RECORD_BYTES_PER_BLOCK_MIN = 32768;
-constexpr int64_t SNAPPY_RECORD_BYTES_PER_BLOCK = 131072, SNAPPY_RECORD_BYTES_PER_BLOCK_MIN = 49152;
-hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats);
-hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32_t* mixedGroups, int32_t minBlocks);
-hipError_t launch_lz4_sequence_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-hipError_t launch_snappy_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-hipError_t launch_snappy_element_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int variant, int maxSrcLenHint, void* scratch);
-int64_t lz4_compress_scratch_bytes();
-extern int g_lz4_mem_waves;
-extern int g_lz4_tier_min_blocks;
-hipError_t launch_snappy_compress(const BatchArgs& a, hipStream_t stream, int variant, void* scratch, bool fan);
-hipError_t launch_blit(void* dst, const void* src, int64_t bytes, int workgroups, hipStream_t stream);
-int64_t snappy_compress_scratch_bytes(int32_t nBlocks);
-hipError_t launch_zstd_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int variant, int32_t tileMax, const ZstdMbProvider* mbp);
-hipError_t launch_zstd_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int variant);
-hipError_t launch_zstd_stream_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int chunked);
-int64_t zstd_decompress_scratch_bytes(int32_t nBlocks, int32_t tileMax);
-int64_t zstd_compress_scratch_bytes(int32_t nBlocks);
-hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux);
-int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams);
-hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant);
-int64_t snappyframed_compress_scratch_bytes(int32_t nStreams);
-hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux);
-int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize);
-hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize);
-int64_t hadoop_compress_scratch_bytes(int32_t nStreams);
-extern int g_zstd_pipe_exec;
-extern int g_zstd_seq_waves;
-extern int g_zstd_lit_items;
-extern int g_snappy_mem_waves;
-int64_t zstd_ostream_state_bytes();
-int64_t zstd_ostream_slab_bytes();
-hipError_t launch_zstd_ostream_step(hipStream_t stream, void* state, void* slab, const uint8_t* buf, int32_t offset, int32_t chunk, int32_t closing, uint8_t* out, int32_t outCap);
-int64_t zstd_stream_carry_bytes();
-void zstd_stream_carry_init(void* hostCarry);
-int64_t zstd_stream_step_scratch_bytes(int32_t blocks);
-hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t scratchBytes, void* carryDev, const uint8_t* dSrc, int32_t srcLen, int32_t blocks, uint8_t* dOut,
-                                   int32_t startPos, int32_t outLimit, int32_t closing, int32_t hasChecksum, uint32_t expected, int32_t* result);
-extern int g_lz4_parse_mode;
-extern int g_snappy_parse_mode;
-hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux);
-int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant);
-hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes);
-int64_t lz4frame_compress_scratch_bytes(int32_t items, bool least);
-hipError_t launch_mix_gather(const int32_t* perm, int32_t n, const BatchArgs& a, int64_t* gSrcOff, int32_t* gSrcLen, int64_t* gDstOff, int32_t* gDstCap, hipStream_t stream);
-hipError_t launch_mix_scatter(const int32_t* perm, int32_t n, const int32_t* gOutLen, const int32_t* gStatus, const int64_t* gErr, const BatchArgs& a, hipStream_t stream);
-hipError_t launch_xxh64_batch(const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t n, uint64_t seed, int64_t* out, hipStream_t stream);
-hipError_t launch_xxh32_batch(const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t n, uint32_t seed, int32_t* out, hipStream_t stream);
-}  // namespace achip
-
-// What achip_ctx_set_option sets (and the bookkeeping of the last launch): a context's settings as a value, so that the helper contexts a mixed
-// batch runs its buckets on (mix_lane) can take them over whole.
-struct achip_options {
+// A context: its settings (achip_settings.h: what achip_ctx_set_option writes) and the state it owns.
+struct achip_ctx : achip::Settings {
     int device = 0;
-    int lz4dGroup = 0;       // ring decoder, lanes per block: 0 = by the batch size (4 from 32 768 blocks on -- the headline's form --, 16 below, 64 up to 4 096: lz4_ring_group_for), else 1 .. 64
-    int snappydGroup = 0;    // likewise (64 up to 2 048 blocks, 16 below 16 384, 4 above: snappy_ring_group_for)
-    int lz4dAutoMinBlocks = 4096;  // auto mode probes batches from this size on (smaller ones always take the rings)
-    int lz4dVariant = 5;     // 5 = chosen on the device per batch (default: DESIGN 4c), 1 = LDS rings, a lane group per block (lz4_decompress_v2.hip), 7 = two passes: parse to records + a wavefront per block (lz4_decompress_v7.hip).  (4 / 6, a lane per block, lost to 7 on every batch they were built for -- 300 .. 330 GiB/s against 515 on corpus -- and were removed in round 4.)
-    int snappydVariant = 5;  // 5 auto, 1 rings (snappy_decompress_v2.hip), 7 two passes (snappy_decompress_v5.hip), as for LZ4
     int smallBatchHint = 0;      // set by the host-pointer path for ONE launch: what a look at the first block's tokens says -- 1 short sequences, 2 long ones (0: nobody looked)
-    int latencyMaxBlocks = 256;  // batches of at most this many blocks (a single block!) take the ring decoders' latency class: a wavefront and 128 KiB of LDS history per block
-    int ringClass = 0;       // 0 = compact rings, 1 = large rings
-    int lz4cVariant = 4;     // 4 = many matches per window of 64 positions (lz4_compress_mw.h; default since round 3: 25.8 against 18.2 GiB/s on corpus, 100 against 111 on fragments), 0 = serial probes, 1 = 64 probes per step (batch).  (3, the batch over an LDS input window, measured 17.2 against 18.2 GiB/s on corpus in round 3: removed)
-    int snappycVariant = 4;  // THE DEFAULT IS 4 = two tiers, many matches per window (snappy_compress_mw.h; since round 3: 22.0 against 8.3 GiB/s on corpus, 65 against 74 on fragments); tested non-default variants: 0 = serial probes, 1 = 64 probes per step (batch), 2 = batch in two tiers: tables in LDS and in global memory.  (3, variant 2 over an LDS input window, measured 8.3 against 7.6 GiB/s for 2 and a third of variant 4: removed in round 4.)
-    int zstddVariant = 1;  // 1 = five-stage pipeline (+ one-kernel decoder for its fallback list), 0 = one-kernel decoder only
-    int zstdcVariant = 3;  // match kernel in window form (zstd_dfast_mw.h) + entropy kernel
-    int hadoopBufferSize = 262144;        // Hadoop block streams: the streams' buffer size (Lz4HadoopStreams.java:30; io.compression.codec.*.buffersize)
-    int lz4FrameDecompressVariant = 2;    // 2 = chosen per call by a probe of the sequence lengths (default: 75 / 13.4 GiB/s on fragments / corpus frames); 0 = a wavefront per item (75 / 7.8); 1 = the frames' blocks as one batch through the two-pass block decoder (22 / 13.4)
-    int hadoopDecompressVariant = 3;      // 3 = chunk list, the block decoder chosen per call by a probe of the sequence lengths (default); 1 = always the rings; 2 = always the two-pass decoders; 0 = one wavefront per stream (profiles/r03_notes.md)
-    int snappyFramedCompressVariant = 1;  // framed writer: 1 = block list + two-tier block encoder + compaction (default), 0 = one wavefront per stream
-    int snappyFramedVariant = 3;  // framed reader: 3 = chunk list, the block decoder chosen per call by a probe of the element lengths (default); 1 = always the rings; 2 = always the two-pass decoder; 0 = one wavefront per stream
-    int zstdTile = 65536;    // items per pass of the Zstd decode pipeline (halved automatically when its scratch cannot be allocated)
-    int zstdStreamChunked = 1;     // 1: the stream writer takes streams from 4 MiB on as well (chunks flushed before close(), window slides: zstd_stream.hip; byte-identical with
-                                   // the test suite's CPU restatement under tools/hostemu, not yet run on a GPU); 0: it refuses them (INVALID_ARGUMENT / ACHIP_D_UNSUPPORTED)
-    int zstdStreamBlocks = 65536;  // 128 KiB blocks a pass of the pipeline's multi-block stages has room for (0: multi-block frames take the one-kernel decoder); ~20 GB of scratch, allocated when a batch first holds such frames (halved as often as it takes when the device cannot give that)
-    int ringPad = 80;        // 64 bytes of far-match staging + 16: consecutive blocks start on different LDS banks
-    int scratchPoison = -1;
     int32_t lastZstddBlocks = 0;  // achip_ctx_get_stat
     int lastZstddVariant = 0;
     int32_t lastAutoBlocks = 0;  // ... and this many blocks
-    bool lastAutoIsLz4 = false;
+    int lastAutoFam = 0;         // ... of this codec family (kBlockCodecs)
     bool lastTwopass = false;   // the last decode was a two-pass one: its arena header leads the scratch
     bool lastLz4dAuto = false;  // the last LZ4 decode ran in auto mode: its probe count leads the scratch
     // Auto mode remembers (round 6): a call's probe statistics come back to pinned memory behind its kernels, without a wait; while the batches that follow have its
@@ -118,7 +36,6 @@ struct achip_options {
     // many calls as it takes the first new statistics to arrive: one, for a caller that waits for its results.  (A first version probed one call in sixteen
     // and ran the rest blind: bench.py's own extras -- fragments, then text, same shape, same buffers -- decoded text on the rings for a whole measurement, 148
     // against 377 GiB/s.)  decompress.auto_remember = 0: both decoders are launched in every call, as until round 5.
-    int autoRemember = 1;
     int32_t* autoPinned = nullptr;     // 8 words: the probe statistics of the call in flight
     hipEvent_t autoEv = nullptr;
     bool autoInFlight = false;
@@ -131,14 +48,6 @@ struct achip_options {
     const void* autoSrc[2] = {nullptr, nullptr};
     const void* autoDst[2] = {nullptr, nullptr};
     int lastRemembered = -1;           // the last decode ran on a remembered choice: that choice (decompress.choice reports it)
-    int maxSrcLenHint = 0;
-    int snappyFan = 1;     // snappy.compress.fan: 1 = the sub-blocks of buffers beyond 64 KiB are work units of their own (default), 0 = a buffer is one wavefront's work
-    int execVariant = 2;     // two-pass decoders: 2 = the executor of achip_seqexec2.h (the only one)
-    int mixConcurrent = 1;   // mixed batches: 1 = the three codec families side by side, each on a stream (and scratch) of its own -- a bucket's tail is a few long
-                             // serial chains on a few CUs (a 10 MB file as ONE block: 0.4 s of one wavefront) --, 0 = every bucket in turn on the context's stream
-};
-
-struct achip_ctx : achip_options {
     hipStream_t stream = nullptr;
     // scratch for the zstd pipeline (grown on demand)
     void* scratch = nullptr;
@@ -158,11 +67,7 @@ struct achip_ctx : achip_options {
     hipEvent_t mixUploaded = nullptr;  // the last permutation upload: the pinned buffer may be rewritten once it has completed
     // host-pointer batches (achip_batch_host / achip_mixed_batch_host): up to four staging slots, chunks pipelined over three streams, gather and
     // scatter on copy pools of their own
-    static constexpr int kHostSlots = 8;
-    int hostLookMaxBlocks = 0;  // host.look_max_blocks: chunks of up to this many blocks have their first tokens looked at on the host (long sequences: the rings at 64 lanes)
-    int hostCopyLowPriority = 1;  // host.copy_priority: 1 = the pipeline's copy streams at the lowest stream priority (to be set before the first host-pointer batch)
-    int hostRamp = 1;  // host.ramp: 1 = smaller chunks at a batch's start and end (default), 0 = chunks of host.chunk_bytes throughout
-    int hostSlots = 8;  // host.slots: staging slots the host-pointer pipeline uses (2 .. kHostSlots; round 6: 8 -- with 4 the gather thread waited for a slot 20 of a call's 34 ms)
+    static constexpr int kHostSlots = 8;  // (the most host.slots accepts)
     struct CopyPool* pool = nullptr;     // gather: the caller's inputs -> pinned slot
     struct CopyPool* poolOut = nullptr;  // scatter: pinned slot -> the caller's outputs
     uint8_t* slotHost[kHostSlots] = {};  // pinned
@@ -171,15 +76,6 @@ struct achip_ctx : achip_options {
     int slotCount = 0;
     hipStream_t copyIn = nullptr, copyOut = nullptr;
     hipEvent_t evH2D[kHostSlots] = {}, evK[kHostSlots] = {}, evD2H[kHostSlots] = {};
-    int hostBlit = 0;          // host.blit: bit 0 = the pipeline's uploads by a copy kernel instead of hipMemcpyAsync, bit 1 = its downloads
-    int hostBlitGroups = 128;  // host.blit_groups: workgroups of that kernel
-    int64_t hostChunkBytes = 192 << 20;   // staging bytes (inputs + output capacities) per pipeline chunk: ~2000 blocks of 64 KiB -- a chunk's kernels
-                                         // take a block's serial chain (~1-2 ms) however few blocks it holds, so a chunk must be worth that long on the
-                                         // link.  Round 6 (profiles/r06_hostsweep.txt, r06_host_timeline.txt): with eight slots, the copy streams at the lowest
-                                         // priority and smaller chunks at both ends 192 MiB gives 40-42 GiB/s where round 5's 96 MiB over four slots gave 26-30
-                                         // on the same box (the 48 MiB of rounds 1-4 over two slots: 8.7)
-    int hostCopyThreads = 0;             // per copy pool; 0 = hardware threads / 16, 2 .. 8 (4 and 8 measured best; 32 no better: the scatter is
-                                         // bound by the host's memory system, not by the thread count)
     // achip_ctx_get_stat("host.*"): where the last host-pointer batch of several chunks spent its wall time (microseconds)
     int64_t hostGatherUs = 0, hostScatterUs = 0, hostWaitSlotUs = 0, hostWaitDownloadUs = 0, hostChunks = 0, hostTotalUs = 0;
     // staging for the one-shot hashers (grown on demand)
@@ -255,17 +151,40 @@ int64_t few_blocks_record_bytes(int32_t nBlocks, int64_t perBlock)
     return std::max<int64_t>(perBlock, ((1LL << 30) / nBlocks) & ~4095LL);
 }
 
-// Auto mode's memory (achip_ctx::autoRemember).  auto_remembered: the decoder to launch alone for this batch (0 rings, 3 two passes), or -1: launch both.  First takes
+// LZ4 and Snappy block decoding: one policy (launch_block_decode), a row per codec family -- 0 LZ4, 1 Snappy.
+struct BlockCodec {
+    hipError_t (*rings)(const achip::BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
+    hipError_t (*twopass)(const achip::BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats,
+                          const achip::KernelSettings& ks);
+    hipError_t (*sample)(const achip::BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);  // auto mode's probe of the lengths
+    int (*groupFor)(int32_t nBlocks);  // ring decoder lanes per block by the batch size
+    int64_t recordBytes, recordBytesMin;  // the two-pass decoder's record arena per block
+    int32_t shortLimit;                   // sequences (LZ4) / elements (Snappy) shorter than this are short ones (lz4_pick)
+};
+const BlockCodec kBlockCodecs[2] = {
+    {achip::launch_lz4_decompress_rings, achip::launch_lz4_decompress_twopass, achip::launch_lz4_sequence_sample, achip::lz4_ring_group_for,
+     achip::LZ4_RECORD_BYTES_PER_BLOCK, achip::LZ4_RECORD_BYTES_PER_BLOCK_MIN, 12},
+    {achip::launch_snappy_decompress_rings, achip::launch_snappy_decompress_twopass, achip::launch_snappy_element_sample, achip::snappy_ring_group_for,
+     achip::SNAPPY_RECORD_BYTES_PER_BLOCK, achip::SNAPPY_RECORD_BYTES_PER_BLOCK_MIN, 6},
+};
+
+// The decoder auto mode picks from a call's probe statistics (the first six words) for a batch of `nBlocks` blocks of family `fam`: 3 two passes (a mixed
+// or a short-sequence batch), 0 rings.  The rule of lz4_pick (achip_device.h), on the host.
+int auto_pick(const int32_t* v, int32_t nBlocks, int fam)
+{
+    const bool mixed = (int64_t)v[0] * 4 > (nBlocks + 15) / 16;
+    const bool pooledShort = v[1] > 0 && (int64_t)v[2] < kBlockCodecs[fam].shortLimit * (int64_t)v[1];
+    const bool isShort = v[5] > 0 ? (int64_t)v[4] * 3 > (int64_t)v[5] : pooledShort;
+    return (mixed || isShort) ? 3 : 0;
+}
+
+// Auto mode's memory (achip_ctx::autoPinned ...).  auto_remembered: the decoder to launch alone for this batch (0 rings, 3 two passes), or -1: launch both.  First takes
 // in what an earlier call sent home, if it has arrived (an event query, never a wait).
 int auto_remembered(achip_ctx* ctx, int fam, const achip::BatchArgs& a)
 {
     if (ctx->autoInFlight && hipEventQuery(ctx->autoEv) == hipSuccess) {
-        const int32_t* v = ctx->autoPinned;
         const int pf = ctx->autoPendingFam;
-        const bool mixed = (int64_t)v[0] * 4 > (ctx->autoPendingBlocks + 15) / 16;  // the rule of lz4_pick (achip_device.h)
-        const bool pooledShort = v[1] > 0 && (int64_t)v[2] < (pf == 0 ? 12 : 6) * (int64_t)v[1];
-        const bool isShort = v[5] > 0 ? (int64_t)v[4] * 3 > (int64_t)v[5] : pooledShort;
-        ctx->autoChoice[pf] = (mixed || isShort) ? 3 : 0;
+        ctx->autoChoice[pf] = auto_pick(ctx->autoPinned, ctx->autoPendingBlocks, pf);
         ctx->autoBlocks[pf] = ctx->autoPendingBlocks;
         ctx->autoSrc[pf] = ctx->autoPendingSrc;
         ctx->autoDst[pf] = ctx->autoPendingDst;
@@ -439,6 +358,61 @@ int32_t ensure_stage(achip_ctx* ctx, int64_t bytes)
     return 0;
 }
 
+int32_t launch_block_decode(achip_ctx* ctx, const achip::BatchArgs& a, int fam, int variant, int group)
+{
+    const BlockCodec& c = kBlockCodecs[fam];
+    const int groupSize = group > 0 ? group : (a.nBlocksDev != nullptr ? 4 : c.groupFor(a.nBlocks));
+    auto launched = [](hipError_t e) { return e != hipSuccess ? device_failure("kernel launch", e) : 0; };
+    if (variant == 5 && a.nBlocks >= ctx->lz4dAutoMinBlocks) {
+        // auto: the choice is made on the device (no host round trip): probes count the mixed 16-block groups and sample the
+        // sequence lengths, every candidate decoder is launched and the ones not chosen return at once.  Mixed or short-sequence
+        // batches go to the two-pass decoder (parse to records + a wavefront per block), the rest to the rings.
+        // scratch: [probe statistics: the first 4 KiB][two-pass header, meta, arena]
+        const int32_t r = ensure_twopass_scratch(ctx, 4096, a.nBlocks, c.recordBytes, c.recordBytesMin);
+        if (r < 0) return r;
+        if (r == 0) {  // no room for records on this device right now: the rings alone
+            return launched(c.rings(a, ctx->stream, groupSize, ctx->ringClass, nullptr));
+        }
+        int32_t* stats = (int32_t*)ctx->scratch;
+        ctx->lastZstddBlocks = 0;
+        const int remembered = auto_remembered(ctx, fam, a);
+        ctx->lastLz4dAuto = true;
+        ctx->lastAutoBlocks = a.nBlocks;
+        ctx->lastAutoFam = fam;
+        hipError_t e = achip::launch_lz4_mixed_groups(a, ctx->stream, stats, 0);
+        if (e == hipSuccess) e = hipMemsetAsync(stats + 3, 1, 1, ctx->stream);  // stats[3] = 1: the two-pass scheme (achip_device.h lz4_pick)
+        if (e == hipSuccess) e = c.sample(a, ctx->stream, stats, 0, c.shortLimit);
+        // (remembered: that decoder alone and whatever this call's probes say -- they are for the calls to come)
+        if (e == hipSuccess && remembered != 3) e = c.rings(a, ctx->stream, groupSize, ctx->ringClass, remembered == 0 ? nullptr : stats);
+        if (remembered != 0) {
+            ctx->lastTwopass = true;
+            if (e == hipSuccess) e = c.twopass(a, ctx->stream, (uint8_t*)ctx->scratch + 4096, ctx->scratchBytes - 4096, groupSize, ctx->ringClass, remembered == 3 ? nullptr : stats, ctx->kernel);
+        }
+        if (e == hipSuccess) auto_send_home(ctx, fam, a, stats);
+        return launched(e);
+    }
+    // FEW blocks (at most decompress.latency_max_blocks; a single block is the literal Lz4HipDecompressor.decompress): nothing hides a lone block's chain,
+    // so the choice is by what one 64 KiB block costs (profiles/r05_single_block_latency.txt): long sequences -- the ring decoders' latency class
+    // (0.64 ms; the two passes 1.0); short ones or unknown -- the two passes with the wavefront-per-block parser (text 1.3 ms; the latency class 5.1;
+    // Snappy: one 64 KiB text block 7.2 ms with a lane parsing it)
+    // ... and so does every batch below the size auto mode probes from (4 096): such a batch of LARGE blocks -- files as single blocks, a frame's 4 MiB blocks --
+    // is the compact rings' worst case (four lanes per block, 83 % of a text block's matches a memory round trip each: the 263-item LZ4 bucket of the mixed corpus batch
+    // took 526 ms, its two largest files alone through the two passes 80), and on long sequences the two passes cost about what the rings do at these sizes
+    const bool fewBlocks = variant == 5 && a.nBlocks < ctx->lz4dAutoMinBlocks && a.nBlocksDev == nullptr && a.only == nullptr;
+    const int hint = ctx->smallBatchHint;
+    ctx->smallBatchHint = 0;
+    if (variant == 7 || (fewBlocks && hint != 2)) {  // two passes: parse to records, a wavefront per block executes them (lz4_decompress_v7.hip, snappy_decompress_v5.hip)
+        const int32_t r = ensure_twopass_scratch(ctx, 0, a.nBlocks, few_blocks_record_bytes(a.nBlocks, c.recordBytes), c.recordBytesMin);
+        if (r < 0) return r;
+        if (r == 0) {
+            return launched(c.rings(a, ctx->stream, groupSize, ctx->ringClass, nullptr));
+        }
+        ctx->lastTwopass = true;
+        return launched(c.twopass(a, ctx->stream, ctx->scratch, ctx->scratchBytes, groupSize, ctx->ringClass, nullptr, ctx->kernel));
+    }
+    return launched(c.rings(a, ctx->stream, groupSize, ctx->ringClass == 0 && a.nBlocks <= ctx->latencyMaxBlocks ? 3 : ctx->ringClass, nullptr));
+}
+
 int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
 {
     if (!ctx) {
@@ -459,110 +433,16 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
     ctx->lastTwopass = false;
     ctx->lastRemembered = -1;
     switch (op) {
-        case ACHIP_OP_LZ4_DECOMPRESS: {
-            const int lz4Group = ctx->lz4dGroup > 0 ? ctx->lz4dGroup : (a.nBlocksDev != nullptr ? 4 : achip::lz4_ring_group_for(a.nBlocks));
-            if (ctx->lz4dVariant == 5 && a.nBlocks >= ctx->lz4dAutoMinBlocks) {
-                // auto: the choice is made on the device (no host round trip): probes count the mixed 16-block groups and sample the
-                // sequence lengths, every candidate decoder is launched and the ones not chosen return at once.  Mixed or short-sequence
-                // batches go to the two-pass decoder (parse to records + a wavefront per block), the rest to the rings.
-                // scratch: [probe statistics: the first 4 KiB][two-pass header, meta, arena]
-                const int32_t r = ensure_twopass_scratch(ctx, 4096, a.nBlocks, achip::LZ4_RECORD_BYTES_PER_BLOCK, achip::LZ4_RECORD_BYTES_PER_BLOCK_MIN);
-                if (r < 0) return r;
-                if (r == 0) {  // no room for records on this device right now: the rings alone
-                    e = achip::launch_lz4_decompress_rings(a, ctx->stream, lz4Group, ctx->ringClass, nullptr);
-                    break;
-                }
-                int32_t* stats = (int32_t*)ctx->scratch;
-                ctx->lastZstddBlocks = 0;
-                const int remembered = auto_remembered(ctx, 0, a);
-                ctx->lastLz4dAuto = true;
-                ctx->lastAutoBlocks = a.nBlocks;
-                ctx->lastAutoIsLz4 = true;
-                e = achip::launch_lz4_mixed_groups(a, ctx->stream, stats, 0);
-                if (e == hipSuccess) e = hipMemsetAsync(stats + 3, 1, 1, ctx->stream);  // stats[3] = 1: the two-pass scheme (achip_device.h lz4_pick)
-                if (e == hipSuccess) e = achip::launch_lz4_sequence_sample(a, ctx->stream, stats, 0, 12);
-                // (remembered: that decoder alone and whatever this call's probes say -- they are for the calls to come)
-                if (e == hipSuccess && remembered != 3) e = achip::launch_lz4_decompress_rings(a, ctx->stream, lz4Group, ctx->ringClass, remembered == 0 ? nullptr : stats);
-                if (remembered != 0) {
-                    ctx->lastTwopass = true;
-                    if (e == hipSuccess) e = achip::launch_lz4_decompress_twopass(a, ctx->stream, (uint8_t*)ctx->scratch + 4096, ctx->scratchBytes - 4096, lz4Group, ctx->ringClass, ctx->execVariant, remembered == 3 ? nullptr : stats);
-                }
-                if (e == hipSuccess) auto_send_home(ctx, 0, a, stats);
-                break;
-            }
-            // FEW blocks (at most decompress.latency_max_blocks; a single block is the literal Lz4HipDecompressor.decompress): nothing hides a lone block's chain,
-            // so the choice is by what one 64 KiB block costs (profiles/r05_single_block_latency.txt): long sequences -- the ring decoders' latency class
-            // (0.64 ms; the two passes 1.0); short ones or unknown -- the two passes with the wavefront-per-block parser (text 1.3 ms; the latency class 5.1)
-            // ... and so does every batch below the size auto mode probes from (4 096): such a batch of LARGE blocks -- files as single blocks, a frame's 4 MiB blocks --
-            // is the compact rings' worst case (four lanes per block, 83 % of a text block's matches a memory round trip each: the 263-item LZ4 bucket of the mixed corpus batch
-            // took 526 ms, its two largest files alone through the two passes 80), and on long sequences the two passes cost about what the rings do at these sizes
-            const bool fewBlocks = ctx->lz4dVariant == 5 && a.nBlocks < ctx->lz4dAutoMinBlocks && a.nBlocksDev == nullptr && a.only == nullptr;
-            const int hint = ctx->smallBatchHint;
-            ctx->smallBatchHint = 0;
-            if (ctx->lz4dVariant == 7 || (fewBlocks && hint != 2)) {  // two passes: parse to records, a wavefront per block executes them (lz4_decompress_v7.hip)
-                const int32_t r = ensure_twopass_scratch(ctx, 0, a.nBlocks, few_blocks_record_bytes(a.nBlocks, achip::LZ4_RECORD_BYTES_PER_BLOCK), achip::LZ4_RECORD_BYTES_PER_BLOCK_MIN);
-                if (r < 0) return r;
-                if (r == 0) {
-                    e = achip::launch_lz4_decompress_rings(a, ctx->stream, lz4Group, ctx->ringClass, nullptr);
-                    break;
-                }
-                ctx->lastTwopass = true;
-                e = achip::launch_lz4_decompress_twopass(a, ctx->stream, ctx->scratch, ctx->scratchBytes, lz4Group, ctx->ringClass, ctx->execVariant, nullptr);
-                break;
-            }
-            e = achip::launch_lz4_decompress_rings(a, ctx->stream, lz4Group, ctx->ringClass == 0 && a.nBlocks <= ctx->latencyMaxBlocks ? 3 : ctx->ringClass, nullptr);
-            break;
-        }
+        case ACHIP_OP_LZ4_DECOMPRESS: return launch_block_decode(ctx, a, 0, ctx->lz4dVariant, ctx->lz4dGroup);
+        case ACHIP_OP_SNAPPY_DECOMPRESS: return launch_block_decode(ctx, a, 1, ctx->snappydVariant, ctx->snappydGroup);
         case ACHIP_OP_LZ4_COMPRESS: {
-            if (ctx->lz4cVariant == 4 && achip::g_lz4_mem_waves > 0) {  // (the two-tier kernel's table slabs)
+            // the two-tier kernel's table slabs, for a batch that takes it (the launcher takes it only with this scratch in hand)
+            const achip::KernelSettings& ks = ctx->kernel;
+            if (ctx->lz4cVariant == 4 && ks.lz4MemWaves > 0 && a.nBlocks >= ks.lz4TierMinBlocks) {
                 const int32_t r = ensure_scratch(ctx, achip::lz4_compress_scratch_bytes());
                 if (r < 0) return r;
             }
-            e = achip::launch_lz4_compress(a, ctx->stream, ctx->lz4cVariant, ctx->maxSrcLenHint, ctx->scratch);
-            break;
-        }
-        case ACHIP_OP_SNAPPY_DECOMPRESS: {
-            const int snappyGroup = ctx->snappydGroup > 0 ? ctx->snappydGroup : (a.nBlocksDev != nullptr ? 4 : achip::snappy_ring_group_for(a.nBlocks));
-            if (ctx->snappydVariant == 5 && a.nBlocks >= ctx->lz4dAutoMinBlocks) {  // auto, as for LZ4
-                const int32_t r = ensure_twopass_scratch(ctx, 4096, a.nBlocks, achip::SNAPPY_RECORD_BYTES_PER_BLOCK, achip::SNAPPY_RECORD_BYTES_PER_BLOCK_MIN);
-                if (r < 0) return r;
-                if (r == 0) {
-                    e = achip::launch_snappy_decompress_rings(a, ctx->stream, snappyGroup, ctx->ringClass, nullptr);
-                    break;
-                }
-                int32_t* stats = (int32_t*)ctx->scratch;
-                ctx->lastZstddBlocks = 0;
-                const int remembered = auto_remembered(ctx, 1, a);
-                ctx->lastLz4dAuto = true;
-                ctx->lastAutoBlocks = a.nBlocks;
-                ctx->lastAutoIsLz4 = false;
-                e = achip::launch_lz4_mixed_groups(a, ctx->stream, stats, 0);
-                if (e == hipSuccess) e = hipMemsetAsync(stats + 3, 1, 1, ctx->stream);
-                if (e == hipSuccess) e = achip::launch_snappy_element_sample(a, ctx->stream, stats, 0, 6);
-                if (e == hipSuccess && remembered != 3) e = achip::launch_snappy_decompress_rings(a, ctx->stream, snappyGroup, ctx->ringClass, remembered == 0 ? nullptr : stats);
-                if (remembered != 0) {
-                    ctx->lastTwopass = true;
-                    if (e == hipSuccess) e = achip::launch_snappy_decompress_twopass(a, ctx->stream, (uint8_t*)ctx->scratch + 4096, ctx->scratchBytes - 4096, snappyGroup, ctx->ringClass, ctx->execVariant, remembered == 3 ? nullptr : stats);
-                }
-                if (e == hipSuccess) auto_send_home(ctx, 1, a, stats);
-                break;
-            }
-            // (few blocks, and every batch below the size auto mode probes from: as for LZ4 -- the two passes with the wavefront-per-block parser unless the host looked and
-            // saw long elements, which take the latency class: one 64 KiB text block 7.2 ms with a lane parsing it, profiles/r05_single_block_latency.txt for what it is now)
-            const bool fewSnappy = ctx->snappydVariant == 5 && a.nBlocks < ctx->lz4dAutoMinBlocks && a.nBlocksDev == nullptr && a.only == nullptr && ctx->smallBatchHint != 2;
-            ctx->smallBatchHint = 0;
-            if (ctx->snappydVariant == 7 || fewSnappy) {  // two passes (snappy_decompress_v5.hip)
-                const int32_t r = ensure_twopass_scratch(ctx, 0, a.nBlocks, few_blocks_record_bytes(a.nBlocks, achip::SNAPPY_RECORD_BYTES_PER_BLOCK), achip::SNAPPY_RECORD_BYTES_PER_BLOCK_MIN);
-                if (r < 0) return r;
-                if (r == 0) {
-                    e = achip::launch_snappy_decompress_rings(a, ctx->stream, snappyGroup, ctx->ringClass, nullptr);
-                    break;
-                }
-                ctx->lastTwopass = true;
-                e = achip::launch_snappy_decompress_twopass(a, ctx->stream, ctx->scratch, ctx->scratchBytes, snappyGroup, ctx->ringClass, ctx->execVariant, nullptr);
-                break;
-            }
-            e = achip::launch_snappy_decompress_rings(a, ctx->stream, snappyGroup, ctx->ringClass == 0 && a.nBlocks <= ctx->latencyMaxBlocks ? 3 : ctx->ringClass, nullptr);
+            e = achip::launch_lz4_compress(a, ctx->stream, ctx->lz4cVariant, ctx->maxSrcLenHint, ctx->scratch, ctx->scratchBytes, ks);
             break;
         }
         case ACHIP_OP_SNAPPY_COMPRESS: {
@@ -571,7 +451,7 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
                 if (r < 0) return r;
             }
             // (buffers beyond 64 KiB: their independent sub-blocks side by side -- unless the caller, or the host-pointer path that has seen the lengths, says there are none)
-            e = achip::launch_snappy_compress(a, ctx->stream, ctx->snappycVariant, ctx->scratch, ctx->snappyFan != 0 && !(ctx->maxSrcLenHint > 0 && ctx->maxSrcLenHint <= 65536));
+            e = achip::launch_snappy_compress(a, ctx->stream, ctx->snappycVariant, ctx->scratch, ctx->snappyFan != 0 && !(ctx->maxSrcLenHint > 0 && ctx->maxSrcLenHint <= 65536), ctx->kernel);
             break;
         }
         case ACHIP_OP_ZSTD_DECOMPRESS: {
@@ -584,7 +464,7 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
             }
             if (r < 0) return r;
             const achip::ZstdMbProvider mbp{zstd_mb_scratch, ctx, ctx->zstdStreamBlocks};
-            e = achip::launch_zstd_decompress(a, ctx->stream, ctx->scratch, ctx->scratchBytes, ctx->zstddVariant, ctx->zstdTile, ctx->zstdStreamBlocks >= 16 ? &mbp : nullptr);
+            e = achip::launch_zstd_decompress(a, ctx->stream, ctx->scratch, ctx->scratchBytes, ctx->zstddVariant, ctx->zstdTile, ctx->zstdStreamBlocks >= 16 ? &mbp : nullptr, ctx->kernel);
             ctx->lastZstddBlocks = a.nBlocks;
             ctx->lastZstddVariant = ctx->zstddVariant;
             break;
@@ -593,14 +473,14 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
             int32_t r = ensure_scratch(ctx, achip::lz4frame_decompress_scratch_bytes(a.nBlocks, ctx->lz4FrameDecompressVariant));
             if (r < 0) return r;
             const achip::AuxScratch aux{zstd_mb_scratch, ctx};
-            e = achip::launch_lz4frame_decompress(a, ctx->stream, ctx->scratch, ctx->lz4FrameDecompressVariant, &aux);
+            e = achip::launch_lz4frame_decompress(a, ctx->stream, ctx->scratch, ctx->lz4FrameDecompressVariant, &aux, ctx->kernel);
             break;
         }
         case ACHIP_OP_SNAPPYFRAMED_DECOMPRESS: {
             int32_t r = ensure_scratch(ctx, achip::snappyframed_decompress_scratch_bytes(a.nBlocks));
             if (r < 0) return r;
             const achip::AuxScratch aux{zstd_mb_scratch, ctx};
-            e = achip::launch_snappyframed_decompress(a, ctx->stream, ctx->scratch, ctx->snappyFramedVariant, &aux);
+            e = achip::launch_snappyframed_decompress(a, ctx->stream, ctx->scratch, ctx->snappyFramedVariant, &aux, ctx->kernel);
             break;
         }
         case ACHIP_OP_SNAPPYFRAMED_COMPRESS: {
@@ -614,7 +494,7 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
             int32_t r = ensure_scratch(ctx, achip::hadoop_decompress_scratch_bytes(a.nBlocks, ctx->hadoopBufferSize));
             if (r < 0) return r;
             const achip::AuxScratch aux{zstd_mb_scratch, ctx};  // (the context's second, lazily grown buffer: shared with the Zstd multi-block stages)
-            e = achip::launch_hadoop_decompress(a, ctx->stream, ctx->scratch, op == ACHIP_OP_SNAPPYHADOOP_DECOMPRESS, ctx->hadoopBufferSize, ctx->hadoopDecompressVariant, &aux);
+            e = achip::launch_hadoop_decompress(a, ctx->stream, ctx->scratch, op == ACHIP_OP_SNAPPYHADOOP_DECOMPRESS, ctx->hadoopBufferSize, ctx->hadoopDecompressVariant, &aux, ctx->kernel);
             break;
         }
         case ACHIP_OP_LZ4HADOOP_COMPRESS:
@@ -1020,173 +900,17 @@ int32_t achip_ctx_synchronize(achip_ctx* ctx)
 int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value)
 {
     if (!ctx || !name) return bad_argument("ctx/name is null");
-    std::string k(name);
-    auto pow2 = [](int64_t v) { return v >= 1 && v <= 64 && (v & (v - 1)) == 0; };
-    if (k == "lz4.decompress.group") {
-        if (!pow2(value)) return bad_argument("group size must be a power of two in 1..64");
-        ctx->lz4dGroup = (int)value;
+    achip::Settings next = *ctx;
+    const char* refusal = nullptr;
+    switch (achip::apply(next, name, value, &refusal)) {
+        case achip::Applied::Unknown: return bad_argument("unknown option");
+        case achip::Applied::BadValue: return bad_argument(refusal);
+        case achip::Applied::Ok: break;
     }
-    else if (k == "snappy.decompress.group") {
-        if (value != 0 && !pow2(value)) return bad_argument("snappy.decompress.group: 0 (by the batch size) or a power of two in 1..64");
-        ctx->snappydGroup = (int)value;
-    }
-    else if (k == "lz4.decompress.variant") {
-        if (value != 1 && value != 5 && value != 7) return bad_argument("lz4.decompress.variant: 1 rings, 7 two passes, 5 auto");
-        ctx->lz4dVariant = (int)value;
-    }
-    else if (k == "lz4.decompress.auto_min_blocks") {
-        if (value < 16 || value > 0x7FFFFFFF) return bad_argument("lz4.decompress.auto_min_blocks must be at least 16");
-        ctx->lz4dAutoMinBlocks = (int)value;
-    }
-    else if (k == "snappy.decompress.variant") {
-        if (value != 1 && value != 5 && value != 7) return bad_argument("snappy.decompress.variant: 1 rings, 7 two passes, 5 auto");
-        ctx->snappydVariant = (int)value;
-    }
-    else if (k == "decompress.ring_class") {
-        if (value < 0 || value > 2) return bad_argument("decompress.ring_class: 0 compact (4 lanes per block: phased), 1 large, 2 round-2 compact rings (4 lanes per block)");
-        ctx->ringClass = (int)value;
-    }
-    else if (k == "lz4.compress.variant") {
-        if (value != 0 && value != 1 && value != 4) return bad_argument("lz4.compress.variant: 0 serial probes, 1 batch probes, 4 many matches per window");
-        ctx->lz4cVariant = (int)value;
-    }
-    else if (k == "snappy.compress.variant") {
-        if (value < 0 || value > 4 || value == 3) return bad_argument("snappy.compress.variant: 0 serial probes, 1 batch probes, 2 two tiers, 4 two tiers, many matches per window");
-        ctx->snappycVariant = (int)value;
-    }
-    else if (k == "snappyframed.decompress.variant") {
-        if (value < 0 || value > 3) return bad_argument("snappyframed.decompress.variant: 0 a wavefront per stream, 1 chunk list through the ring decoders, 2 through the two-pass decoder, 3 chosen by a probe");
-        ctx->snappyFramedVariant = (int)value;
-    }
-    else if (k == "snappyframed.compress.variant") {
-        if (value != 0 && value != 1) return bad_argument("snappyframed.compress.variant: 0 a wavefront per stream, 1 block list");
-        ctx->snappyFramedCompressVariant = (int)value;
-    }
-    else if (k == "hadoop.buffer_size") {
-        if (value < 64 || value > 0x40000000) return bad_argument("hadoop.buffer_size out of range");
-        ctx->hadoopBufferSize = (int)value;
-    }
-    else if (k == "hadoop.decompress.variant") {
-        if (value < 0 || value > 3) return bad_argument("hadoop.decompress.variant: 0 a wavefront per stream, 1 chunk list through the ring decoders, 2 through the two-pass decoders, 3 chosen by a probe");
-        ctx->hadoopDecompressVariant = (int)value;
-    }
-    else if (k == "lz4frame.decompress.variant") {
-        if (value < 0 || value > 2) return bad_argument("lz4frame.decompress.variant: 0 a wavefront per item, 1 block list through the two-pass decoder, 2 chosen by a probe");
-        ctx->lz4FrameDecompressVariant = (int)value;
-    }
-    else if (k == "lz4.decompress.parse") {
-        if (value < 0 || value > 2) return bad_argument("lz4.decompress.parse: 0 by the batch (a wavefront per block below 32768 blocks), 1 a lane per block, 2 a wavefront per block");
-        achip::g_lz4_parse_mode = (int)value;
-    }
-    else if (k == "mixed.concurrent") {
-        if (value != 0 && value != 1) return bad_argument("mixed.concurrent: 1 a mixed batch's codec families side by side (a stream and scratch each), 0 every bucket in turn");
-        ctx->mixConcurrent = (int)value;
-    }
-    else if (k == "snappy.decompress.parse") {
-        if (value < 0 || value > 2) return bad_argument("snappy.decompress.parse: 0 by the batch (a wavefront per block up to 4096 blocks), 1 a lane per block, 2 a wavefront per block");
-        achip::g_snappy_parse_mode = (int)value;
-    }
-    else if (k == "zstd.decompress.exec") {
-        if (value < 0 || value > 2) return bad_argument("zstd.decompress.exec: 0 rings, 1 record executor, 2 chosen per item");
-        achip::g_zstd_pipe_exec = (int)value;
-    }  // (process-wide: a development switch between the two execute stages)
-    else if (k == "zstd.decompress.seq_waves") {
-        if (value != 1 && value != 2 && value != 4) return bad_argument("zstd.decompress.seq_waves: wavefronts per workgroup of the pipeline's sequence stage: 1, 2 or 4 (64 items a workgroup either way)");
-        achip::g_zstd_seq_waves = (int)value;
-    }  // (process-wide, like zstd.decompress.exec)
-    else if (k == "zstd.decompress.lit_items") {
-        if (value != 8 && value != 10 && value != 13 && value != 16 && value != 20) return bad_argument("zstd.decompress.lit_items: items per wavefront of the pipeline's literal stage: 8, 10 or 16 (4 KiB of LDS an item), 13 (3 KiB: symbols and length nibbles apart), 20 (16 items of 2 304 bytes: symbols, and lengths by symbol)");
-        achip::g_zstd_lit_items = (int)value;
-    }  // (process-wide)
-    else if (k == "decompress.latency_max_blocks") {
-        if (value < 0 || value > 65536) return bad_argument("decompress.latency_max_blocks: 0 (never) .. 65536: LZ4 / Snappy batches of at most this many blocks take a wavefront and 128 KiB of LDS history per block");
-        ctx->latencyMaxBlocks = (int)value;
-    }
-    else if (k == "decompress.ring_pad") {
-        if (value < 0 || value > 256 || (value & 15) != 0) return bad_argument("ring pad must be a multiple of 16 in 0..256");
-        ctx->ringPad = (int)value;
-    }
-    else if (k == "zstd.decompress.tile") {
-        if (value < 64 || value > 65536) return bad_argument("tile must be in 64..65536");
-        ctx->zstdTile = (int)value;
-    }
-    else if (k == "debug.scratch_poison") ctx->scratchPoison = (int)value;
-    else if (k == "zstd.decompress.variant") {
-        if (value != 0 && value != 1) return bad_argument("zstd.decompress.variant: 1 pipeline, 0 one-kernel decoder");
-        ctx->zstddVariant = (int)value;
-    }
-    else if (k == "zstd.stream.chunked") ctx->zstdStreamChunked = value != 0 ? 1 : 0;
-    else if (k == "zstd.decompress.stream_blocks") {
-        if (value != 0 && (value < 16 || value > 131072)) return bad_argument("zstd.decompress.stream_blocks must be 0 or 16..131072");
-        ctx->zstdStreamBlocks = (int)value;
-    }
-    else if (k == "zstd.compress.variant") {
-        const bool ok = value >= 0 && value <= 3;
-        if (!ok) return bad_argument("zstd.compress.variant: 3 match-finder kernel (many matches per window) + entropy kernel, 0 the same with batch probes, 1 with serial probes, 2 one kernel");
-        ctx->zstdcVariant = (int)value;
-    }
-    else if (k == "host.look_max_blocks") {
-        if (value < 0 || value > 65536) return bad_argument("host.look_max_blocks: 0 .. 65536");
-        ctx->hostLookMaxBlocks = (int)value;
-    }
-    else if (k == "host.copy_priority") {
-        if (value != 0 && value != 1) return bad_argument("host.copy_priority: 1 the host-pointer pipeline's copy streams at the lowest priority (default), 0 at the default priority");
-        ctx->hostCopyLowPriority = (int)value;
-    }
-    else if (k == "decompress.auto_remember") {
-        if (value != 0 && value != 1) return bad_argument("decompress.auto_remember: 1 auto mode launches only the decoder the last arrived probe statistics chose for batches of that shape (default), 0 both decoders in every call");
-        ctx->autoRemember = (int)value;
-        ctx->autoChoice[0] = ctx->autoChoice[1] = -1;
-    }
-    else if (k == "host.ramp") {
-        if (value != 0 && value != 1) return bad_argument("host.ramp: 1 smaller chunks at the start and the end of a host-pointer batch (default), 0 equal chunks");
-        ctx->hostRamp = (int)value;
-    }
-    else if (k == "host.slots") {
-        if (value < 2 || value > achip_ctx::kHostSlots) return bad_argument("host.slots: 2 .. 8 staging slots of the host-pointer pipeline");
-        ctx->hostSlots = (int)value;
-    }
-    else if (k == "host.blit") {
-        if (value < 0 || value > 3) return bad_argument("host.blit: bit 0 = the host-pointer pipeline's uploads by a copy kernel, bit 1 = its downloads (0 = both by hipMemcpyAsync)");
-        ctx->hostBlit = (int)value;
-    }
-    else if (k == "host.blit_groups") {
-        if (value < 1 || value > 4096) return bad_argument("host.blit_groups: 1 .. 4096 workgroups of the copy kernel");
-        ctx->hostBlitGroups = (int)value;
-    }
-    else if (k == "max_src_len_hint") ctx->maxSrcLenHint = (int)value;
-    else if (k == "lz4.compress.mem_waves") {
-        if (value < 0 || value > 2) return bad_argument("lz4.compress.mem_waves: wavefronts per workgroup of the window encoder whose table lies in memory: 0 (one wavefront per block, table in LDS), 1 or 2");
-        achip::g_lz4_mem_waves = (int)value;
-    }  // (process-wide)
-    else if (k == "lz4.compress.tier_min_blocks") {
-        if (value < 1 || value > (1 << 30)) return bad_argument("lz4.compress.tier_min_blocks: batches of at least this many blocks take the two-tier kernel (default 5120)");
-        achip::g_lz4_tier_min_blocks = (int)value;
-    }  // (process-wide)
-    else if (k == "snappy.compress.mem_waves") {
-        if (value < 0 || value > 3) return bad_argument("snappy.compress.mem_waves: wavefronts per workgroup of the two-tier encoder whose table lies in memory, 0 .. 3");
-        achip::g_snappy_mem_waves = (int)value;
-    }  // (process-wide)
-    else if (k == "snappy.compress.fan") {
-        if (value != 0 && value != 1) return bad_argument("snappy.compress.fan: 1 the independent 64 KiB sub-blocks of a buffer side by side (default), 0 in turn on one wavefront");
-        ctx->snappyFan = (int)value;
-    }
-    else if (k == "decompress.exec_variant") {
-        // 2: the one executor there is.  (Round 2's experiments and timing aids -- 121 .. 125, 201, 302 .. 308 -- were measured, then removed: rounds 3 and 4.)
-        const bool ok = value == 2;
-        if (!ok) return bad_argument("decompress.exec_variant: 2");
-        ctx->execVariant = (int)value;
-    }
-    else if (k == "host.chunk_bytes") {
-        if (value < (1 << 16) || value > (1LL << 32)) return bad_argument("host.chunk_bytes must be in 64 KiB .. 4 GiB");
-        ctx->hostChunkBytes = value;
-    }
-    else if (k == "host.copy_threads") {
-        if (value < 0 || value > 64) return bad_argument("host.copy_threads must be in 0..64");
-        if (ctx->pool) return bad_argument("host.copy_threads must be set before the first host-pointer batch");
-        ctx->hostCopyThreads = (int)value;
-    }
-    else return bad_argument("unknown option");
+    const std::string k(name);
+    if (k == "host.copy_threads" && ctx->pool) return bad_argument("host.copy_threads must be set before the first host-pointer batch");
+    static_cast<achip::Settings&>(*ctx) = next;
+    if (k == "decompress.auto_remember") ctx->autoChoice[0] = ctx->autoChoice[1] = -1;
     return 0;
 }
 
@@ -1213,10 +937,7 @@ int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name)
         if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
         int32_t v[6] = {0, 0, 0, 0, 0, 0};
         if (hipMemcpy(v, ctx->scratch, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        const bool mixed = (int64_t)v[0] * 4 > (ctx->lastAutoBlocks + 15) / 16;  // the rule of lz4_pick (achip_device.h)
-        const bool pooledShort = v[1] > 0 && (int64_t)v[2] < (ctx->lastAutoIsLz4 ? 12 : 6) * (int64_t)v[1];
-        const bool isShort = v[5] > 0 ? (int64_t)v[4] * 3 > (int64_t)v[5] : pooledShort;
-        return (mixed || isShort) ? 3 : 0;
+        return auto_pick(v, ctx->lastAutoBlocks, ctx->lastAutoFam);
     }
     if (k == "decompress.scratch_bytes") {  // the context's decode scratch as granted (the two-pass decoders' record arena is what lies behind its fixed part): a smaller grant than a batch asked for shows here and in decompress.twopass_fallback_blocks
         return ctx->scratchBytes;
@@ -1403,7 +1124,7 @@ int32_t mix_lane(achip_ctx* ctx, int op, achip_ctx** out)
     if (!ctx->mixLaneDone[op]) {  // (on its own: a context whose event could not be made at the first attempt tries again, it does not record on a null event)
         HIP_TRY(hipEventCreateWithFlags(&ctx->mixLaneDone[op], hipEventDisableTiming));
     }
-    static_cast<achip_options&>(*ctx->mixLane[op]) = static_cast<const achip_options&>(*ctx);
+    static_cast<achip::Settings&>(*ctx->mixLane[op]) = *ctx;  // (the settings only: a lane's state -- auto mode's memory among it -- is its own)
     *out = ctx->mixLane[op];
     return 0;
 }
@@ -2351,7 +2072,7 @@ int32_t dstream_step(achip_zstd_dstream* z, const std::vector<StepBlock>& list, 
     // positions count from the oldest history byte kept: the step writes from histLen on
     uint8_t* dOut = z->hist + (z->window - z->histLen);
     HIP_TRY(achip::launch_zstd_stream_step(ctx->stream, z->scratch, z->scratchBytes, z->carry, z->dSrc, (int32_t)at, blocks, dOut, (int32_t)z->histLen,
-                                           (int32_t)(z->histLen + achip_zstd_dstream::kStepBytes), closing ? 1 : 0, z->hasChecksum ? 1 : 0, expected, result));
+                                           (int32_t)(z->histLen + achip_zstd_dstream::kStepBytes), closing ? 1 : 0, z->hasChecksum ? 1 : 0, expected, result, ctx->kernel));
     const int32_t good = result[0], produced = result[1];
     if (produced > 0) {
         HIP_TRY(hipMemcpyAsync(z->hostOut, z->hist + z->window, (size_t)produced, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,0 +1,89 @@
+// achip_launch.h -- the host launchers one translation unit calls in another: achip_abi.cpp calls them all, the container readers call the
+// block decoders, the Zstd decoder's two halves call each other, and tools/hostemu calls them on the CPU.  Every file that defines or calls
+// one includes this header.
+#pragma once
+#include "achip_device.h"
+#include "achip_settings.h"
+
+namespace achip {
+
+namespace sx {
+struct BlockMeta;
+}
+namespace zd {
+struct FseTable;
+}
+
+// ---- LZ4 / Snappy block decoders ----
+// ring decoders (lz4_decompress_v2.hip, snappy_decompress_v2.hip) and their lanes per block by the batch size
+hipError_t launch_lz4_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
+hipError_t launch_snappy_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
+int lz4_ring_group_for(int32_t nBlocks);
+int snappy_ring_group_for(int32_t nBlocks);
+// two-pass decoders (lz4_decompress_v7.hip, snappy_decompress_v5.hip): parse to records, a wavefront per block executes them
+hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks);
+hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks);
+hipError_t launch_seq_execute2(const BatchArgs& a, hipStream_t stream, const sx::BlockMeta* meta, const uint64_t* arena, const int32_t* stats, int32_t shortLimit);
+int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
+// record arena per block of the two-pass decoders (8 bytes per record; lz4_decompress_v7.hip: text-like 64 KiB blocks make 6 000 .. 8 500 LZ4
+// records, 8 500 .. 11 500 Snappy records), and the least it is worth running them with (blocks that do not fit go to the ring decoder)
+constexpr int64_t LZ4_RECORD_BYTES_PER_BLOCK = 98304, LZ4_RECORD_BYTES_PER_BLOCK_MIN = 32768;
+constexpr int64_t SNAPPY_RECORD_BYTES_PER_BLOCK = 131072, SNAPPY_RECORD_BYTES_PER_BLOCK_MIN = 49152;
+// auto mode's probes (decode_probes.hip)
+hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32_t* mixedGroups, int32_t minBlocks);
+hipError_t launch_lz4_sequence_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
+hipError_t launch_snappy_element_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
+
+// ---- LZ4 / Snappy block encoders ----
+// the two-tier LZ4 kernel runs only with at least lz4_compress_scratch_bytes() of scratch (scratchBytes); with less, the one-wavefront kernel writes the same bytes
+hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int variant, int maxSrcLenHint, void* scratch, int64_t scratchBytes, const KernelSettings& ks);
+int64_t lz4_compress_scratch_bytes();
+hipError_t launch_snappy_compress(const BatchArgs& a, hipStream_t stream, int variant, void* scratch, bool fan, const KernelSettings& ks);
+int64_t snappy_compress_scratch_bytes(int32_t nBlocks);
+
+// ---- Zstd ----
+hipError_t launch_zstd_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int variant, int32_t tileMax, const ZstdMbProvider* mbp, const KernelSettings& ks);
+int64_t zstd_decompress_scratch_bytes(int32_t nBlocks, int32_t tileMax);
+// the pipeline (zstd_decompress_pipe.hip) and the one-kernel decoder it hands items to (zstd_decompress.hip)
+hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, void* scratch, void* generalScratch, int32_t tileMax, const ZstdMbProvider* mbp, const KernelSettings& ks);
+int64_t zstd_decompress_pipe_scratch_bytes(int32_t nBlocks, int32_t tileMax);
+void* zstd_decompress_pipe_general_scratch(void* scratch, int32_t nBlocks, int32_t tileMax);
+hipError_t launch_zstd_decompress_prepare(hipStream_t stream, void* generalScratch, const zd::FseTable** dflt);
+hipError_t launch_zstd_decompress_list(const BatchArgs& a, hipStream_t stream, void* generalScratch, const int32_t* list, const int32_t* listCount);
+int64_t zstd_decompress_general_scratch_bytes();
+hipError_t launch_zstd_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int variant);
+hipError_t launch_zstd_stream_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int chunked);
+int64_t zstd_compress_scratch_bytes(int32_t nBlocks);
+// ZstdOutputStream, a step at a time (zstd_stream.hip)
+int64_t zstd_ostream_state_bytes();
+int64_t zstd_ostream_slab_bytes();
+hipError_t launch_zstd_ostream_step(hipStream_t stream, void* state, void* slab, const uint8_t* buf, int32_t offset, int32_t chunk, int32_t closing, uint8_t* out, int32_t outCap);
+// ZstdInputStream's frames without a content size, a step at a time (zstd_decompress_pipe.hip)
+int64_t zstd_stream_carry_bytes();
+void zstd_stream_carry_init(void* hostCarry);
+int64_t zstd_stream_step_scratch_bytes(int32_t blocks);
+hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t scratchBytes, void* carryDev, const uint8_t* dSrc, int32_t srcLen, int32_t blocks, uint8_t* dOut,
+                                   int32_t startPos, int32_t outLimit, int32_t closing, int32_t hasChecksum, uint32_t expected, int32_t* result, const KernelSettings& ks);
+
+// ---- containers: LZ4 frames, x-snappy-framed, Hadoop block streams (the readers pass `ks` on to the two-pass decoders) ----
+hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
+int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant);
+hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes);
+int64_t lz4frame_compress_scratch_bytes(int32_t items, bool least);
+hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
+int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams);
+hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant);
+int64_t snappyframed_compress_scratch_bytes(int32_t nStreams);
+hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux, const KernelSettings& ks);
+int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize);
+hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize);
+int64_t hadoop_compress_scratch_bytes(int32_t nStreams);
+
+// ---- mixed batches, host-pointer staging, hashes (batch_mix.hip, xxhash.hip) ----
+hipError_t launch_mix_gather(const int32_t* perm, int32_t n, const BatchArgs& a, int64_t* gSrcOff, int32_t* gSrcLen, int64_t* gDstOff, int32_t* gDstCap, hipStream_t stream);
+hipError_t launch_mix_scatter(const int32_t* perm, int32_t n, const int32_t* gOutLen, const int32_t* gStatus, const int64_t* gErr, const BatchArgs& a, hipStream_t stream);
+hipError_t launch_blit(void* dst, const void* src, int64_t bytes, int workgroups, hipStream_t stream);
+hipError_t launch_xxh64_batch(const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t n, uint64_t seed, int64_t* out, hipStream_t stream);
+hipError_t launch_xxh32_batch(const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t n, uint32_t seed, int32_t* out, hipStream_t stream);
+
+}  // namespace achip

@@ -3,6 +3,7 @@
 // arrays from the caller's arrays in that order, every op's kernels then run over their contiguous slice, and `scatter` puts the
 // results back where the caller's item order wants them.  Blocks stay where they are: only 44 bytes of metadata per item move.
 #include "achip_device.h"
+#include "achip_launch.h"
 
 namespace achip {
 

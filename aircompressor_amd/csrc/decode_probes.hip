@@ -9,6 +9,7 @@
 // (Until round 4 these lived in lz4_decompress_v5.hip / snappy_decompress_v4.hip beside the lane-per-block decoders, which the two-pass
 // decoders superseded: 300 .. 330 GiB/s against 515 on the corpus batch; removed.)
 #include "achip_device.h"
+#include "achip_launch.h"
 
 namespace achip {
 

@@ -36,6 +36,7 @@
 #include "snappy_decode_body.h"
 #include "lz4_compress_mw.h"
 #include "snappy_compress_mw.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -656,17 +657,6 @@ __global__ __launch_bounds__(64) void hadoop_compact_kernel(BatchArgs a, BlockLi
 
 }  // namespace hdp
 
-hipError_t launch_lz4_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-int lz4_ring_group_for(int32_t nBlocks);
-int snappy_ring_group_for(int32_t nBlocks);
-hipError_t launch_lz4_sequence_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-hipError_t launch_snappy_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-hipError_t launch_snappy_element_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32_t* mixedGroups, int32_t minBlocks);
-hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats);
-hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats);
-int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
-
 namespace {
 constexpr int HDP_SERIAL_WAVES = 1024;
 int64_t hdp_internal_bytes(int32_t bufferSize)
@@ -687,7 +677,7 @@ int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize)
 // without a GPU at hand: not the default until measured): the chunks through the TWO-PASS decoders -- their record arena is
 // sized by the chunk count, which only the device knows, so the host reads it back (one synchronisation) and asks `aux` for the arena;
 // chunks whose records do not fit, and every chunk when there is no arena, take the ring decoder as in variant 1.
-hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux)
+hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -783,7 +773,7 @@ hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void
                 BatchArgs t = c;
                 t.nBlocks = nChunks;
                 t.nBlocksDev = nullptr;
-                e = snappy ? launch_snappy_decompress_twopass(t, stream, arena, bytes, 4, 0, 2, nullptr) : launch_lz4_decompress_twopass(t, stream, arena, bytes, 16, 0, 2, nullptr);
+                e = snappy ? launch_snappy_decompress_twopass(t, stream, arena, bytes, 4, 0, nullptr, ks) : launch_lz4_decompress_twopass(t, stream, arena, bytes, 16, 0, nullptr, ks);
                 if (e != hipSuccess) return e;
                 viaTwoPass = true;
             }

@@ -16,6 +16,7 @@
 // inside the batch so the table evolves exactly as in program order.
 #include "lz4_compress_body.h"
 #include "lz4_compress_mw.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -419,14 +420,10 @@ hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void
     return hipGetLastError();
 }
 
-// the two-tier kernel: from batches that fill the LDS tier on (fewer blocks: a wavefront per block, all tables in LDS)
-int g_lz4_mem_waves = 1;            // `lz4.compress.mem_waves`: 0 = one wavefront per block, table in LDS (until round 6); 1 / 2 = memory-tier wavefronts beside five LDS ones.
-                                    // Measured, 65 536 blocks (profiles/r06_ab_lz4_compress_tiers.txt): corpus 38.8 / **44.1** / 41.3 GiB/s at 0 / 1 / 2, fragments 103.6 / 104.8 / 93.0
-int g_lz4_tier_workgroups = 0;      // (0: lz4t::WORKGROUPS; tools/hostemu makes it small)
-int g_lz4_tier_min_blocks = 256 * 20;  // `lz4.compress.tier_min_blocks` (what the LDS tier holds at once)
+// the two-tier kernel: from batches that fill the LDS tier on (fewer blocks: a wavefront per block, all tables in LDS); ks.lz4MemWaves, ks.lz4TierMinBlocks
 int64_t lz4_compress_scratch_bytes() { return 4096 + (int64_t)lz4t::WORKGROUPS * lz4t::MEM_WAVES_MAX * lz4c::MAX_TABLE_SIZE * 2; }
 
-hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int variant, int maxSrcLenHint, void* scratch)
+hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int variant, int maxSrcLenHint, void* scratch, int64_t scratchBytes, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -434,12 +431,12 @@ hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int varia
     // maxSrcLenHint: 0 = unknown, else the caller's promise about the largest srcLen in the batch: when it is <= 64 KiB the launch of
     // the wide-table kernel is skipped (a block that breaks the promise gets an INVALID_ARGUMENT status, not silence)
     const int32_t both = maxSrcLenHint == 0 || maxSrcLenHint > 65536;
-    if (variant == 4 && g_lz4_mem_waves > 0 && scratch != nullptr && a.nBlocks >= g_lz4_tier_min_blocks) {
+    if (variant == 4 && ks.lz4MemWaves > 0 && a.nBlocks >= ks.lz4TierMinBlocks && scratch != nullptr && scratchBytes >= lz4_compress_scratch_bytes()) {
         int32_t* counter = (int32_t*)scratch;
         const hipError_t e = hipMemsetAsync(counter, 0, 64, stream);
         if (e != hipSuccess) return e;
-        const unsigned perGroup = (unsigned)(lz4t::LDS_WAVES + g_lz4_mem_waves);
-        unsigned groups = g_lz4_tier_workgroups > 0 ? (unsigned)g_lz4_tier_workgroups : (unsigned)lz4t::WORKGROUPS;
+        const unsigned perGroup = (unsigned)(lz4t::LDS_WAVES + ks.lz4MemWaves);
+        unsigned groups = ks.lz4TierWorkgroups > 0 ? (unsigned)ks.lz4TierWorkgroups : (unsigned)lz4t::WORKGROUPS;
         groups = groups > (unsigned)lz4t::WORKGROUPS ? (unsigned)lz4t::WORKGROUPS : groups;
         const unsigned need = ((unsigned)a.nBlocks + perGroup - 1) / perGroup;
         hipLaunchKernelGGL(lz4_compress_tiers_kernel, dim3(need < groups ? need : groups), dim3(64 * perGroup), 0, stream, a, both, (uint16_t*)((uint8_t*)scratch + 4096), counter);

@@ -6,6 +6,7 @@
 // history ring and flushed to HBM in whole aligned chunks, and back-references within LDS_REACH are
 // served from LDS (achip_rings.h).  HBM traffic per block ~= compressed bytes + plaintext bytes.
 #include "lz4_decode_body.h"
+#include "achip_launch.h"
 
 namespace achip {
 

@@ -15,6 +15,7 @@
 #include "achip_seqexec.h"
 #include "achip_seqexec2.h"
 #include "achip_waveparse.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -599,7 +600,6 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
 // stream), the wavefront parser's does from 8 192 blocks on (the wavefronts a launch has resident).  Corpus blocks of 64 KiB, GiB/s lane / wavefront (profiles/r05_parsesweep.txt):
 // 4 096 blocks 48 / 132; 8 192: 90 / 153; 16 384: 163 / 186; 32 768: 255 / 205; 131 072: 443 / 220.  (Round 4 had the line at 4 096: the wavefront parser was half as fast then.)
 constexpr int32_t LZ4_WAVE_PARSE_MAX_BLOCKS = 16384;
-int g_lz4_parse_mode = 0;
 
 // the execute pass (achip_seqexec2.h): pieces of at most 16 + 16 bytes, every global load one batch ahead
 template <int WIN = sx2::WIN_DEFAULT, int WAVES = 0>
@@ -628,22 +628,19 @@ int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock)
 }
 int64_t lz4_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_bytes(nBlocks, 98304); }
 
-// the execute pass (shared with snappy_decompress_v5.hip).  (execVariant: 2, the only one -- round 2's timing aids, executor and parser variants
-// that left work out, were development tools and went in round 4 together with their build switch)
-hipError_t launch_seq_execute2(const BatchArgs& a, hipStream_t stream, const sx::BlockMeta* meta, const uint64_t* arena, int execVariant, const int32_t* stats, int32_t shortLimit)
+// the execute pass (shared with snappy_decompress_v5.hip).  (Round 2's timing aids, executor and parser variants that left work out, were
+// development tools and went in round 4 together with their build switch)
+hipError_t launch_seq_execute2(const BatchArgs& a, hipStream_t stream, const sx::BlockMeta* meta, const uint64_t* arena, const int32_t* stats, int32_t shortLimit)
 {
-    (void)execVariant;
     hipLaunchKernelGGL(seq_execute2_kernel<>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, meta, arena, stats, shortLimit);
     return hipGetLastError();
 }
-
-hipError_t launch_lz4_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
 
 // The two passes of a batch on the caller's stream.  (Round 2 left an experiment here -- the batch cut into 2 .. 8 parts alternating between two
 // helper streams, so that one part's parse could share the chip with another part's execute; measured in round 3 on the corpus batch
 // (profiles/r03_notes.md): 2 parts 520 GiB/s against 517, 4 parts 456, 8 parts 363: the two kernels compete for the same issue slots.
 // Removed, with the 8 KiB-window executor (489) and the register-capped one.)
-hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats)
+hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -660,14 +657,14 @@ hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream,
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((a.nBlocks + 63) / 64)), wg(64);
     {
-    const bool wavePerBlock = a.nBlocksDev == nullptr && (g_lz4_parse_mode == 2 || (g_lz4_parse_mode == 0 && a.nBlocks <= LZ4_WAVE_PARSE_MAX_BLOCKS));
+    const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.lz4Parse == 2 || (ks.lz4Parse == 0 && a.nBlocks <= LZ4_WAVE_PARSE_MAX_BLOCKS));
     if (wavePerBlock) {
         hipLaunchKernelGGL(lz4_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
     }
     else {
         hipLaunchKernelGGL(lz4_parse2_kernel, grid, wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
     }
-    e = launch_seq_execute2(a, stream, meta, arena, execVariant, stats, 12);
+    e = launch_seq_execute2(a, stream, meta, arena, stats, 12);
     if (e != hipSuccess) return e;
     }
     BatchArgs f = a;

@@ -9,6 +9,7 @@
 // many frames per batch; a 4 MiB block is one wavefront's work.
 #include "lz4_decode_body.h"
 #include "achip_xxhash.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -425,12 +426,6 @@ __global__ __launch_bounds__(64) void lz4frame_decompress_kernel(BatchArgs a, in
     }
 }
 
-hipError_t launch_lz4_sequence_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats);
-hipError_t launch_lz4_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-int lz4_ring_group_for(int32_t nBlocks);
-int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
-
 int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant)
 {
     if (variant != 1 && variant != 2) {
@@ -441,7 +436,7 @@ int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant)
 }
 
 // variant 0 (default): a wavefront per item; variant 1: the block list (above)
-hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux)
+hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -518,7 +513,7 @@ hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, vo
         const int64_t bytes = twopass_scratch_bytes(nListed, perBlock < 98304 ? 98304 : perBlock);
         void* arena = aux->get(aux->user, bytes);
         if (arena != nullptr) {
-            e = launch_lz4_decompress_twopass(c, stream, arena, bytes, 16, 0, 2, nullptr);
+            e = launch_lz4_decompress_twopass(c, stream, arena, bytes, 16, 0, nullptr, ks);
             if (e != hipSuccess) return e;
             decoded = 1;
         }

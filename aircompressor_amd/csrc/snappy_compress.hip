@@ -10,6 +10,7 @@
 // mismatch) and the literal copies (64 x 16 bytes per step).
 #include "snappy_compress_body.h"
 #include "snappy_compress_mw.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -336,20 +337,15 @@ __global__ __launch_bounds__(256) void snappy_compress_tiers_kernel(BatchArgs a,
 
 namespace {
 constexpr int SNC_TIER_WORKGROUPS = 256 * 5;  // five 32 KB LDS tables per CU
-}
-int g_snappy_tier_workgroups = SNC_TIER_WORKGROUPS;  // (the persistent grid where the unit count is known on the device only; tools/hostemu makes it small)
-// wavefronts of a workgroup whose table lies in memory (0 .. 3; `snappy.compress.mem_waves`).  Their tables are what the kernel's HBM traffic is made of -- 431 GB
-// a launch on the corpus batch, 100 x the input: 1 280 workgroups x 3 slabs x 32 KiB = 120 MB of tables, 15 MB per XCD against 4 MB of L2.
-int g_snappy_mem_waves = 3;
-namespace {
 constexpr int64_t SNC_SLABS_BYTES = (int64_t)SNC_TIER_WORKGROUPS * 3 * snc::MAX_HASH_TABLE_SIZE * 2;
 }
+static_assert(KernelSettings{}.snappyTierWorkgroups == SNC_TIER_WORKGROUPS, "the fan-out's persistent grid defaults to the tier's workgroups");
 // [4 KiB: the draw counter, the fan-out's state][the memory tier's table slabs][listed buffers: nBlocks x int32][their first units: nBlocks x int32]
 int64_t snappy_compress_scratch_bytes(int32_t nBlocks) { return 4096 + SNC_SLABS_BYTES + 2 * (((int64_t)(nBlocks > 0 ? nBlocks : 1) * 4 + 255) & ~(int64_t)255); }
 
 // variant 0: serial probing, 1: batch probing with the table in LDS (a wavefront per buffer), 2: batch probing, two tiers, 4 (default): many matches per
 // window, two tiers, the sub-blocks of buffers beyond 64 KiB side by side (fan = false: in turn, as until round 5)
-hipError_t launch_snappy_compress(const BatchArgs& a, hipStream_t stream, int variant, void* scratch, bool fan)
+hipError_t launch_snappy_compress(const BatchArgs& a, hipStream_t stream, int variant, void* scratch, bool fan, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -359,7 +355,7 @@ hipError_t launch_snappy_compress(const BatchArgs& a, hipStream_t stream, int va
         const hipError_t e = hipMemsetAsync(counter, 0, 64, stream);
         if (e != hipSuccess) return e;
         uint16_t* slabs = (uint16_t*)((uint8_t*)scratch + 4096);
-        const unsigned perGroup = (unsigned)(1 + g_snappy_mem_waves);
+        const unsigned perGroup = (unsigned)(1 + ks.snappyMemWaves);
         const unsigned need = (unsigned)((a.nBlocks + perGroup - 1) / perGroup);
         if (variant == 4 && fan) {
             snfan::State* state = (snfan::State*)scratch;
@@ -368,7 +364,7 @@ hipError_t launch_snappy_compress(const BatchArgs& a, hipStream_t stream, int va
             const unsigned listGrid = (unsigned)((a.nBlocks + 255) / 256);
             hipLaunchKernelGGL(snappy_fan_list_kernel, dim3(listGrid < 1024u ? listGrid : 1024u), dim3(256), 0, stream, a, state, bigItem, bigFirst);
             // (the extra units are known on the device only: the persistent grid is launched whole)
-            hipLaunchKernelGGL(snappy_compress_tiers_kernel<true>, dim3((unsigned)g_snappy_tier_workgroups), dim3(64 * (1 + g_snappy_mem_waves)), 0, stream, a, slabs, counter, state, bigItem, bigFirst);
+            hipLaunchKernelGGL(snappy_compress_tiers_kernel<true>, dim3((unsigned)ks.snappyTierWorkgroups), dim3(64 * perGroup), 0, stream, a, slabs, counter, state, bigItem, bigFirst);
             hipLaunchKernelGGL(snappy_fan_fold_kernel, dim3((unsigned)(a.nBlocks < 4096 ? a.nBlocks : 4096)), dim3(64), 0, stream, a, state, bigItem);
             return hipGetLastError();
         }

@@ -4,6 +4,7 @@
 // bytes move through the per-block LDS rings of achip_rings.h (input pulled from HBM once, output
 // flushed in whole aligned chunks, near back-references served from LDS).
 #include "snappy_decode_body.h"
+#include "achip_launch.h"
 
 namespace achip {
 

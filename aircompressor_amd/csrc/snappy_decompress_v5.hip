@@ -10,6 +10,7 @@
 
 #include "achip_seqexec.h"
 #include "achip_waveparse.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -638,15 +639,10 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
 // 2 = a wavefront per block (context option snappy.decompress.parse).  Corpus blocks of 64 KiB, GiB/s lane / wavefront (profiles/r05_parsesweep.txt): 4 096 blocks 27 / 106;
 // 8 192: 53 / 129; 16 384: 98 / 156; 32 768: 157 / 173; 65 536: 236 / 182.
 constexpr int32_t SNAPPY_WAVE_PARSE_MAX_BLOCKS = 32768;
-int g_snappy_parse_mode = 0;
-
-hipError_t launch_seq_execute2(const BatchArgs& a, hipStream_t stream, const sx::BlockMeta* meta, const uint64_t* arena, int execVariant, const int32_t* stats, int32_t shortLimit);
-int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
-hipError_t launch_snappy_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
 
 int64_t snappy_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_bytes(nBlocks, 131072); }
 
-hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats)
+hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -663,14 +659,14 @@ hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stre
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((a.nBlocks + 63) / 64)), wg(64);
     {
-        const bool wavePerBlock = a.nBlocksDev == nullptr && (g_snappy_parse_mode == 2 || (g_snappy_parse_mode == 0 && a.nBlocks <= SNAPPY_WAVE_PARSE_MAX_BLOCKS));
+        const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.snappyParse == 2 || (ks.snappyParse == 0 && a.nBlocks <= SNAPPY_WAVE_PARSE_MAX_BLOCKS));
         if (wavePerBlock) {
             hipLaunchKernelGGL(snappy_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
         }
         else {
             hipLaunchKernelGGL(snappy_parse2_kernel, grid, wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
         }
-        e = launch_seq_execute2(a, stream, meta, arena, execVariant, stats, 6);
+        e = launch_seq_execute2(a, stream, meta, arena, stats, 6);
         if (e != hipSuccess) return e;
     }
     BatchArgs f = a;

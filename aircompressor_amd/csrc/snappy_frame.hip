@@ -15,6 +15,7 @@
 #include "snappy_decode_body.h"
 #include "snappy_compress_mw.h"
 #include "achip_crc32c.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -747,24 +748,16 @@ __global__ __launch_bounds__(64) void snappyframed_fold_kernel(BatchArgs a, Chun
 }
 }  // namespace snf
 
-hipError_t launch_snappy_decompress_rings(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-int snappy_ring_group_for(int32_t nBlocks);
-hipError_t launch_snappy_element_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32_t* mixedGroups, int32_t minBlocks);
-
 int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams)
 {
     const int64_t n = nStreams < 1 ? 1 : nStreams;
     return 4096 + n * (4 * 5 + 8) + (int64_t)snf::MAX_CHUNKS * (8 * 3 + 4 * 7) + 4096;
 }
 
-hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, int execVariant, const int32_t* stats);
-int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
-
 // variant 1 (default): the chunks through the ring decoders (with the probes' other choices behind them); variant 2 (round 2, written without
 // a GPU at hand: not the default until measured): through the two-pass decoder -- the host reads the chunk count back (one
 // synchronisation) and asks `aux` for the record arena; chunks whose records do not fit take the rings as in variant 1; 0: a wavefront per stream
-hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux)
+hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -854,7 +847,7 @@ hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream
                 BatchArgs t = c;
                 t.nBlocks = nChunks;
                 t.nBlocksDev = nullptr;
-                e = launch_snappy_decompress_twopass(t, stream, arena, bytes, 4, 0, 2, nullptr);
+                e = launch_snappy_decompress_twopass(t, stream, arena, bytes, 4, 0, nullptr, ks);
                 if (e != hipSuccess) return e;
                 viaTwoPass = true;
             }

@@ -8,6 +8,7 @@
 // buffers: the 4 lanes of a buffer read one stripe (32 or 16 contiguous bytes) per step, four steps in flight.
 // Roofline: HBM (read-once); algorithmic bytes = the buffer lengths.
 #include "achip_xxhash.h"
+#include "achip_launch.h"
 
 namespace achip {
 

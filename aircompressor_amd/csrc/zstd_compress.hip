@@ -20,6 +20,7 @@
 // Hash tables (up to 2^17 + 2^16 ints) and the sequence store live in a per-wave slab in HBM (L2-resident while the
 // frame is being encoded); all entropy tables live in LDS.
 #include "zstd_compress_body.h"
+#include "achip_launch.h"
 
 namespace achip {
 

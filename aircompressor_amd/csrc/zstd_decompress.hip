@@ -18,6 +18,7 @@
 // the regenerated literals of the current block live in a per-wave scratch slab in HBM (128 KiB + 64).
 // Checks are made in the order the Java code makes them, so status + detail equal the Java exception.
 #include "zstd_dec_common.h"
+#include "achip_launch.h"
 
 namespace achip {
 
@@ -699,10 +700,6 @@ constexpr int ZD_MAX_WAVES = 256 * 8;  // persistent waves: 8 per CU
 // scratch of the one-kernel decoder: [item counter | predefined tables | one literal slab per persistent wave]
 int64_t zstd_decompress_general_scratch_bytes() { return 4096 + (int64_t)sizeof(zd::FseTable) * 3 + (int64_t)ZD_MAX_WAVES * zd::LIT_SLAB; }
 
-int64_t zstd_decompress_pipe_scratch_bytes(int32_t nBlocks, int32_t tileMax);
-hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, void* scratch, void* generalScratch, int32_t tileMax, const ZstdMbProvider* mbp);
-void* zstd_decompress_pipe_general_scratch(void* scratch, int32_t nBlocks, int32_t tileMax);
-
 int64_t zstd_decompress_scratch_bytes(int32_t nBlocks, int32_t tileMax) { return zstd_decompress_pipe_scratch_bytes(nBlocks, tileMax); }
 
 // resets the item counter and builds the predefined FSE tables; returns them through *dflt
@@ -727,7 +724,7 @@ hipError_t launch_zstd_decompress_list(const BatchArgs& a, hipStream_t stream, v
 }
 
 // variant 1 (default): five-stage pipeline + one-kernel decoder for whatever it hands back; variant 0: one-kernel decoder only
-hipError_t launch_zstd_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int variant, int32_t tileMax, const ZstdMbProvider* mbp)
+hipError_t launch_zstd_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int variant, int32_t tileMax, const ZstdMbProvider* mbp, const KernelSettings& ks)
 {
     (void)scratchBytes;
     if (a.nBlocks <= 0) {
@@ -740,7 +737,7 @@ hipError_t launch_zstd_decompress(const BatchArgs& a, hipStream_t stream, void* 
         if (e != hipSuccess) return e;
         return launch_zstd_decompress_list(a, stream, general, nullptr, nullptr);
     }
-    return launch_zstd_decompress_pipe(a, stream, scratch, general, tileMax, mbp);
+    return launch_zstd_decompress_pipe(a, stream, scratch, general, tileMax, mbp, ks);
 }
 
 }  // namespace achip

@@ -31,6 +31,7 @@
 #include "achip_seqexec2.h"
 #include "zstd_codes.h"
 #include "achip_xxhash.h"
+#include "achip_launch.h"
 #include <cstring>
 #include <vector>
 
@@ -820,21 +821,20 @@ __global__ __launch_bounds__(64) void zstd_pipe_literals_kernel(BatchArgs a, zp:
 // Measured (profiles/r06_notes.md section 10; 32 768 corpus frames): 16 items 6.96 ms, 10 items **4.83**, 8 items 6.96 (the fifth wavefront does not get
 // its LDS: four of 32 lanes are the 128 streams of two full ones).  Then the table itself (SPLIT, above): symbol bytes and length nibbles apart are 3 KiB an item --
 // 13 items a wavefront, 208 streams a CU: **4.11**; symbols and lengths-by-symbol (2 304 bytes, 16 items, 256 streams, but a dependent second lookup): 4.60.
-// 13 is the default.
-int g_zstd_lit_items = 13;
+// 13 is the default (ks.zstdLitItems).
 template <bool MB>
-inline void launch_literals(const BatchArgs& a, const zp::Pipe& p, hipStream_t stream)
+inline void launch_literals(const BatchArgs& a, const zp::Pipe& p, hipStream_t stream, const KernelSettings& ks)
 {
-    if (g_zstd_lit_items == 13) {  // (3 KiB an item: 13 items = 39 KiB, four wavefronts a CU, 208 streams)
+    if (ks.zstdLitItems == 13) {  // (3 KiB an item: 13 items = 39 KiB, four wavefronts a CU, 208 streams)
         hipLaunchKernelGGL((zstd_pipe_literals_kernel<MB, 13, 1>), dim3((unsigned)((p.count + 12) / 13)), dim3(64), 0, stream, a, p);
     }
-    else if (g_zstd_lit_items == 20) {  // (2 304 bytes an item, 16 items = 36 KiB, four wavefronts a CU, 256 streams -- and a dependent second lookup per symbol)
+    else if (ks.zstdLitItems == 20) {  // (2 304 bytes an item, 16 items = 36 KiB, four wavefronts a CU, 256 streams -- and a dependent second lookup per symbol)
         hipLaunchKernelGGL((zstd_pipe_literals_kernel<MB, 16, 2>), dim3((unsigned)((p.count + 15) / 16)), dim3(64), 0, stream, a, p);
     }
-    else if (g_zstd_lit_items == 8) {
+    else if (ks.zstdLitItems == 8) {
         hipLaunchKernelGGL((zstd_pipe_literals_kernel<MB, 8>), dim3((unsigned)((p.count + 7) / 8)), dim3(64), 0, stream, a, p);
     }
-    else if (g_zstd_lit_items == 10) {
+    else if (ks.zstdLitItems == 10) {
         hipLaunchKernelGGL((zstd_pipe_literals_kernel<MB, 10>), dim3((unsigned)((p.count + 9) / 10)), dim3(64), 0, stream, a, p);
     }
     else {
@@ -936,25 +936,23 @@ __device__ uint64_t seq_idle_sink[SEQ_IDLE_GROUPS * 256];
 // are 64 workgroups on 64 of the 256 CUs, each as long as a full one takes.  So a tile of fewer than 256 x 64 items is spread: count / 256 items a workgroup
 // (the static LDS allocation stays: still one workgroup per CU), down to a single item; a step of a wavefront with fewer lanes on it is also the shorter one.
 constexpr int32_t ZSTD_EXEC_ALL_RECORDS_MAX_ITEMS = 16384;
-int g_zstd_seq_spread = 256;  // (the CUs a small tile is spread over; tools/hostemu sets 1 to get full workgroups from a handful of items)
-inline int32_t seql_items_for(int32_t count)
+inline int32_t seql_items_for(int32_t count, const KernelSettings& ks)  // (ks.zstdSeqSpread: the CUs a small tile is spread over)
 {
-    const int32_t per = (count + g_zstd_seq_spread - 1) / g_zstd_seq_spread;
+    const int32_t per = (count + ks.zstdSeqSpread - 1) / ks.zstdSeqSpread;
     return per < 1 ? 1 : (per > zp::SEQL_ITEMS ? zp::SEQL_ITEMS : per);
 }
-int g_zstd_seq_waves = 1;
-// Wavefronts per workgroup of the sequence stage (context option zstd.decompress.seq_waves: 1, 2 or 4).  The LDS holds 64 items' tables however they are
+// Wavefronts per workgroup of the sequence stage (ks.zstdSeqWaves: context option zstd.decompress.seq_waves, 1, 2 or 4).  The LDS holds 64 items' tables however they are
 // spread; a wavefront's step costs its ~140 vector instructions whether 16 or 64 of its lanes hold an item, but four wavefronts of 16 items issue theirs on
 // four SIMDs side by side where one wavefront of 64 leaves three SIMDs idle.
-inline int32_t seql_waves_for(int32_t count)
+inline int32_t seql_waves_for(int32_t count, const KernelSettings& ks)
 {
-    const int32_t items = seql_items_for(count);
-    return items < g_zstd_seq_waves ? 1 : g_zstd_seq_waves;
+    const int32_t items = seql_items_for(count, ks);
+    return items < ks.zstdSeqWaves ? 1 : ks.zstdSeqWaves;
 }
-inline int32_t seql_items_per_wave(int32_t count)
+inline int32_t seql_items_per_wave(int32_t count, const KernelSettings& ks)
 {
-    const int32_t w = seql_waves_for(count);
-    return (seql_items_for(count) + w - 1) / w;
+    const int32_t w = seql_waves_for(count, ks);
+    return (seql_items_for(count, ks) + w - 1) / w;
 }
 template <bool MB>
 __global__ __launch_bounds__(256) void zstd_pipe_sequences_lane_kernel(BatchArgs a, zp::Pipe p, int32_t itemsPerGroup, int32_t itemsPerWave)
@@ -1391,7 +1389,7 @@ __global__ __launch_bounds__(256) void zstd_pipe_execute_kernel(BatchArgs a, zp:
 // 128 KiB frames: fragments data -- 100 bytes per sequence -- 720 against 600 GiB/s; corpus -- 13 bytes per sequence -- 83 against 105), and the
 // item's capacity over its sequence count is what both kernels can see (an upper bound of the bytes per sequence: a caller that hands over far
 // more capacity than the frame needs gets the ring version).
-int g_zstd_pipe_exec = 2;  // context option zstd.decompress.exec: 2 = per item (default), 1 = this kernel, 0 = the ring version above
+// (ks.zstdExec, context option zstd.decompress.exec: 2 = per item (default), 1 = this kernel, 0 = the ring version above)
 
 template <int WIN = sx2::WIN_DEFAULT>
 __global__ __launch_bounds__(64) void zstd_pipe_execute2_kernel(BatchArgs a, zp::Pipe p, int32_t mode)
@@ -1868,11 +1866,6 @@ __global__ __launch_bounds__(64) void zstd_mb_checksum_kernel(BatchArgs a, zp::P
     }
 }
 
-// the one-kernel decoder, run over a list of items (zstd_decompress.hip)
-hipError_t launch_zstd_decompress_prepare(hipStream_t stream, void* generalScratch, const zd::FseTable** dflt);
-hipError_t launch_zstd_decompress_list(const BatchArgs& a, hipStream_t stream, void* generalScratch, const int32_t* list, const int32_t* listCount);
-int64_t zstd_decompress_general_scratch_bytes();
-
 namespace {
 constexpr int32_t PIPE_TILE_DEFAULT = 65536;              // items per pass through the five stages (K4 wants >= 64 Ki items in flight: 16 per wavefront)
 constexpr uint32_t PIPE_LIT_PER_ITEM = 80 * 1024 / 64;   // literal arena: average 64-byte units per item ...
@@ -1972,7 +1965,7 @@ namespace {
 // The multi-block stages over the items K1 listed (p: the pipeline's Pipe after its tiles).  The one host synchronisation of a decode
 // call is here: the number of listed items and of their blocks decides whether there is anything to do, how much scratch to ask the
 // caller for, and how many passes to run.
-hipError_t launch_zstd_mb_stages(const BatchArgs& a, hipStream_t stream, zp::Pipe p, const zd::FseTable* dflt, const ZstdMbProvider* mbp)
+hipError_t launch_zstd_mb_stages(const BatchArgs& a, hipStream_t stream, zp::Pipe p, const zd::FseTable* dflt, const ZstdMbProvider* mbp, const KernelSettings& ks)
 {
     const MbCaps top = mb_caps(mbp->passBlocks);
     p.mbSlots = top.slots;
@@ -2062,7 +2055,7 @@ hipError_t launch_zstd_mb_stages(const BatchArgs& a, hipStream_t stream, zp::Pip
         const unsigned nItems = (unsigned)(p.itemEnd - p.itemFirst);
         hipLaunchKernelGGL(zstd_mb_fill_kernel, dim3((nItems + 63) / 64), dim3(64), 0, stream, a, p);
         hipLaunchKernelGGL(zstd_mb_parse_kernel, dim3((unsigned)p.count), dim3(64), 0, stream, a, p, dflt);
-        launch_literals<true>(a, p, stream);
+        launch_literals<true>(a, p, stream, ks);
         p.order = nullptr;
         if (p.count > zp::SEQL_ITEMS) {  // (more than one wavefront of slots)
             p.orderHist = (int32_t*)(mbase + M.order);
@@ -2073,7 +2066,7 @@ hipError_t launch_zstd_mb_stages(const BatchArgs& a, hipStream_t stream, zp::Pip
             hipLaunchKernelGGL(zstd_mb_order_kernel<false>, dim3(g64), dim3(64), 0, stream, p);
             hipLaunchKernelGGL(zstd_mb_order_kernel<true>, dim3(g64), dim3(64), 0, stream, p);
         }
-        hipLaunchKernelGGL(zstd_pipe_sequences_lane_kernel<true>, dim3((unsigned)((p.count + seql_items_for(p.count) - 1) / seql_items_for(p.count))), dim3(64 * seql_waves_for(p.count)), 0, stream, a, p, seql_items_for(p.count), seql_items_per_wave(p.count));
+        hipLaunchKernelGGL(zstd_pipe_sequences_lane_kernel<true>, dim3((unsigned)((p.count + seql_items_for(p.count, ks) - 1) / seql_items_for(p.count, ks))), dim3(64 * seql_waves_for(p.count, ks)), 0, stream, a, p, seql_items_for(p.count, ks), seql_items_per_wave(p.count, ks));
         // A frame is one wavefront's work whatever its size: a pass of few frames leaves the LDS idle, and a window of 32 KiB instead of 4 turns most
         // of a text frame's far matches (offsets beyond the window: 64-byte sectors re-read through the L2) into LDS reads
         if (nItems <= 1024) {  // (four wavefronts per CU on 256 CUs: what 32 KiB windows leave room for)
@@ -2089,7 +2082,7 @@ hipError_t launch_zstd_mb_stages(const BatchArgs& a, hipStream_t stream, zp::Pip
 }  // namespace
 void* zstd_decompress_pipe_general_scratch(void* scratch, int32_t nBlocks, int32_t tileMax) { return (uint8_t*)scratch + pipe_layout(nBlocks, tileMax).general; }
 
-hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, void* scratch, void* generalScratch, int32_t tileMax, const ZstdMbProvider* mbp)
+hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, void* scratch, void* generalScratch, int32_t tileMax, const ZstdMbProvider* mbp, const KernelSettings& ks)
 {
     const PipeLayout L = pipe_layout(a.nBlocks, tileMax);
     uint8_t* base = (uint8_t*)scratch;
@@ -2135,12 +2128,12 @@ hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, v
         hipLaunchKernelGGL(zstd_pipe_parse_kernel, dim3((unsigned)p.count), dim3(64), 0, stream, a, p, dflt);
         // (items per wavefront in K2 / K3 of 8 instead of 16, and an 8 KiB window for the record executor, were round-2 experiments: measured in
         // round 3 within noise of the defaults on all three data sets -- profiles/r03_notes.md -- and removed)
-        launch_literals<false>(a, p, stream);
-        hipLaunchKernelGGL(zstd_pipe_sequences_lane_kernel<false>, dim3((unsigned)((p.count + seql_items_for(p.count) - 1) / seql_items_for(p.count))), dim3(64 * seql_waves_for(p.count)), 0, stream, a, p, seql_items_for(p.count), seql_items_per_wave(p.count));
+        launch_literals<false>(a, p, stream, ks);
+        hipLaunchKernelGGL(zstd_pipe_sequences_lane_kernel<false>, dim3((unsigned)((p.count + seql_items_for(p.count, ks) - 1) / seql_items_for(p.count, ks))), dim3(64 * seql_waves_for(p.count, ks)), 0, stream, a, p, seql_items_for(p.count, ks), seql_items_per_wave(p.count, ks));
         constexpr int GS = 4, IN_RING = 128, OUT_RING = 256;
         // (a tile of few items: every item to the record executor, a wavefront each -- the rings give an item four lanes, and an item of long sequences is then a
         // serial chain of 5.4 ms whatever else the chip does: 64 frames 15.2 ms a call, 6.8 of it the sequence stage's own chain, 5.4 this one)
-        const int32_t execMode = g_zstd_pipe_exec == 2 && p.count <= ZSTD_EXEC_ALL_RECORDS_MAX_ITEMS ? 1 : (int32_t)g_zstd_pipe_exec;
+        const int32_t execMode = ks.zstdExec == 2 && p.count <= ZSTD_EXEC_ALL_RECORDS_MAX_ITEMS ? 1 : (int32_t)ks.zstdExec;
         if (execMode != 0) {
             hipLaunchKernelGGL(zstd_pipe_execute2_kernel<>, dim3((unsigned)p.count), dim3(64), 0, stream, a, p, execMode);
         }
@@ -2152,7 +2145,7 @@ hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, v
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (mbOn) {
-        e = launch_zstd_mb_stages(a, stream, p, dflt, mbp);
+        e = launch_zstd_mb_stages(a, stream, p, dflt, mbp, ks);
         if (e != hipSuccess) return e;
     }
     return launch_zstd_decompress_list(a, stream, generalScratch, p.fallback, p.fallbackCount);
@@ -2460,7 +2453,7 @@ int64_t zstd_stream_step_scratch_bytes(int32_t blocks)
 // kept -- lies; the step's output starts at startPos and may reach outLimit; closing: the step ends the frame, with a checksum word to verify if
 // hasChecksum.  result[0..2] (host): blocks decoded, bytes produced, checksum verdict (1 ok, 0 mismatch, -1 none checked).  Synchronous.
 hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t scratchBytes, void* carryDev, const uint8_t* dSrc, int32_t srcLen, int32_t blocks, uint8_t* dOut,
-                                   int32_t startPos, int32_t outLimit, int32_t closing, int32_t hasChecksum, uint32_t expected, int32_t* result)
+                                   int32_t startPos, int32_t outLimit, int32_t closing, int32_t hasChecksum, uint32_t expected, int32_t* result, const KernelSettings& ks)
 {
     ZstdStreamCarry* carry = (ZstdStreamCarry*)carryDev;
     const StepLayout L = step_layout(blocks + 1, (uint32_t)blocks * (uint32_t)((zp::LIT_STRIDE + 63) / 64 + 1), (uint32_t)blocks * 43691u + 64u);
@@ -2530,8 +2523,8 @@ hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t sc
     hipLaunchKernelGGL(zstd_mb_fill_kernel, dim3(1), dim3(64), 0, stream, a, p);
     hipLaunchKernelGGL(zstd_ss_ghost_kernel, dim3(1), dim3(64), 0, stream, p, carry);
     hipLaunchKernelGGL(zstd_mb_parse_kernel, dim3((unsigned)p.count), dim3(64), 0, stream, a, p, dflt);
-    launch_literals<true>(a, p, stream);
-    hipLaunchKernelGGL(zstd_pipe_sequences_lane_kernel<true>, dim3((unsigned)((p.count + seql_items_for(p.count) - 1) / seql_items_for(p.count))), dim3(64 * seql_waves_for(p.count)), 0, stream, a, p, seql_items_for(p.count), seql_items_per_wave(p.count));
+    launch_literals<true>(a, p, stream, ks);
+    hipLaunchKernelGGL(zstd_pipe_sequences_lane_kernel<true>, dim3((unsigned)((p.count + seql_items_for(p.count, ks) - 1) / seql_items_for(p.count, ks))), dim3(64 * seql_waves_for(p.count, ks)), 0, stream, a, p, seql_items_for(p.count, ks), seql_items_per_wave(p.count, ks));
     hipLaunchKernelGGL(zstd_ss_execute_kernel<32768>, dim3(1), dim3(64), 0, stream, a, p, carry, startPos);
     hipLaunchKernelGGL(zstd_ss_carry_kernel, dim3(1), dim3(64), 0, stream, p, carry);
     hipLaunchKernelGGL(zstd_ss_checksum_kernel, dim3(1), dim3(64), 0, stream, dOut + startPos, carry, closing != 0 && hasChecksum != 0 ? 1 : 0, expected);

@@ -16,6 +16,7 @@
 //             slides).  `chunked` == 0 (context option zstd.stream.chunked) refuses such streams instead.
 #include "zstd_compress_body.h"
 #include "achip_xxhash.h"
+#include "achip_launch.h"
 
 namespace achip {
 

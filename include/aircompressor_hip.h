@@ -184,7 +184,8 @@ void achip_ctx_destroy(achip_ctx* ctx);
 int32_t achip_ctx_device(achip_ctx* ctx);
 void* achip_ctx_stream(achip_ctx* ctx);           /* the hipStream_t the batched calls launch on */
 int32_t achip_ctx_synchronize(achip_ctx* ctx);    /* hipStreamSynchronize */
-/* tuning knobs (kernel variant selection); name/value pairs documented in DESIGN.md. returns 0 or status */
+/* tuning knobs (kernel variant selection) of this context -- a mixed batch's helper contexts take a copy of them; name/value pairs documented
+ * in DESIGN.md. returns 0 or status */
 int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value);
 /* diagnostics of the LAST batched call on this context (synchronizes the stream); -1 = unknown name / nothing recorded.
  * "zstd.decompress.fallback_items": items the five-stage pipeline handed to the one-kernel decoder;
@@ -193,8 +194,8 @@ int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value);
  *   (ZstdOutputStream's output; ZstdFrameCompressor's and libzstd's beyond 128 KiB), their blocks, and how many of them the pipeline's
  *   multi-block stages finished (the rest went to the one-kernel decoder); option "zstd.decompress.stream_blocks" sizes those stages;
  * "lz4.decompress.mixed_groups": auto mode's count of mixed 16-block groups of the last LZ4 / Snappy decode (-1: no probe ran);
- * "decompress.choice": the decoder auto mode ran (0 LDS rings, 1 a lane per block with copy steps, 2 a lane per block with an LDS
- *   output window; -1: no probe ran).  DESIGN.md 8b lists every option and statistic. */
+ * "decompress.choice": the decoder auto mode ran (0 LDS rings, 3 two passes; -1: no probe ran).  DESIGN.md 8b lists every option and
+ *   statistic. */
 int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name);
 
 /* device / pinned memory helpers; addresses are usable as MemorySegment.ofAddress */

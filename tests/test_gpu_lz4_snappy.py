@@ -95,6 +95,23 @@ def test_lz4_two_tier_encoder_is_bit_exact_with_oracle(o, mem_waves):
         g.set_option("lz4.compress.tier_min_blocks", 5120)
 
 
+def test_kernel_options_belong_to_their_context(o):
+    """Options are per context: B's lz4.compress.mem_waves = 0 does not reach A, which sizes its scratch for the two-tier kernel and runs it; both write the
+    oracle's bytes."""
+    from tests.gpu_harness import GpuBatch
+    a, b = GpuBatch(0), GpuBatch(0)
+    blocks = [d for _, d, _ in common.corpus_sample() if len(d) <= 65536][:8]
+    caps = [o.max_compressed_length("lz4", len(x)) for x in blocks]
+    want = [o.compress("lz4", x) for x in blocks]
+    b.set_option("lz4.compress.mem_waves", 0)
+    a.set_option("lz4.compress.tier_min_blocks", 1)
+    for g in (a, b):
+        outs, status, _ = g.run(CODECS["lz4"]["c"], blocks, caps)
+        assert all(s == 0 for s in status), status
+        assert outs == want
+    assert a.codec.native.get_stat("decompress.scratch_bytes") >= (16 << 20) + 4096
+
+
 @pytest.mark.parametrize("codec", ["lz4", "snappy"])
 @pytest.mark.parametrize("cfg", DECODERS)
 def test_decompress_matches_plaintext_all_decoder_configs(gb, o, codec, cfg):

@@ -294,7 +294,7 @@ def test_sequence_stage_wavefronts_per_workgroup(o, waves):
         assert [hashlib.sha256(p).digest() for p in outs] == want
         assert g.codec.native.get_stat("zstd.decompress.fallback_items") == 0
     finally:
-        g.set_option("zstd.decompress.seq_waves", DEFAULT_SEQ_WAVES)  # (process-wide)
+        g.set_option("zstd.decompress.seq_waves", DEFAULT_SEQ_WAVES)
 
 
 @pytest.mark.parametrize("items", [8, 10, 13, 16, 20])
@@ -322,7 +322,7 @@ def test_literal_stage_items_per_wavefront(o, items):
         assert [hashlib.sha256(p).digest() for p in outs] == want
         assert g.codec.native.get_stat("zstd.decompress.fallback_items") == 0
     finally:
-        g.set_option("zstd.decompress.lit_items", DEFAULT_LIT_ITEMS)  # (process-wide)
+        g.set_option("zstd.decompress.lit_items", DEFAULT_LIT_ITEMS)
 
 
 def test_pipeline_takes_java_encoded_frames(gbd, o):

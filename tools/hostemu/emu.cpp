@@ -16,25 +16,24 @@ extern "C" { long long achip_emu_counters[16]; }  // development counters of ker
 #include <vector>
 // the probes of the decoders' auto mode are not built here: the probe statistics stay
 // zero, which picks the ring decoders
-namespace achip {
-hipError_t launch_snappy_element_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
-hipError_t launch_lz4_sequence_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
-hipError_t launch_lz4_mixed_groups(const BatchArgs&, hipStream_t, int32_t*, int32_t) { return hipSuccess; }
-}  // namespace achip
+hipError_t achip::launch_snappy_element_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
+hipError_t achip::launch_lz4_sequence_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
+hipError_t achip::launch_lz4_mixed_groups(const BatchArgs&, hipStream_t, int32_t*, int32_t) { return hipSuccess; }
 extern "C" int emu_batch(int op, const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, uint8_t* dstBase, const int64_t* dstOff,
                          const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n)
 {
     achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, 0};
     if (op == 24 || op == 25 || op == 26 || op == 27 || op == 34 || op == 35 || op == 36 || op == 37) {  // two-pass decoders (24 / 25 LZ4 with a lane per block parsing, 26 / 27 with a wavefront per block; 34 / 35 and 36 / 37 Snappy likewise); odd ops: a tiny arena, so that blocks fall back
         const bool snappy = op >= 34, tiny = (op & 1) != 0;
-        achip::g_lz4_parse_mode = op == 26 || op == 27 ? 2 : 1;
-        achip::g_snappy_parse_mode = op == 36 || op == 37 ? 2 : 1;
+        achip::KernelSettings ks;
+        ks.lz4Parse = op == 26 || op == 27 ? 2 : 1;
+        ks.snappyParse = op == 36 || op == 37 ? 2 : 1;
         static std::vector<uint8_t> scratch;
         const int64_t bytes = tiny ? 4096 + ((n * 12 + 4095) & ~4095LL) + 4 * 4096 : achip::lz4_twopass_scratch_bytes(n);
         scratch.assign((size_t)bytes, 0xCD);
         a.ringPad = 16;
-        return snappy ? achip::launch_snappy_decompress_twopass(a, nullptr, scratch.data(), bytes, 1, 0, 2, nullptr)
-                      : achip::launch_lz4_decompress_twopass(a, nullptr, scratch.data(), bytes, 1, 0, 2, nullptr);
+        return snappy ? achip::launch_snappy_decompress_twopass(a, nullptr, scratch.data(), bytes, 1, 0, nullptr, ks)
+                      : achip::launch_lz4_decompress_twopass(a, nullptr, scratch.data(), bytes, 1, 0, nullptr, ks);
     }
     if (op == 16 || op == 17) {  // default ring decoders at GS = 1 (compact / large rings)
         a.ringPad = 16;
@@ -68,7 +67,7 @@ extern "C" int emu_hadoop(int op, int snappy, int bufferSize, int variant, const
     scratch.assign((size_t)bytes, 0xCD);
     static std::vector<uint8_t> auxBuffer;
     const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { auxBuffer.assign((size_t)bytes, 0xCD); return auxBuffer.data(); }, nullptr};
-    return op == 0 ? achip::launch_hadoop_decompress(a, nullptr, scratch.data(), snappy != 0, bufferSize, variant, &aux) : achip::launch_hadoop_compress(a, nullptr, scratch.data(), snappy != 0, bufferSize);
+    return op == 0 ? achip::launch_hadoop_decompress(a, nullptr, scratch.data(), snappy != 0, bufferSize, variant, &aux, achip::KernelSettings()) : achip::launch_hadoop_compress(a, nullptr, scratch.data(), snappy != 0, bufferSize);
 }
 
 // the executor for records of any length (achip_seqexec2.h exec_records, used by the Zstd pipeline): one block, one wavefront
@@ -100,7 +99,7 @@ extern "C" int emu_lz4frame(int variant, const uint8_t* srcBase, const int64_t* 
     static std::vector<uint8_t> scratch, auxBuffer;
     scratch.assign((size_t)achip::lz4frame_decompress_scratch_bytes(n, variant), 0xCD);
     const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { auxBuffer.assign((size_t)bytes, 0xCD); return auxBuffer.data(); }, nullptr};
-    return achip::launch_lz4frame_decompress(a, nullptr, scratch.data(), variant, &aux);
+    return achip::launch_lz4frame_decompress(a, nullptr, scratch.data(), variant, &aux, achip::KernelSettings());
 }
 
 // x-snappy-framed streams (snappy_frame.hip), reader variant 2: walk, the chunks through the two-pass Snappy decoder, CRC verification, fold
@@ -111,5 +110,5 @@ extern "C" int emu_snappyframed(int variant, const uint8_t* srcBase, const int64
     static std::vector<uint8_t> scratch, auxBuffer;
     scratch.assign((size_t)achip::snappyframed_decompress_scratch_bytes(n), 0xCD);
     const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { auxBuffer.assign((size_t)bytes, 0xCD); return auxBuffer.data(); }, nullptr};
-    return achip::launch_snappyframed_decompress(a, nullptr, scratch.data(), variant, &aux);
+    return achip::launch_snappyframed_decompress(a, nullptr, scratch.data(), variant, &aux, achip::KernelSettings());
 }

@@ -25,7 +25,7 @@ extern "C" int emu_zstd_full(const uint8_t* srcBase, const int64_t* srcOff, cons
     static std::vector<uint8_t> scratch;
     scratch.assign((size_t)achip::zstd_decompress_scratch_bytes(n, 0), 0xCD);
     const achip::ZstdMbProvider mbp{all_mb_get, nullptr, passBlocks};
-    const int r = achip::launch_zstd_decompress(a, nullptr, scratch.data(), (int64_t)scratch.size(), variant, 0, passBlocks >= 16 ? &mbp : nullptr);
+    const int r = achip::launch_zstd_decompress(a, nullptr, scratch.data(), (int64_t)scratch.size(), variant, 0, passBlocks >= 16 ? &mbp : nullptr, achip::KernelSettings());
     if (counters != nullptr) {
         memcpy(counters, scratch.data(), 256);
     }

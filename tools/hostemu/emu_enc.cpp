@@ -25,15 +25,17 @@ extern "C" int emu_encode(int op, const uint8_t* srcBase, const int64_t* srcOff,
         int maxLen = 0;
         for (int i = 0; i < n; i++) maxLen = srcLen[i] > maxLen ? srcLen[i] : maxLen;
         scratch.assign((size_t)achip::lz4_compress_scratch_bytes(), 0xCD);
-        achip::g_lz4_tier_workgroups = 2;  // (the persistent grid: the emulator runs its wavefronts one after the other)
-        achip::g_lz4_tier_min_blocks = 1;   // (... and its batches are small)
-        achip::g_lz4_mem_waves = (option >> 4) & 3 ? ((option >> 4) & 3) - 1 : 1;  // (option bits 4, 5: 1 = one wavefront per block, 2 / 3 = one / two memory-tier wavefronts; 0 = the default)
-        return achip::launch_lz4_compress(a, nullptr, option & 15, maxLen, scratch.data());
+        achip::KernelSettings ks;
+        ks.lz4TierWorkgroups = 2;  // (the persistent grid: the emulator runs its wavefronts one after the other)
+        ks.lz4TierMinBlocks = 1;   // (... and its batches are small)
+        ks.lz4MemWaves = (option >> 4) & 3 ? ((option >> 4) & 3) - 1 : 1;  // (option bits 4, 5: 1 = one wavefront per block, 2 / 3 = one / two memory-tier wavefronts; 0 = the default)
+        return achip::launch_lz4_compress(a, nullptr, option & 15, maxLen, scratch.data(), (int64_t)scratch.size(), ks);
     }
     if (op == 3) {
         scratch.assign((size_t)achip::snappy_compress_scratch_bytes(n), 0xCD);
-        achip::g_snappy_tier_workgroups = 2;  // (the persistent grid: the emulator runs its wavefronts one after the other)
-        return achip::launch_snappy_compress(a, nullptr, option & 15, scratch.data(), (option & 16) == 0);  // (option bit 4: the sub-blocks in turn, as until round 5)
+        achip::KernelSettings ks;
+        ks.snappyTierWorkgroups = 2;  // (the persistent grid: the emulator runs its wavefronts one after the other)
+        return achip::launch_snappy_compress(a, nullptr, option & 15, scratch.data(), (option & 16) == 0, ks);  // (option bit 4: the sub-blocks in turn, as until round 5)
     }
     if (op == 5 || op == 14) {
         if (op == 5) a.ringPad = option == 1 ? 1 : (option == 3 ? 3 : 0);  // (what achip_abi.cpp does: the one-kernel path reads the variant from the spare field)

@@ -81,7 +81,7 @@ extern "C" int emu_zstd_stream_step(void* carry, const uint8_t* src, int32_t src
     static std::vector<uint8_t> scratch;
     const int64_t bytes = achip::zstd_stream_step_scratch_bytes(blocks);
     scratch.assign((size_t)bytes, 0xCD);
-    return (int)achip::launch_zstd_stream_step(nullptr, scratch.data(), bytes, carry, src, srcLen, blocks, out, startPos, outLimit, closing, hasChecksum, expected, result);
+    return (int)achip::launch_zstd_stream_step(nullptr, scratch.data(), bytes, carry, src, srcLen, blocks, out, startPos, outLimit, closing, hasChecksum, expected, result, achip::KernelSettings());
 }
 
 // passBlocks: blocks per pass of the multi-block stages (0: multi-block frames go to the fallback list); counters: the pipeline's 64 counter words
@@ -94,17 +94,18 @@ extern "C" int emu_zstd_pipe(const uint8_t* srcBase, const int64_t* srcOff, cons
     static std::vector<uint8_t> scratch;
     const int64_t bytes = achip::zstd_decompress_pipe_scratch_bytes(n, tile);
     scratch.assign((size_t)bytes, 0xCD);
-    achip::g_zstd_pipe_exec = execMode & 3;
-    achip::g_zstd_seq_waves = (execMode >> 4) & 7 ? (execMode >> 4) & 7 : 1;  // (bits 4 .. 6: wavefronts per workgroup of the sequence stage, with full workgroups)
-    achip::g_zstd_seq_spread = (execMode >> 4) & 7 ? 1 : 256;
-    achip::g_zstd_lit_items = ((execMode >> 2) & 3) == 1 ? 8 : (((execMode >> 2) & 3) == 2 ? 10 : (((execMode >> 2) & 3) == 3 ? 13 : 16));  // (bits 2, 3: items per wavefront of the literal stage; 13: the split table layout)
-    if ((execMode >> 7) & 1) achip::g_zstd_lit_items = 20;  // (bit 7: 16 items, symbols and lengths by symbol)
+    achip::KernelSettings ks;
+    ks.zstdExec = execMode & 3;
+    ks.zstdSeqWaves = (execMode >> 4) & 7 ? (execMode >> 4) & 7 : 1;  // (bits 4 .. 6: wavefronts per workgroup of the sequence stage, with full workgroups)
+    ks.zstdSeqSpread = (execMode >> 4) & 7 ? 1 : 256;
+    ks.zstdLitItems = ((execMode >> 2) & 3) == 1 ? 8 : (((execMode >> 2) & 3) == 2 ? 10 : (((execMode >> 2) & 3) == 3 ? 13 : 16));  // (bits 2, 3: items per wavefront of the literal stage; 13: the split table layout)
+    if ((execMode >> 7) & 1) ks.zstdLitItems = 20;  // (bit 7: 16 items, symbols and lengths by symbol)
     achip::g_fallback.clear();
     for (int32_t i = 0; i < n; i++) {
         status[i] = -999;  // "not written"
     }
     achip::ZstdMbProvider mbp{emu_mb_get, nullptr, passBlocks};
-    achip::launch_zstd_decompress_pipe(a, nullptr, scratch.data(), achip::zstd_decompress_pipe_general_scratch(scratch.data(), n, tile), tile, passBlocks > 0 ? &mbp : nullptr);
+    achip::launch_zstd_decompress_pipe(a, nullptr, scratch.data(), achip::zstd_decompress_pipe_general_scratch(scratch.data(), n, tile), tile, passBlocks > 0 ? &mbp : nullptr, ks);
     memcpy(counters, scratch.data(), 256);
     for (size_t k = 0; k < achip::g_fallback.size(); k++) {
         fallback[k] = achip::g_fallback[k];
