@@ -1245,9 +1245,32 @@ int32_t achip_xxhash32_batch(achip_ctx* ctx, const void* srcBase, const int64_t*
     return 0;
 }
 
+int32_t achip_xxhash3_64_batch(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t seed, int64_t* outHash, int32_t nBuffers)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    if (nBuffers < 0) return bad_argument("nBuffers < 0");
+    if (nBuffers == 0) return 0;
+    if (!srcOff || !srcLen || !outHash) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_xxh3_batch(srcBase, srcOff, srcLen, nBuffers, (uint64_t)seed, false, outHash, ctx->stream));
+    return 0;
+}
+
+int32_t achip_xxhash3_128_batch(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t seed, int64_t* outHash, int32_t nBuffers)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    if (nBuffers < 0) return bad_argument("nBuffers < 0");
+    if (nBuffers == 0) return 0;
+    if (!srcOff || !srcLen || !outHash) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_xxh3_batch(srcBase, srcOff, srcLen, nBuffers, (uint64_t)seed, true, outHash, ctx->stream));
+    return 0;
+}
+
 namespace {
-// one host buffer: staged to the device, hashed there, 8 bytes back
-int32_t hash_host(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, bool wide, int64_t* out)
+enum class HostHash { XXH32, XXH64, XXH3_64, XXH3_128 };
+// one host buffer: staged to the device, hashed there, 8 bytes back (16 for XXH3_128: out[0] = low, out[1] = high)
+int32_t hash_host(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, HostHash kind, int64_t* out)
 {
     if (!ctx) return bad_argument("ctx is null");
     if (srcLen < 0 || srcLen > 0x7FFFFFFF) return bad_argument("length out of range");
@@ -1260,18 +1283,23 @@ int32_t hash_host(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed,
     if (srcLen > 0) memcpy(h, src, (size_t)srcLen);
     *(int64_t*)(h + metaOff) = 0;                      // srcOff
     *(int32_t*)(h + metaOff + 8) = (int32_t)srcLen;    // srcLen
-    *(int64_t*)(h + metaOff + 16) = 0;                 // result
+    *(int64_t*)(h + metaOff + 16) = 0;                 // result (16 bytes)
+    *(int64_t*)(h + metaOff + 24) = 0;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(d, h, (size_t)(metaOff + 64), hipMemcpyHostToDevice, ctx->stream));
-    if (wide) {
-        HIP_TRY(achip::launch_xxh64_batch(d, (const int64_t*)(d + metaOff), (const int32_t*)(d + metaOff + 8), 1, (uint64_t)seed, (int64_t*)(d + metaOff + 16), ctx->stream));
+    const int64_t* dOff = (const int64_t*)(d + metaOff);
+    const int32_t* dLen = (const int32_t*)(d + metaOff + 8);
+    int64_t* dOut = (int64_t*)(d + metaOff + 16);
+    switch (kind) {
+    case HostHash::XXH32: HIP_TRY(achip::launch_xxh32_batch(d, dOff, dLen, 1, (uint32_t)seed, (int32_t*)dOut, ctx->stream)); break;
+    case HostHash::XXH64: HIP_TRY(achip::launch_xxh64_batch(d, dOff, dLen, 1, (uint64_t)seed, dOut, ctx->stream)); break;
+    case HostHash::XXH3_64: HIP_TRY(achip::launch_xxh3_batch(d, dOff, dLen, 1, (uint64_t)seed, false, dOut, ctx->stream)); break;
+    case HostHash::XXH3_128: HIP_TRY(achip::launch_xxh3_batch(d, dOff, dLen, 1, (uint64_t)seed, true, dOut, ctx->stream)); break;
     }
-    else {
-        HIP_TRY(achip::launch_xxh32_batch(d, (const int64_t*)(d + metaOff), (const int32_t*)(d + metaOff + 8), 1, (uint32_t)seed, (int32_t*)(d + metaOff + 16), ctx->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(h + metaOff + 16, d + metaOff + 16, 8, hipMemcpyDeviceToHost, ctx->stream));
+    const int words = kind == HostHash::XXH3_128 ? 2 : 1;
+    HIP_TRY(hipMemcpyAsync(h + metaOff + 16, d + metaOff + 16, (size_t)(8 * words), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = *(int64_t*)(h + metaOff + 16);
+    for (int k = 0; k < words; k++) out[k] = *(int64_t*)(h + metaOff + 16 + 8 * k);
     return 0;
 }
 }  // namespace
@@ -1279,16 +1307,28 @@ int32_t hash_host(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed,
 int32_t achip_xxhash64(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash)
 {
     if (!outHash) return bad_argument("outHash is null");
-    return hash_host(ctx, src, srcLen, seed, true, outHash);
+    return hash_host(ctx, src, srcLen, seed, HostHash::XXH64, outHash);
 }
 
 int32_t achip_xxhash32(achip_ctx* ctx, const void* src, int64_t srcLen, int32_t seed, int32_t* outHash)
 {
     if (!outHash) return bad_argument("outHash is null");
     int64_t v = 0;
-    const int32_t r = hash_host(ctx, src, srcLen, seed, false, &v);
+    const int32_t r = hash_host(ctx, src, srcLen, seed, HostHash::XXH32, &v);
     *outHash = (int32_t)v;
     return r;
+}
+
+int32_t achip_xxhash3_64(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash)
+{
+    if (!outHash) return bad_argument("outHash is null");
+    return hash_host(ctx, src, srcLen, seed, HostHash::XXH3_64, outHash);
+}
+
+int32_t achip_xxhash3_128(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash)
+{
+    if (!outHash) return bad_argument("outHash is null");
+    return hash_host(ctx, src, srcLen, seed, HostHash::XXH3_128, outHash);
 }
 
 // ---- host-pointer batches: chunked, double-buffered staging (H2D || kernels || D2H || host copies) ---------------

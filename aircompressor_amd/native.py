@@ -62,6 +62,10 @@ SIGNATURES = {
     "achip_xxhash32_batch": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32]),
     "achip_xxhash64": (_i32, [_vp, _vp, _i64, _i64, _vp]),
     "achip_xxhash32": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "achip_xxhash3_64_batch": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32]),
+    "achip_xxhash3_128_batch": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32]),
+    "achip_xxhash3_64": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "achip_xxhash3_128": (_i32, [_vp, _vp, _i64, _i64, _vp]),
     "achip_device_alloc": (_vp, [_vp, _i64]),
     "achip_device_free": (_i32, [_vp, _vp]),
     "achip_host_alloc_pinned": (_vp, [_i64]),

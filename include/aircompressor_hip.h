@@ -336,6 +336,14 @@ int32_t achip_xxhash32_batch(achip_ctx* ctx, const void* srcBase, const int64_t*
 /* one HOST buffer (staged through the context's pinned buffer; synchronous): the one-shot form of the same two methods */
 int32_t achip_xxhash64(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash);
 int32_t achip_xxhash32(achip_ctx* ctx, const void* src, int64_t srcLen, int32_t seed, int32_t* outHash);
+/* ---- XXH3 (xxhash3.hip): the reference's XxHash3Native.hash(MemorySegment, long seed) and hash128(MemorySegment, long seed) ----
+ * Same conventions as achip_xxhash64[_batch]: device arrays and asynchronous on the context's stream for the batches (nBuffers == 0: no
+ * launch; a negative length hashes as empty), one staged HOST buffer for the single calls.  The 128-bit hash comes back through the pointer:
+ * outHash[2i] = low 64 bits, outHash[2i + 1] = high 64 bits (a single call fills outHash[0], outHash[1]). */
+int32_t achip_xxhash3_64_batch(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t seed, int64_t* outHash, int32_t nBuffers);
+int32_t achip_xxhash3_128_batch(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t seed, int64_t* outHash, int32_t nBuffers);
+int32_t achip_xxhash3_64(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash);
+int32_t achip_xxhash3_128(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash);
 
 /* Host-pointer batch: nBlocks independent blocks described by HOST arrays of HOST
  * pointers' offsets relative to srcBase/dstBase (host).  Stages in, launches the

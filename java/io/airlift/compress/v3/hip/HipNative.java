@@ -156,6 +156,15 @@ public final class HipNative
             MethodHandle xxhash64Batch,
             @NativeSignature(name = "achip_xxhash32_batch", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, MemorySegment.class, int.class})
             MethodHandle xxhash32Batch,
+            // XXH3 (XxHash3Native.hash / hash128 with a long seed): the 128-bit forms write low, high through the pointer
+            @NativeSignature(name = "achip_xxhash3_64", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, long.class, long.class, MemorySegment.class})
+            MethodHandle xxhash3,
+            @NativeSignature(name = "achip_xxhash3_128", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, long.class, long.class, MemorySegment.class})
+            MethodHandle xxhash3Hash128,
+            @NativeSignature(name = "achip_xxhash3_64_batch", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, long.class, MemorySegment.class, int.class})
+            MethodHandle xxhash3Batch,
+            @NativeSignature(name = "achip_xxhash3_128_batch", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, long.class, MemorySegment.class, int.class})
+            MethodHandle xxhash3Hash128Batch,
             // batched, device-resident: (op, ctx, srcBase, srcOff*, srcLen*, dstBase, dstOff*, dstCap*, outLen*, status*, errOffset*, nBlocks)
             @NativeSignature(name = "achip_batch_host", returnType = int.class, argumentTypes = {int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class,
                     MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
@@ -622,6 +631,27 @@ public final class HipNative
     public static MethodHandle xxhash32Batch()
     {
         return HANDLES.xxhash32Batch();
+    }
+
+    // handles of the XXH3 hashers (io.airlift.compress.v3.xxhash.XxHash3Hip)
+    public static MethodHandle xxhash3()
+    {
+        return HANDLES.xxhash3();
+    }
+
+    public static MethodHandle xxhash3Hash128()
+    {
+        return HANDLES.xxhash3Hash128();
+    }
+
+    public static MethodHandle xxhash3Batch()
+    {
+        return HANDLES.xxhash3Batch();
+    }
+
+    public static MethodHandle xxhash3Hash128Batch()
+    {
+        return HANDLES.xxhash3Hash128Batch();
     }
 
     /** throws what {@link #toException} builds when {@code status} is negative */
