@@ -151,22 +151,9 @@ int64_t few_blocks_record_bytes(int32_t nBlocks, int64_t perBlock)
     return std::max<int64_t>(perBlock, ((1LL << 30) / nBlocks) & ~4095LL);
 }
 
-// LZ4 and Snappy block decoding: one policy (launch_block_decode), a row per codec family -- 0 LZ4, 1 Snappy.
-struct BlockCodec {
-    hipError_t (*rings)(const achip::BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
-    hipError_t (*twopass)(const achip::BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats,
-                          const achip::KernelSettings& ks);
-    hipError_t (*sample)(const achip::BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);  // auto mode's probe of the lengths
-    int (*groupFor)(int32_t nBlocks);  // ring decoder lanes per block by the batch size
-    int64_t recordBytes, recordBytesMin;  // the two-pass decoder's record arena per block
-    int32_t shortLimit;                   // sequences (LZ4) / elements (Snappy) shorter than this are short ones (lz4_pick)
-};
-const BlockCodec kBlockCodecs[2] = {
-    {achip::launch_lz4_decompress_rings, achip::launch_lz4_decompress_twopass, achip::launch_lz4_sequence_sample, achip::lz4_ring_group_for,
-     achip::LZ4_RECORD_BYTES_PER_BLOCK, achip::LZ4_RECORD_BYTES_PER_BLOCK_MIN, 12},
-    {achip::launch_snappy_decompress_rings, achip::launch_snappy_decompress_twopass, achip::launch_snappy_element_sample, achip::snappy_ring_group_for,
-     achip::SNAPPY_RECORD_BYTES_PER_BLOCK, achip::SNAPPY_RECORD_BYTES_PER_BLOCK_MIN, 6},
-};
+// LZ4 and Snappy block decoding: one policy (launch_block_decode) over the row of its codec family in achip::kBlockCodecs (achip_launch.h) -- 0 LZ4, 1 Snappy.
+using achip::BlockCodec;
+using achip::kBlockCodecs;
 
 // The decoder auto mode picks from a call's probe statistics (the first six words) for a batch of `nBlocks` blocks of family `fam`: 3 two passes (a mixed
 // or a short-sequence batch), 0 rings.  The rule of lz4_pick (achip_device.h), on the host.

@@ -1,6 +1,6 @@
-// achip_launch.h -- the host launchers one translation unit calls in another: achip_abi.cpp calls them all, the container readers call the
-// block decoders, the Zstd decoder's two halves call each other, and tools/hostemu calls them on the CPU.  Every file that defines or calls
-// one includes this header.
+// achip_launch.h -- the host launchers one translation unit calls in another: achip_abi.cpp calls them all, the container readers hand their
+// listed blocks to launch_listed_decode (block_decode.cpp), which calls the block decoders, the Zstd decoder's two halves call each other, and
+// tools/hostemu calls them on the CPU.  Every file that defines or calls one includes this header.
 #pragma once
 #include "achip_device.h"
 #include "achip_settings.h"
@@ -33,6 +33,29 @@ constexpr int64_t SNAPPY_RECORD_BYTES_PER_BLOCK = 131072, SNAPPY_RECORD_BYTES_PE
 hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32_t* mixedGroups, int32_t minBlocks);
 hipError_t launch_lz4_sequence_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
 hipError_t launch_snappy_element_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
+// the two families as one table (block_decode.cpp), a row per family -- 0 LZ4, 1 Snappy: the block API's policy (achip_abi.cpp launch_block_decode) and
+// the containers' (launch_listed_decode) read the same row
+struct BlockCodec {
+    hipError_t (*rings)(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);
+    hipError_t (*twopass)(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks);
+    hipError_t (*sample)(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);  // auto mode's probe of the lengths
+    int (*groupFor)(int32_t nBlocks);     // ring decoder lanes per block by the batch size
+    int64_t recordBytes, recordBytesMin;  // the two-pass decoder's record arena per block
+    int32_t shortLimit;                   // sequences (LZ4) / elements (Snappy) shorter than this are short ones (lz4_pick)
+};
+extern const BlockCodec kBlockCodecs[2];
+// What a container reader wants for the batch it listed on the device (lists::ChunkBatch::as_batch).
+struct ListedWant {
+    bool sync;            // false: the host never learns the count -- no synchronisation, the launches are sized for the list's capacity
+    bool probe;           // (sync) true: the family's length probe decides between the two passes and the rings; false: always the two passes
+    bool ringsWithoutArena;  // (sync) the two passes wanted but no arena to be had: true = the rings instead, false = nothing is decoded
+    int64_t recordScale;  // arena per listed block: the family's recordBytes x this ...
+    int roomWord;         // ... or, if >= 0 and larger, 3/2 of the blocks' mean room, rounded up to 4 KiB, from the 64-bit sum at counters[roomWord]
+};
+// The one decode path of a listed batch.  `counters`: the list's ([1] = its sealed count); `stats`: four probe words at most 60 words behind
+// `counters`, zero on entry (the readers clear their counter page once).  *decoded: a decoder was launched over the list.
+hipError_t launch_listed_decode(const BatchArgs& listed, int fam, hipStream_t stream, const int32_t* counters, int32_t* stats, const AuxScratch* aux, const KernelSettings& ks,
+                                const ListedWant& want, bool* decoded);
 
 // ---- LZ4 / Snappy block encoders ----
 // the two-tier LZ4 kernel runs only with at least lz4_compress_scratch_bytes() of scratch (scratchBytes); with less, the one-wavefront kernel writes the same bytes

@@ -51,6 +51,26 @@ struct ArenaHeader {  // leads the scratch
     int32_t pad[61];
 };
 
+// the two-pass decoders' scratch: [header, 4 KiB][meta n x 8][only n x 4][arena, 4 KiB aligned]
+struct TwoPassLayout {
+    ArenaHeader* hdr;
+    BlockMeta* meta;
+    int32_t* only;      // per block: 1 = its records did not fit, the ring decoder takes it
+    uint64_t* arena;
+    int32_t maxChunks;  // what of `scratchBytes` lies behind the fixed part, in chunks (one to spare: the executor's unconditional record loads)
+    static int64_t fixed(int32_t nBlocks) { return 4096 + (((int64_t)nBlocks * 12 + 4095) & ~4095LL); }
+    TwoPassLayout(void* scratch, int64_t scratchBytes, int32_t nBlocks)
+    {
+        uint8_t* s = (uint8_t*)scratch;
+        hdr = (ArenaHeader*)s;
+        meta = (BlockMeta*)(s + 4096);
+        only = (int32_t*)(s + 4096 + (int64_t)nBlocks * 8);
+        arena = (uint64_t*)(s + fixed(nBlocks));
+        const int64_t chunks = (scratchBytes - fixed(nBlocks)) / (CHUNK_SLOTS * 8) - 1;
+        maxChunks = (int32_t)(chunks > 0x7FFFFFFF ? 0x7FFFFFFF : chunks);
+    }
+};
+
 // ---- wave helpers (DPP on the device, shuffles under tools/hostemu) ---------------------------------------------------------------
 __device__ __forceinline__ int32_t wave_scan_incl(int32_t x, int lane)
 {

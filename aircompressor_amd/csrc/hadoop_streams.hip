@@ -37,13 +37,14 @@
 #include "lz4_compress_mw.h"
 #include "snappy_compress_mw.h"
 #include "achip_launch.h"
+#include "achip_lists.h"
 
 namespace achip {
 
 namespace hdp {
 constexpr int IN_RING = 2048, OUT_RING = 4096;
 constexpr int32_t STREAM_EOF = -1000000;  // internal: end of stream
-constexpr int32_t MAX_CHUNKS = 1 << 20;
+using lists::CAPACITY;
 
 __host__ __device__ __forceinline__ int32_t input_max_size(bool snappy, int32_t bufferSize)
 {
@@ -375,22 +376,23 @@ __global__ __launch_bounds__(64) void hadoop_serial_decompress_kernel(BatchArgs 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the chunk-parallel reader
-struct ChunkList {
+struct ChunkList : lists::ChunkBatch {  // per chunk: a batch for the block decoders (counters [16..]: probe statistics of the decoders' choice, [32] serial cursor) ...
+    int32_t* cExpect;   // ... and the block length it has to produce
     // per stream
     int32_t* sFirst;
     int32_t* sCount;
     int32_t* sOut;      // plaintext bytes if every chunk decodes as declared
     int32_t* sSerial;   // 1: the serial kernel takes the stream
-    // per chunk: a batch for the block decoders ...
-    int64_t* cSrcOff;
-    int32_t* cSrcLen;
-    int64_t* cDstOff;
-    int32_t* cDstCap;
-    int32_t* cOutLen;
-    int32_t* cStatus;
-    int64_t* cErrOff;
-    int32_t* cExpect;   // ... and the block length it has to produce
-    int32_t* counters;  // [0] chunks allocated, [1] chunks in the batch, [16..] probe statistics of the decoders' auto choice
+    void carve(lists::Carver& k, int64_t nStreams)
+    {
+        int32_t* counterWords = k.take<int32_t>(lists::COUNTER_WORDS);
+        sFirst = k.take<int32_t>(nStreams);
+        sCount = k.take<int32_t>(nStreams);
+        sOut = k.take<int32_t>(nStreams);
+        sSerial = k.take<int32_t>(nStreams);
+        ChunkBatch::carve(k, counterWords);
+        cExpect = k.take<int32_t>(CAPACITY);
+    }
 };
 
 // The Java loops over one stream without the chunk bodies; returns false when the stream is not of the simple shape (the serial kernel
@@ -454,7 +456,7 @@ __global__ __launch_bounds__(64) void hadoop_walk_kernel(BatchArgs a, ChunkList 
     int32_t n = 0, out = 0;
     const bool simple = walk_stream<SNAPPY, false>(a, L, stream, 0, n, out);
     const int32_t first = simple && n > 0 ? atomicAdd(L.counters, n) : 0;
-    const bool fits = simple && (int64_t)first + n <= MAX_CHUNKS;
+    const bool fits = simple && (int64_t)first + n <= CAPACITY;
     L.sFirst[stream] = first;
     L.sCount[stream] = fits ? n : 0;
     L.sOut[stream] = out;
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(64) void hadoop_walk_kernel(BatchArgs a, ChunkList 
         walk_stream<SNAPPY, true>(a, L, stream, first, n, out);
     }
     else if (simple && !fits) {  // the part of this stream's range that lies inside the arrays: empty blocks nobody looks at
-        for (int64_t c = first; c < (int64_t)first + n && c < MAX_CHUNKS; c++) {
+        for (int64_t c = first; c < (int64_t)first + n && c < CAPACITY; c++) {
             L.cSrcOff[c] = 0;
             L.cSrcLen[c] = 0;
             L.cDstOff[c] = 0;
@@ -471,12 +473,6 @@ __global__ __launch_bounds__(64) void hadoop_walk_kernel(BatchArgs a, ChunkList 
             L.cExpect[c] = -1;
         }
     }
-}
-
-__global__ void hadoop_seal_kernel(ChunkList L)
-{
-    const int32_t allocated = L.counters[0];
-    L.counters[1] = allocated < MAX_CHUNKS ? allocated : MAX_CHUNKS;
 }
 
 __global__ __launch_bounds__(64) void hadoop_fold_kernel(BatchArgs a, ChunkList L)
@@ -502,15 +498,7 @@ __global__ __launch_bounds__(64) void hadoop_fold_kernel(BatchArgs a, ChunkList 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the writer
-struct BlockList {
-    int32_t* sFirst;   // per stream
-    int32_t* sCount;
-    int32_t* sStatus;
-    int32_t* bStream;  // per chunk
-    int32_t* bIndex;
-    int32_t* bSize;    // compressed bytes at the worst-case position
-    int32_t* counters; // [0] chunks allocated, [1] chunks in the list, [2] encode cursor, [3] compact cursor
-};
+using BlockList = lists::WriterList;  // (bSize: a chunk's compressed bytes, or the block encoder's status)
 
 template <bool SNAPPY>
 __global__ __launch_bounds__(64) void hadoop_plan_kernel(BatchArgs a, BlockList L, int32_t bufferSize)
@@ -537,24 +525,10 @@ __global__ __launch_bounds__(64) void hadoop_plan_kernel(BatchArgs a, BlockList 
             st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_HDP_MAX_OUTPUT);
         }
     }
-    const int32_t n = st == 0 ? (int32_t)chunks : 0;
-    const int32_t first = n > 0 ? atomicAdd(L.counters, n) : 0;
-    if (st == 0 && (int64_t)first + n > MAX_CHUNKS) {  // (more than a million chunks in one call)
+    if (!lists::plan_entries(L, stream, st == 0 ? (int32_t)chunks : 0)) {  // (more than a million chunks in one call)
         st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_UNSUPPORTED);
     }
-    L.sFirst[stream] = first;
-    L.sCount[stream] = st == 0 ? n : 0;
     L.sStatus[stream] = st;
-    for (int64_t k = 0; k < n && first + k < MAX_CHUNKS; k++) {
-        L.bStream[first + k] = st == 0 ? stream : -1;
-        L.bIndex[first + k] = (int32_t)k;
-    }
-}
-
-__global__ void hadoop_seal_blocks_kernel(BlockList L)
-{
-    const int32_t allocated = L.counters[0];
-    L.counters[1] = allocated < MAX_CHUNKS ? allocated : MAX_CHUNKS;
 }
 
 // LZ4: a wavefront per workgroup around its table in LDS.  Snappy (round 3): the two tiers of the block encoder (snappy_compress.hip) -- a 32 KB
@@ -666,49 +640,36 @@ int64_t hdp_internal_bytes(int32_t bufferSize)
 }
 }  // namespace
 
-int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize)
+// the reader's scratch: its lists, then the serial kernel's buffers, one per wavefront
+static uint8_t* carve_hadoop_reader(lists::Carver& k, hdp::ChunkList& L, int64_t nStreams, int32_t bufferSize)
 {
-    const int64_t n = nStreams < 1 ? 1 : nStreams;
-    const int64_t waves = n < HDP_SERIAL_WAVES ? n : HDP_SERIAL_WAVES;
-    return 4096 + n * 16 + 64 + (int64_t)hdp::MAX_CHUNKS * (8 * 3 + 4 * 5) + 4096 + waves * hdp_internal_bytes(bufferSize);
+    L.carve(k, nStreams);
+    return k.take<uint8_t>((nStreams < HDP_SERIAL_WAVES ? nStreams : HDP_SERIAL_WAVES) * hdp_internal_bytes(bufferSize));
 }
 
-// variant 1 (default): the chunks through the ring decoders (with the probes' other choices behind them); variant 2 (round 2, written
-// without a GPU at hand: not the default until measured): the chunks through the TWO-PASS decoders -- their record arena is
-// sized by the chunk count, which only the device knows, so the host reads it back (one synchronisation) and asks `aux` for the arena;
-// chunks whose records do not fit, and every chunk when there is no arena, take the ring decoder as in variant 1.
+int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize)
+{
+    lists::Carver k(nullptr);
+    hdp::ChunkList L;
+    carve_hadoop_reader(k, L, nStreams < 1 ? 1 : nStreams, bufferSize);
+    return k.used();
+}
+
+// variant 0: a wavefront per stream only.  The others list the chunks and hand them to launch_listed_decode (achip_launch.h): 1, or no `aux`:
+// without a synchronisation; 2: always through the two-pass decoders -- their record arena is sized by the chunk count, which only
+// the device knows, so the host reads it back (one synchronisation) and asks `aux` for the arena; 3 (the default): the length probe of the
+// block API's auto mode decides between the two.
 hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* base = (uint8_t*)scratch;
-    int32_t* counters = (int32_t*)base;
+    lists::Carver k(scratch);
+    hdp::ChunkList L;
+    uint8_t* internals = carve_hadoop_reader(k, L, a.nBlocks, bufferSize);
+    int32_t* counters = L.counters;
     hipError_t e = hipMemsetAsync(counters, 0, 4096, stream);
     if (e != hipSuccess) return e;
-    hdp::ChunkList L;
-    uint8_t* p = base + 4096;
-    const int64_t n = a.nBlocks;
-    auto take = [&](int64_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 15) & ~(int64_t)15;
-        return r;
-    };
-    L.counters = counters;
-    L.sFirst = (int32_t*)take(4 * n);
-    L.sCount = (int32_t*)take(4 * n);
-    L.sOut = (int32_t*)take(4 * n);
-    L.sSerial = (int32_t*)take(4 * n);
-    const int64_t C = hdp::MAX_CHUNKS;
-    L.cSrcOff = (int64_t*)take(8 * C);
-    L.cDstOff = (int64_t*)take(8 * C);
-    L.cErrOff = (int64_t*)take(8 * C);
-    L.cSrcLen = (int32_t*)take(4 * C);
-    L.cDstCap = (int32_t*)take(4 * C);
-    L.cOutLen = (int32_t*)take(4 * C);
-    L.cStatus = (int32_t*)take(4 * C);
-    L.cExpect = (int32_t*)take(4 * C);
-    uint8_t* internals = take(64);
     const int64_t internalMax = hdp_internal_bytes(bufferSize);
     const unsigned serialGrid = (unsigned)(a.nBlocks < HDP_SERIAL_WAVES ? a.nBlocks : HDP_SERIAL_WAVES);
     if (variant == 0) {  // one wavefront per stream only
@@ -719,92 +680,12 @@ hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
     if (snappy) hipLaunchKernelGGL(hdp::hadoop_walk_kernel<true>, dim3(perStream), dim3(64), 0, stream, a, L);
     else hipLaunchKernelGGL(hdp::hadoop_walk_kernel<false>, dim3(perStream), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(hdp::hadoop_seal_kernel, dim3(1), dim3(1), 0, stream, L);
-    // the chunks as a batch of blocks whose size is known on the device only: launches are sized for the arrays
-    BatchArgs c = a;
-    c.srcOff = L.cSrcOff;
-    c.srcLen = L.cSrcLen;
-    c.dstOff = L.cDstOff;
-    c.dstCap = L.cDstCap;
-    c.outLen = L.cOutLen;
-    c.status = L.cStatus;
-    c.errOffset = L.cErrOff;
-    c.nBlocks = hdp::MAX_CHUNKS;
-    c.nBlocksDev = counters + 1;
-    c.only = nullptr;
-    c.onlyStats = nullptr;
-    int32_t* stats = counters + 16;
-    bool viaTwoPass = false;
-    int32_t nChunksHost = -1;  // the chunk count once the host has read it (variants 2 and 3)
-    if ((variant == 2 || variant == 3) && aux != nullptr && aux->get != nullptr) {
-        // variant 3 (the default since round 3): the probes of the batched block API's auto mode (lz4_pick: mixed 16-chunk groups,
-        // bytes per sampled sequence / element) run on the chunk list BEFORE the one synchronisation that reads the chunk count back, and
-        // their verdict comes back with it -- text-like chunks (short sequences) go through the two-pass decoders, long copies
-        // through the rings: measured (profiles/r03_notes.md, 1024 streams x 4 MiB) LZ4 818 / 83 GiB/s on fragments / corpus with the
-        // rings, 271 / 158 with the two-pass decoders; Snappy 474 / 39 against 230 / 107
-        int32_t head[20] = {0};
-        if (variant == 3) {
-            e = hipMemsetAsync(stats, 0, 4 * sizeof(int32_t), stream);
-            if (e == hipSuccess) e = snappy ? launch_snappy_element_sample(c, stream, stats, 0, 0) : launch_lz4_sequence_sample(c, stream, stats, 0, 0);
-            if (e != hipSuccess) return e;
-        }
-        e = hipMemcpyAsync(head, counters, sizeof(head), hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        const int32_t nChunks = head[1];
-        nChunksHost = nChunks;
-        bool wantTwoPass = true;
-        if (variant == 3) {
-            // (only the sampled sequence lengths count here: a stream's last chunk is a short one, so "compressed sizes within a 16-chunk
-            // group differ by 2x" -- the block API's sign of a mixed batch -- holds for every group of a batch of streams)
-            const int32_t* v = head + 16;
-            wantTwoPass = v[1] > 0 && (int64_t)v[2] < (int64_t)(snappy ? 6 : 12) * (int64_t)v[1];
-        }
-        if (!wantTwoPass) {
-        }
-        else if (nChunks > 0) {
-            // records per chunk as for 64 KiB blocks (lz4_decompress_v7.hip twopass_scratch_bytes), scaled to the streams' chunk size
-            const int64_t per64k = snappy ? 131072 : 98304;
-            const int64_t perChunk = per64k * (((int64_t)(bufferSize > 65536 ? bufferSize : 65536) + 65535) / 65536);
-            const int64_t bytes = twopass_scratch_bytes(nChunks, perChunk);
-            void* arena = aux->get(aux->user, bytes);
-            if (arena != nullptr) {
-                BatchArgs t = c;
-                t.nBlocks = nChunks;
-                t.nBlocksDev = nullptr;
-                e = snappy ? launch_snappy_decompress_twopass(t, stream, arena, bytes, 4, 0, nullptr, ks) : launch_lz4_decompress_twopass(t, stream, arena, bytes, 16, 0, nullptr, ks);
-                if (e != hipSuccess) return e;
-                viaTwoPass = true;
-            }
-        }
-        else {
-            viaTwoPass = true;  // (nothing listed)
-        }
-    }
-    if (!viaTwoPass && nChunksHost >= 0) {
-        // the host knows the chunk count (variant 3 chose the rings): one launch of the size that fits, no probes
-        BatchArgs t = c;
-        t.nBlocks = nChunksHost;
-        t.nBlocksDev = nullptr;
-        if (nChunksHost > 0) {
-            e = snappy ? launch_snappy_decompress_rings(t, stream, snappy_ring_group_for(nChunksHost), 0, nullptr) : launch_lz4_decompress_rings(t, stream, lz4_ring_group_for(nChunksHost), 0, nullptr);
-        }
-    }
-    else if (!viaTwoPass) {
-    // LZ4: the ring decoder at two lane-group sizes: 4 lanes per chunk from 32768 chunks on, 16 below (721 -> 814 GiB/s fragments, 56 -> 83 corpus at 16384 chunks) (a stream's chunks are up to 256 KiB: a few
-    // thousand of them at 4 lanes each leave most of the chip idle); the chunk count, known on the device only, picks one
-    BatchArgs big = c, small = c;
-    big.countLo = 32768;
-    small.countHi = 32768;
-    if (snappy) {
-        e = launch_snappy_decompress_rings(c, stream, 4, 0, nullptr);  // (16 lanes per chunk measured slower for Snappy: 390 against 481 GiB/s)
-    }
-    else {
-        e = launch_lz4_decompress_rings(big, stream, 4, 0, nullptr);
-        if (e == hipSuccess) e = launch_lz4_decompress_rings(small, stream, 16, 0, nullptr);
-    }
-    }
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, counters, lists::CAPACITY);
+    // records per chunk as for 64 KiB blocks, scaled to the streams' chunk size
+    const bool sync = (variant == 2 || variant == 3) && aux != nullptr && aux->get != nullptr;
+    const ListedWant want{sync, variant == 3, true, ((int64_t)(bufferSize > 65536 ? bufferSize : 65536) + 65535) / 65536, -1};
+    bool decoded = false;
+    e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), snappy ? 1 : 0, stream, counters, counters + 16, aux, ks, want, &decoded);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(hdp::hadoop_fold_kernel, dim3(perStream), dim3(64), 0, stream, a, L);
     // streams of any other shape, and those a chunk of which did not decode as declared
@@ -815,13 +696,21 @@ hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void
 
 namespace {
 constexpr int HADOOP_SNAPPY_WORKGROUPS = 256 * 5;  // five 32 KB LDS tables per CU, four wavefronts around each
-constexpr int64_t HADOOP_SNAPPY_SLAB_BYTES = (int64_t)HADOOP_SNAPPY_WORKGROUPS * 3 * snc::MAX_HASH_TABLE_SIZE * 2 + 64;
+constexpr int64_t HADOOP_SNAPPY_SLAB_WORDS = (int64_t)HADOOP_SNAPPY_WORKGROUPS * 3 * snc::MAX_HASH_TABLE_SIZE;
+// the writer's scratch: its list, then the Snappy encoder's table slabs
+uint16_t* carve_hadoop_writer(lists::Carver& k, hdp::BlockList& L, int64_t nStreams)
+{
+    L.carve(k, k.take<int32_t>(lists::COUNTER_WORDS), nStreams, false);
+    return k.take<uint16_t>(HADOOP_SNAPPY_SLAB_WORDS);
+}
 }
 
 int64_t hadoop_compress_scratch_bytes(int32_t nStreams)
 {
-    const int64_t n = nStreams < 1 ? 1 : nStreams;
-    return 4096 + n * 12 + 64 + (int64_t)hdp::MAX_CHUNKS * 12 + 4096 + HADOOP_SNAPPY_SLAB_BYTES;
+    lists::Carver k(nullptr);
+    hdp::BlockList L;
+    carve_hadoop_writer(k, L, nStreams < 1 ? 1 : nStreams);
+    return k.used();
 }
 
 hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize)
@@ -829,38 +718,23 @@ hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* 
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* base = (uint8_t*)scratch;
-    int32_t* counters = (int32_t*)base;
-    hipError_t e = hipMemsetAsync(counters, 0, 4096, stream);
-    if (e != hipSuccess) return e;
-    uint8_t* p = base + 4096;
-    auto take = [&](int64_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 15) & ~(int64_t)15;
-        return r;
-    };
+    lists::Carver k(scratch);
     hdp::BlockList L;
-    const int64_t n = a.nBlocks;
-    L.counters = counters;
-    L.sFirst = (int32_t*)take(4 * n);
-    L.sCount = (int32_t*)take(4 * n);
-    L.sStatus = (int32_t*)take(4 * n);
-    L.bStream = (int32_t*)take(4 * (int64_t)hdp::MAX_CHUNKS);
-    L.bIndex = (int32_t*)take(4 * (int64_t)hdp::MAX_CHUNKS);
-    L.bSize = (int32_t*)take(4 * (int64_t)hdp::MAX_CHUNKS);
-    uint16_t* const slabs = (uint16_t*)take(HADOOP_SNAPPY_SLAB_BYTES - 64);
+    uint16_t* const slabs = carve_hadoop_writer(k, L, a.nBlocks);
+    hipError_t e = hipMemsetAsync(L.counters, 0, 4096, stream);
+    if (e != hipSuccess) return e;
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
     const unsigned encodeGrid = snappy ? HADOOP_SNAPPY_WORKGROUPS : 256 * 10;  // (LZ4: chunks beyond 64 KiB take the 16 KB table: ten wavefronts per CU)
     const unsigned compactGrid = (unsigned)a.nBlocks;
     if (snappy) {
         hipLaunchKernelGGL(hdp::hadoop_plan_kernel<true>, dim3(perStream), dim3(64), 0, stream, a, L, bufferSize);
-        hipLaunchKernelGGL(hdp::hadoop_seal_blocks_kernel, dim3(1), dim3(1), 0, stream, L);
+        hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, lists::CAPACITY);
         hipLaunchKernelGGL(hdp::hadoop_encode_kernel<true>, dim3(encodeGrid), dim3(256), 0, stream, a, L, bufferSize, slabs);
         hipLaunchKernelGGL(hdp::hadoop_compact_kernel<true>, dim3(compactGrid), dim3(64), 0, stream, a, L, bufferSize);
     }
     else {
         hipLaunchKernelGGL(hdp::hadoop_plan_kernel<false>, dim3(perStream), dim3(64), 0, stream, a, L, bufferSize);
-        hipLaunchKernelGGL(hdp::hadoop_seal_blocks_kernel, dim3(1), dim3(1), 0, stream, L);
+        hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, lists::CAPACITY);
         hipLaunchKernelGGL(hdp::hadoop_encode_kernel<false>, dim3(encodeGrid), dim3(64), 0, stream, a, L, bufferSize, slabs);
         hipLaunchKernelGGL(hdp::hadoop_compact_kernel<false>, dim3(compactGrid), dim3(64), 0, stream, a, L, bufferSize);
     }

@@ -617,16 +617,14 @@ __global__ __launch_bounds__(64, WAVES) void seq_execute2_kernel(BatchArgs a, co
     sx2::exec_block<WIN>(win, a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], arena, m.firstChunk, m.count, (int)threadIdx.x);
 }
 
-// scratch: [header 256 B][meta n x 8][only n x 4][arena, 4 KiB aligned]
+// scratch: sx::TwoPassLayout
 // (perBlock: arena bytes per block -- 8 bytes per record.  Pieces of <= 16 + 16 bytes: text-like 64 KiB blocks make 6 000 .. 8 500 LZ4 records and
 // 8 500 .. 11 500 Snappy records, a few percent of them empty ones from trips a lane sat out; blocks that do not fit go to the ring decoder.)
 int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock)
 {
-    const int64_t fixed = 4096 + (((int64_t)nBlocks * 12 + 4095) & ~4095LL);
-    int64_t arena = (int64_t)nBlocks * perBlock + (64LL << 20) + 4096;  // (+ the chunk the executor's record loads may run into)
-    return fixed + arena;
+    return sx::TwoPassLayout::fixed(nBlocks) + (int64_t)nBlocks * perBlock + (64LL << 20) + 4096;  // (+ the chunk the executor's record loads may run into)
 }
-int64_t lz4_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_bytes(nBlocks, 98304); }
+int64_t lz4_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_bytes(nBlocks, LZ4_RECORD_BYTES_PER_BLOCK); }
 
 // the execute pass (shared with snappy_decompress_v5.hip).  (Round 2's timing aids, executor and parser variants that left work out, were
 // development tools and went in round 4 together with their build switch)
@@ -645,30 +643,21 @@ hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream,
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* s = (uint8_t*)scratch;
-    sx::ArenaHeader* hdr = (sx::ArenaHeader*)s;
-    sx::BlockMeta* meta = (sx::BlockMeta*)(s + 4096);
-    int32_t* only = (int32_t*)(s + 4096 + (int64_t)a.nBlocks * 8);
-    const int64_t fixed = 4096 + (((int64_t)a.nBlocks * 12 + 4095) & ~4095LL);
-    uint64_t* arena = (uint64_t*)(s + fixed);
-    const int64_t chunks = (scratchBytes - fixed) / (sx::CHUNK_SLOTS * 8) - 1;  // (one to spare: the executor's unconditional record loads)
-    const int32_t maxChunks = (int32_t)(chunks > 0x7FFFFFFF ? 0x7FFFFFFF : chunks);
-    hipError_t e = hipMemsetAsync(hdr, 0, sizeof(sx::ArenaHeader), stream);
+    const sx::TwoPassLayout s(scratch, scratchBytes, a.nBlocks);
+    hipError_t e = hipMemsetAsync(s.hdr, 0, sizeof(sx::ArenaHeader), stream);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((a.nBlocks + 63) / 64)), wg(64);
-    {
     const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.lz4Parse == 2 || (ks.lz4Parse == 0 && a.nBlocks <= LZ4_WAVE_PARSE_MAX_BLOCKS));
     if (wavePerBlock) {
-        hipLaunchKernelGGL(lz4_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
+        hipLaunchKernelGGL(lz4_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
     }
     else {
-        hipLaunchKernelGGL(lz4_parse2_kernel, grid, wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
+        hipLaunchKernelGGL(lz4_parse2_kernel, grid, wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
     }
-    e = launch_seq_execute2(a, stream, meta, arena, stats, 12);
+    e = launch_seq_execute2(a, stream, s.meta, s.arena, stats, 12);
     if (e != hipSuccess) return e;
-    }
     BatchArgs f = a;
-    f.only = only;
+    f.only = s.only;
     f.onlyStats = stats;
     f.onlyShortLimit = 12;
     e = launch_lz4_decompress_rings(f, stream, groupSize, ringClass, nullptr);

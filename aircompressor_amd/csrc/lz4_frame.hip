@@ -10,6 +10,7 @@
 #include "lz4_decode_body.h"
 #include "achip_xxhash.h"
 #include "achip_launch.h"
+#include "achip_lists.h"
 
 namespace achip {
 
@@ -170,29 +171,30 @@ __device__ int32_t decompress_item(const uint8_t* __restrict__ in, int32_t inLen
 
 }  // namespace lz4f
 
-// ---- reader variant 1 (round 2; written without a GPU at hand, not the default until measured): the blocks of the regular frames as ONE
-// batch for the two-pass block decoder, as hadoop_streams.hip does it for Hadoop streams.
+// ---- reader variants 1 and 2 (2: the default): the blocks of the regular frames as ONE batch for the block decoders, as hadoop_streams.hip
+// does it for Hadoop streams.
 //   walk   a lane per item: the item is exactly one frame, its header is in order, no block checksums; every compressed block becomes an
 //          entry of a device-side batch, block k at output position k x blockMaxSize with at most a block's room.  That position is a GUESS
 //          -- a block's length is not in the frame -- which holds for what every writer produces (all blocks but the last are full);
-//   decode the batch through the two-pass decoder; its record arena is sized after the host has read back the number of blocks and their room;
+//   decode the batch through launch_listed_decode (achip_launch.h); the record arena of the two-pass decoder is sized after the host
+//          has read back the number of blocks and their room;
 //   fold   a wavefront per item walks the frame again: compressed blocks must have decoded, all but the last to a full block; stored blocks
 //          are copied now; content checksum and content size are checked; anything else flags the item;
 //   then the kernel above runs the flagged items, and every item of any other shape, from scratch (the Java loop: same status / offset).
 namespace lz4f {
-constexpr int32_t MAX_LIST_BLOCKS = 1 << 20;
-
-struct BlockList {
-    int32_t* counters;   // [0] entries allocated, [1] entries in use (sealed), [2..3] the entries' room (64 bits)
+struct BlockList : lists::ChunkBatch {  // (counters [2..3]: the entries' room, 64 bits; [8..11]: probe statistics)
     int32_t* sFirst;     // per item: first entry, -1 = not on this path
     int32_t* sSerial;    // per item: 1 = the wavefront-per-item kernel decodes it
-    int64_t* cSrcOff;
-    int64_t* cDstOff;
-    int64_t* cErrOff;
-    int32_t* cSrcLen;
-    int32_t* cDstCap;
-    int32_t* cOutLen;
-    int32_t* cStatus;
+    int32_t* cursor;     // the wavefront-per-item kernel's
+    void carve(lists::Carver& k, int64_t nItems, bool listed)
+    {
+        cursor = k.take<int32_t>(lists::COUNTER_WORDS);
+        if (listed) {
+            sFirst = k.take<int32_t>(nItems);
+            sSerial = k.take<int32_t>(nItems);
+            ChunkBatch::carve(k, cursor + 16);
+        }
+    }
 };
 
 struct FrameShape {
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(64) void lz4frame_walk_kernel(BatchArgs a, lz4f::Bl
         return;
     }
     const int32_t first = atomicAdd(L.counters, f.compressedBlocks);
-    if ((int64_t)first + f.compressedBlocks > MAX_LIST_BLOCKS) {
+    if ((int64_t)first + f.compressedBlocks > lists::CAPACITY) {
         return;
     }
     frame_blocks<true>(a, item, f, L, first);
@@ -326,12 +328,6 @@ __global__ __launch_bounds__(64) void lz4frame_walk_kernel(BatchArgs a, lz4f::Bl
     atomicAdd((unsigned long long*)(L.counters + 2), (unsigned long long)room);
     L.sFirst[item] = first;
     L.sSerial[item] = 0;
-}
-
-__global__ void lz4frame_seal_kernel(lz4f::BlockList L)
-{
-    const int32_t allocated = L.counters[0];
-    L.counters[1] = allocated < lz4f::MAX_LIST_BLOCKS ? allocated : lz4f::MAX_LIST_BLOCKS;
 }
 
 // a wavefront per item on the list path
@@ -428,106 +424,42 @@ __global__ __launch_bounds__(64) void lz4frame_decompress_kernel(BatchArgs a, in
 
 int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant)
 {
-    if (variant != 1 && variant != 2) {
-        return 4096;
-    }
-    const int64_t n = nItems < 1 ? 1 : nItems;
-    return 4096 + n * 8 + 64 + (int64_t)lz4f::MAX_LIST_BLOCKS * (8 * 3 + 4 * 4) + 4096;
+    lists::Carver k(nullptr);
+    lz4f::BlockList().carve(k, nItems < 1 ? 1 : nItems, variant == 1 || variant == 2);
+    return k.used();
 }
 
-// variant 0 (default): a wavefront per item; variant 1: the block list (above)
+// variant 0, or no `aux`: a wavefront per item; variants 1 and 2: the block list (above).  1: always the two-pass decoder.  2 (the default): the
+// sequence-length probe of the block API's auto mode decides -- short sequences (text: 7.8 -> 13.4 GiB/s) take the two-pass decoder, and leave
+// every item to the wavefront-per-item kernel when there is no arena for it; long ones the ring decoders, the lanes per block by how many blocks
+// there are (profiles/r05_groupsweep.txt: 16 384 blocks of 256 KiB 890 GiB/s at 16 lanes, 1 024 of 4 MiB 85 at 64) -- the wavefront-per-item
+// kernel, where these frames went until round 5, is a serial reader that was never the fast one: 149 GiB/s on 16 384 frames of 256 KiB.
 hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* base = (uint8_t*)scratch;
-    int32_t* counter = (int32_t*)base;
-    hipError_t e = hipMemsetAsync(counter, 0, 4096, stream);
+    const bool listed = (variant == 1 || variant == 2) && aux != nullptr && aux->get != nullptr;
+    lists::Carver k(scratch);
+    lz4f::BlockList L;
+    L.carve(k, a.nBlocks, listed);
+    hipError_t e = hipMemsetAsync(L.cursor, 0, 4096, stream);
     if (e != hipSuccess) return e;
     const int32_t maxWaves = 256 * 16;
     const unsigned grid = (unsigned)(a.nBlocks < maxWaves ? a.nBlocks : maxWaves);
-    if ((variant != 1 && variant != 2) || aux == nullptr || aux->get == nullptr) {
-        hipLaunchKernelGGL(lz4frame_decompress_kernel<false>, dim3(grid), dim3(64), 0, stream, a, counter, (const int32_t*)nullptr);
+    if (!listed) {
+        hipLaunchKernelGGL(lz4frame_decompress_kernel<false>, dim3(grid), dim3(64), 0, stream, a, L.cursor, (const int32_t*)nullptr);
         return hipGetLastError();
     }
-    lz4f::BlockList L;
-    uint8_t* p = base + 4096;
-    auto take = [&](int64_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 15) & ~(int64_t)15;
-        return r;
-    };
-    const int64_t n = a.nBlocks, C = lz4f::MAX_LIST_BLOCKS;
-    L.counters = counter + 16;
-    L.sFirst = (int32_t*)take(4 * n);
-    L.sSerial = (int32_t*)take(4 * n);
-    L.cSrcOff = (int64_t*)take(8 * C);
-    L.cDstOff = (int64_t*)take(8 * C);
-    L.cErrOff = (int64_t*)take(8 * C);
-    L.cSrcLen = (int32_t*)take(4 * C);
-    L.cDstCap = (int32_t*)take(4 * C);
-    L.cOutLen = (int32_t*)take(4 * C);
-    L.cStatus = (int32_t*)take(4 * C);
     hipLaunchKernelGGL(lz4frame_walk_kernel, dim3((unsigned)((a.nBlocks + 63) / 64)), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(lz4frame_seal_kernel, dim3(1), dim3(1), 0, stream, L);
-    // variant 2 (the default since round 3): the sequence-length probe of the block API's auto mode runs on the listed blocks before the
-    // synchronisation; long sequences (a lane walking them pays per sequence, the wavefront-per-item kernel moves 64 bytes per step: 75
-    // against 22 GiB/s on the fragments frames) leave every item to the wavefront-per-item kernel, short ones (text: 7.8 -> 13.4 GiB/s) take the list
-    int32_t* stats = counter + 24;
-    if (variant == 2) {
-        BatchArgs c = a;
-        c.srcOff = L.cSrcOff;
-        c.srcLen = L.cSrcLen;
-        c.nBlocks = (int32_t)C;
-        c.nBlocksDev = L.counters + 1;
-        e = launch_lz4_sequence_sample(c, stream, stats, 0, 0);
-        if (e != hipSuccess) return e;
-    }
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, lists::CAPACITY);
     // the number of listed blocks and their room decide the record arena: the one synchronisation of the call
-    int32_t counts[12] = {0};
-    e = hipMemcpyAsync(counts, L.counters, sizeof(counts), hipMemcpyDeviceToHost, stream);
+    const ListedWant want{true, variant == 2, false, 1, 2};
+    bool decoded = false;
+    e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), 0, stream, L.counters, L.counters + 8, aux, ks, want, &decoded);
     if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return e;
-    const int32_t nListed = counts[1];
-    const bool isShort = counts[8 + 1] > 0 && (int64_t)counts[8 + 2] < 12LL * (int64_t)counts[8 + 1];
-    int32_t decoded = 0;
-    BatchArgs c = a;
-    c.srcOff = L.cSrcOff;
-    c.srcLen = L.cSrcLen;
-    c.dstOff = L.cDstOff;
-    c.dstCap = L.cDstCap;
-    c.outLen = L.cOutLen;
-    c.status = L.cStatus;
-    c.errOffset = L.cErrOff;
-    c.nBlocks = nListed;
-    c.nBlocksDev = nullptr;
-    c.only = nullptr;
-    c.onlyStats = nullptr;
-    if (nListed > 0 && (variant == 1 || isShort)) {
-        long long room = 0;
-        __builtin_memcpy(&room, counts + 2, 8);
-        // records per block as for the block codec (96 KiB of arena per 64 KiB of output: lz4_decompress_v7.hip), by the blocks' room
-        const int64_t perBlock = ((room + nListed - 1) / nListed * 3 / 2 + 4095) & ~4095LL;
-        const int64_t bytes = twopass_scratch_bytes(nListed, perBlock < 98304 ? 98304 : perBlock);
-        void* arena = aux->get(aux->user, bytes);
-        if (arena != nullptr) {
-            e = launch_lz4_decompress_twopass(c, stream, arena, bytes, 16, 0, nullptr, ks);
-            if (e != hipSuccess) return e;
-            decoded = 1;
-        }
-    }
-    else if (nListed > 0) {
-        // long sequences (round 5): the listed blocks through the ring decoders, the lanes per block by how many blocks there are (profiles/r05_groupsweep.txt: 16 384
-        // blocks of 256 KiB 890 GiB/s at 16 lanes, 1 024 of 4 MiB 85 at 64) -- the wavefront-per-item kernel below, where these frames went until now, is a serial
-        // reader that was never the fast one: 149 GiB/s on 16 384 frames of 256 KiB
-        e = launch_lz4_decompress_rings(c, stream, lz4_ring_group_for(nListed), 0, nullptr);
-        if (e != hipSuccess) return e;
-        decoded = 1;
-    }
-    hipLaunchKernelGGL(lz4frame_fold_kernel, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, L, decoded);
-    hipLaunchKernelGGL(lz4frame_decompress_kernel<true>, dim3(grid), dim3(64), 0, stream, a, counter, (const int32_t*)L.sSerial);
+    hipLaunchKernelGGL(lz4frame_fold_kernel, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, L, decoded ? 1 : 0);
+    hipLaunchKernelGGL(lz4frame_decompress_kernel<true>, dim3(grid), dim3(64), 0, stream, a, L.cursor, (const int32_t*)L.sSerial);
     return hipGetLastError();
 }
 

@@ -640,37 +640,28 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
 // 8 192: 53 / 129; 16 384: 98 / 156; 32 768: 157 / 173; 65 536: 236 / 182.
 constexpr int32_t SNAPPY_WAVE_PARSE_MAX_BLOCKS = 32768;
 
-int64_t snappy_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_bytes(nBlocks, 131072); }
+int64_t snappy_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_bytes(nBlocks, SNAPPY_RECORD_BYTES_PER_BLOCK); }
 
 hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* s = (uint8_t*)scratch;
-    sx::ArenaHeader* hdr = (sx::ArenaHeader*)s;
-    sx::BlockMeta* meta = (sx::BlockMeta*)(s + 4096);
-    int32_t* only = (int32_t*)(s + 4096 + (int64_t)a.nBlocks * 8);
-    const int64_t fixed = 4096 + (((int64_t)a.nBlocks * 12 + 4095) & ~4095LL);
-    uint64_t* arena = (uint64_t*)(s + fixed);
-    const int64_t chunks = (scratchBytes - fixed) / (sx::CHUNK_SLOTS * 8) - 1;  // (one to spare: the second executor's unconditional record loads)
-    const int32_t maxChunks = (int32_t)(chunks > 0x7FFFFFFF ? 0x7FFFFFFF : chunks);
-    hipError_t e = hipMemsetAsync(hdr, 0, sizeof(sx::ArenaHeader), stream);
+    const sx::TwoPassLayout s(scratch, scratchBytes, a.nBlocks);
+    hipError_t e = hipMemsetAsync(s.hdr, 0, sizeof(sx::ArenaHeader), stream);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((a.nBlocks + 63) / 64)), wg(64);
-    {
-        const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.snappyParse == 2 || (ks.snappyParse == 0 && a.nBlocks <= SNAPPY_WAVE_PARSE_MAX_BLOCKS));
-        if (wavePerBlock) {
-            hipLaunchKernelGGL(snappy_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
-        }
-        else {
-            hipLaunchKernelGGL(snappy_parse2_kernel, grid, wg, 0, stream, a, hdr, meta, only, arena, maxChunks, stats);
-        }
-        e = launch_seq_execute2(a, stream, meta, arena, stats, 6);
-        if (e != hipSuccess) return e;
+    const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.snappyParse == 2 || (ks.snappyParse == 0 && a.nBlocks <= SNAPPY_WAVE_PARSE_MAX_BLOCKS));
+    if (wavePerBlock) {
+        hipLaunchKernelGGL(snappy_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
     }
+    else {
+        hipLaunchKernelGGL(snappy_parse2_kernel, grid, wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
+    }
+    e = launch_seq_execute2(a, stream, s.meta, s.arena, stats, 6);
+    if (e != hipSuccess) return e;
     BatchArgs f = a;
-    f.only = only;
+    f.only = s.only;
     f.onlyStats = stats;
     f.onlyShortLimit = 6;
     e = launch_snappy_decompress_rings(f, stream, groupSize, ringClass, nullptr);

@@ -16,6 +16,7 @@
 #include "snappy_compress_mw.h"
 #include "achip_crc32c.h"
 #include "achip_launch.h"
+#include "achip_lists.h"
 
 namespace achip {
 
@@ -276,19 +277,8 @@ __global__ __launch_bounds__(64) void snappyframed_compress_kernel(BatchArgs a, 
 //            left with all loads of a round before its stores is safe at any distance).
 // Streams whose blocks do not fit into the list go to the one-wavefront-per-stream kernel above.
 namespace snf {
-constexpr int32_t MAX_BLOCKS = 1 << 20;
 constexpr int32_t WORST_CHUNK = 8 + MAX_BLOCK_SIZE;
-
-struct BlockList {
-    int32_t* sFirst;   // per stream
-    int32_t* sCount;
-    int32_t* sStatus;
-    int32_t* sSerial;
-    int32_t* bStream;  // per block
-    int32_t* bIndex;
-    int32_t* bSize;    // chunk bytes written at the worst-case position (header included)
-    int32_t* counters; // [0] blocks allocated, [1] blocks in the list, [2] encode cursor, [3] compact cursor, [32] serial cursor
-};
+using BlockList = lists::WriterList;  // (bSize: a chunk's bytes, header included; counters [32]: the serial kernel's cursor)
 
 __global__ __launch_bounds__(64) void snappyframed_plan_kernel(BatchArgs a, BlockList L)
 {
@@ -312,23 +302,9 @@ __global__ __launch_bounds__(64) void snappyframed_plan_kernel(BatchArgs a, Bloc
             st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_SNF_MAX_OUTPUT);
         }
     }
-    const int32_t n = st == 0 ? (int32_t)blocks : 0;
-    const int32_t first = n > 0 ? atomicAdd(L.counters, n) : 0;
-    const bool fits = (int64_t)first + n <= MAX_BLOCKS;
-    L.sFirst[stream] = first;
-    L.sCount[stream] = fits ? n : 0;
+    const bool fits = lists::plan_entries(L, stream, st == 0 ? (int32_t)blocks : 0);
     L.sStatus[stream] = st;
-    L.sSerial[stream] = fits ? 0 : 1;
-    for (int64_t k = 0; k < n && first + k < MAX_BLOCKS; k++) {
-        L.bStream[first + k] = fits ? stream : -1;  // -1: a hole (its stream goes the other way)
-        L.bIndex[first + k] = (int32_t)k;
-    }
-}
-
-__global__ void snappyframed_seal_blocks_kernel(BlockList L)
-{
-    const int32_t allocated = L.counters[0];
-    L.counters[1] = allocated < MAX_BLOCKS ? allocated : MAX_BLOCKS;
+    L.sSerial[stream] = fits ? 0 : 1;  // (its stream goes the other way)
 }
 
 __global__ __launch_bounds__(256) void snappyframed_encode_kernel(BatchArgs a, BlockList L, uint8_t* outSlabs, uint16_t* tableSlabs)
@@ -432,12 +408,28 @@ __global__ __launch_bounds__(64) void snappyframed_compact_kernel(BatchArgs a, B
 namespace {
 constexpr int SNF_COMPRESS_WAVES = 256 * 3;    // one wavefront per stream: 44 KB of LDS each
 constexpr int SNF_ENCODE_WORKGROUPS = 256 * 3; // four wavefronts around one LDS table + the CRC tables
-}
+// the writer's scratch: the counters, the serial kernel's slabs, the encode kernel's output and table slabs, the list
+struct SnfWriterScratch {
+    uint8_t* serialSlabs;
+    uint8_t* outSlabs;
+    uint16_t* tableSlabs;
+    snf::BlockList L;
+    void carve(lists::Carver& k, int64_t nStreams)
+    {
+        int32_t* counterWords = k.take<int32_t>(lists::COUNTER_WORDS);
+        serialSlabs = k.take<uint8_t>((int64_t)SNF_COMPRESS_WAVES * snf::SLAB_BYTES);
+        outSlabs = k.take<uint8_t>((int64_t)SNF_ENCODE_WORKGROUPS * 4 * snf::SLAB_BYTES);
+        tableSlabs = k.take<uint16_t>((int64_t)SNF_ENCODE_WORKGROUPS * 3 * snc::MAX_HASH_TABLE_SIZE);
+        L.carve(k, counterWords, nStreams, true);
+    }
+};
+}  // namespace
+
 int64_t snappyframed_compress_scratch_bytes(int32_t nStreams)
 {
-    const int64_t n = nStreams < 1 ? 1 : nStreams;
-    return 4096 + (int64_t)SNF_COMPRESS_WAVES * snf::SLAB_BYTES + (int64_t)SNF_ENCODE_WORKGROUPS * (4 * snf::SLAB_BYTES + 3 * snc::MAX_HASH_TABLE_SIZE * 2) +
-           n * 16 + (int64_t)snf::MAX_BLOCKS * 12 + 4096;
+    lists::Carver k(nullptr);
+    SnfWriterScratch().carve(k, nStreams < 1 ? 1 : nStreams);
+    return k.used();
 }
 
 hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant)
@@ -445,40 +437,24 @@ hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, 
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* base = (uint8_t*)scratch;
-    int32_t* counters = (int32_t*)base;
+    lists::Carver k(scratch);
+    SnfWriterScratch S;
+    S.carve(k, a.nBlocks);
+    const snf::BlockList& L = S.L;
+    int32_t* counters = L.counters;
     hipError_t e = hipMemsetAsync(counters, 0, 4096, stream);
     if (e != hipSuccess) return e;
-    uint8_t* serialSlabs = base + 4096;
     const unsigned serialGrid = (unsigned)(a.nBlocks < SNF_COMPRESS_WAVES ? a.nBlocks : SNF_COMPRESS_WAVES);
     if (variant == 0) {  // one wavefront per stream
-        hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, serialSlabs, counters + 32, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, S.serialSlabs, counters + 32, (const int32_t*)nullptr);
         return hipGetLastError();
     }
-    uint8_t* p = serialSlabs + (int64_t)SNF_COMPRESS_WAVES * snf::SLAB_BYTES;
-    auto take = [&](int64_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 63) & ~(int64_t)63;
-        return r;
-    };
-    uint8_t* outSlabs = take((int64_t)SNF_ENCODE_WORKGROUPS * 4 * snf::SLAB_BYTES);
-    uint16_t* tableSlabs = (uint16_t*)take((int64_t)SNF_ENCODE_WORKGROUPS * 3 * snc::MAX_HASH_TABLE_SIZE * 2);
-    snf::BlockList L;
-    const int64_t n = a.nBlocks;
-    L.counters = counters;
-    L.sFirst = (int32_t*)take(4 * n);
-    L.sCount = (int32_t*)take(4 * n);
-    L.sStatus = (int32_t*)take(4 * n);
-    L.sSerial = (int32_t*)take(4 * n);
-    L.bStream = (int32_t*)take(4 * (int64_t)snf::MAX_BLOCKS);
-    L.bIndex = (int32_t*)take(4 * (int64_t)snf::MAX_BLOCKS);
-    L.bSize = (int32_t*)take(4 * (int64_t)snf::MAX_BLOCKS);
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
     hipLaunchKernelGGL(snf::snappyframed_plan_kernel, dim3(perStream), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(snf::snappyframed_seal_blocks_kernel, dim3(1), dim3(1), 0, stream, L);
-    hipLaunchKernelGGL(snf::snappyframed_encode_kernel, dim3(SNF_ENCODE_WORKGROUPS), dim3(256), 0, stream, a, L, outSlabs, tableSlabs);
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, counters, lists::CAPACITY);
+    hipLaunchKernelGGL(snf::snappyframed_encode_kernel, dim3(SNF_ENCODE_WORKGROUPS), dim3(256), 0, stream, a, L, S.outSlabs, S.tableSlabs);
     hipLaunchKernelGGL(snf::snappyframed_compact_kernel, dim3((unsigned)(a.nBlocks < 2048 ? a.nBlocks : 2048)), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, serialSlabs, counters + 32, (const int32_t*)L.sSerial);
+    hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, S.serialSlabs, counters + 32, (const int32_t*)L.sSerial);
     return hipGetLastError();
 }
 
@@ -496,9 +472,13 @@ hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, 
 //           checksum error) gives the stream's status, else the error the walk stopped at, else the length.
 // A stream whose chunks do not fit into the descriptor arrays is left to the one-wavefront-per-stream kernel below.
 namespace snf {
-constexpr int32_t MAX_CHUNKS = 1 << 20;
+using lists::CAPACITY;
 
-struct ChunkList {
+struct ChunkList : lists::ChunkBatch {  // per chunk: a batch for the block decoders (counters [2]: verify cursor, [16..]: probe statistics, [32]: serial cursor) ...
+    // ... and what the verify / fold steps need
+    uint32_t* cCrc;
+    int32_t* cRawLen;   // >= 0: a stored chunk of this many bytes (the decoders see an empty input and are overruled); -1: compressed
+    int32_t* cPos;      // position of the chunk header in its stream
     // per stream
     int32_t* sFirst;
     int32_t* sCount;
@@ -506,19 +486,20 @@ struct ChunkList {
     int64_t* sErrOff;
     int32_t* sOut;      // plaintext bytes if every chunk decodes
     int32_t* sSerial;   // 1: handled by the serial kernel
-    // per chunk: a batch for the block decoders ...
-    int64_t* cSrcOff;
-    int32_t* cSrcLen;
-    int64_t* cDstOff;
-    int32_t* cDstCap;
-    int32_t* cOutLen;
-    int32_t* cStatus;
-    int64_t* cErrOff;
-    // ... and what the verify / fold steps need
-    uint32_t* cCrc;
-    int32_t* cRawLen;   // >= 0: a stored chunk of this many bytes (the decoders see an empty input and are overruled); -1: compressed
-    int32_t* cPos;      // position of the chunk header in its stream
-    int32_t* counters;  // [0] chunks allocated, [1] chunks in the batch (= min(allocated, MAX_CHUNKS)), [2] verify cursor, [16] mixed groups
+    void carve(lists::Carver& k, int64_t nStreams)
+    {
+        int32_t* counterWords = k.take<int32_t>(lists::COUNTER_WORDS);
+        sErrOff = k.take<int64_t>(nStreams);
+        sFirst = k.take<int32_t>(nStreams);
+        sCount = k.take<int32_t>(nStreams);
+        sStatus = k.take<int32_t>(nStreams);
+        sOut = k.take<int32_t>(nStreams);
+        sSerial = k.take<int32_t>(nStreams);
+        ChunkBatch::carve(k, counterWords);
+        cCrc = k.take<uint32_t>(CAPACITY);
+        cRawLen = k.take<int32_t>(CAPACITY);
+        cPos = k.take<int32_t>(CAPACITY);
+    }
 };
 
 __device__ __forceinline__ uint32_t rd_bytes(const uint8_t* p, int n)  // little-endian, n <= 4 (cold: byte loads)
@@ -656,7 +637,7 @@ __global__ __launch_bounds__(64) void snappyframed_walk_kernel(BatchArgs a, Chun
     int64_t eo = 0;
     walk_stream<false>(a, L, stream, 0, n, st, eo, out);
     const int32_t first = n > 0 ? atomicAdd(L.counters, n) : 0;
-    const bool fits = (int64_t)first + n <= MAX_CHUNKS;
+    const bool fits = (int64_t)first + n <= CAPACITY;
     L.sFirst[stream] = first;
     L.sCount[stream] = fits ? n : 0;
     L.sStatus[stream] = st;
@@ -667,7 +648,7 @@ __global__ __launch_bounds__(64) void snappyframed_walk_kernel(BatchArgs a, Chun
         walk_stream<true>(a, L, stream, first, n, st, eo, out);
     }
     else if (!fits) {  // the part of this stream's range that lies inside the arrays: empty blocks nobody looks at
-        for (int64_t c = first; c < (int64_t)first + n && c < MAX_CHUNKS; c++) {
+        for (int64_t c = first; c < (int64_t)first + n && c < CAPACITY; c++) {
             L.cSrcOff[c] = 0;
             L.cSrcLen[c] = 0;
             L.cDstOff[c] = 0;
@@ -677,13 +658,6 @@ __global__ __launch_bounds__(64) void snappyframed_walk_kernel(BatchArgs a, Chun
             L.cPos[c] = 0;
         }
     }
-}
-
-// the batch holds the chunks that fit: a stream that does not fit leaves a hole of descriptors nobody reads (src length 0 below)
-__global__ void snappyframed_seal_kernel(ChunkList L)
-{
-    const int32_t allocated = L.counters[0];
-    L.counters[1] = allocated < MAX_CHUNKS ? allocated : MAX_CHUNKS;
 }
 
 __global__ __launch_bounds__(64) void snappyframed_verify_kernel(BatchArgs a, ChunkList L)
@@ -750,20 +724,24 @@ __global__ __launch_bounds__(64) void snappyframed_fold_kernel(BatchArgs a, Chun
 
 int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams)
 {
-    const int64_t n = nStreams < 1 ? 1 : nStreams;
-    return 4096 + n * (4 * 5 + 8) + (int64_t)snf::MAX_CHUNKS * (8 * 3 + 4 * 7) + 4096;
+    lists::Carver k(nullptr);
+    snf::ChunkList().carve(k, nStreams < 1 ? 1 : nStreams);
+    return k.used();
 }
 
-// variant 1 (default): the chunks through the ring decoders (with the probes' other choices behind them); variant 2 (round 2, written without
-// a GPU at hand: not the default until measured): through the two-pass decoder -- the host reads the chunk count back (one
-// synchronisation) and asks `aux` for the record arena; chunks whose records do not fit take the rings as in variant 1; 0: a wavefront per stream
+// variant 0: a wavefront per stream.  The others list the chunks and hand them to launch_listed_decode (achip_launch.h): 1, or no `aux`: without a
+// synchronisation; 2: always through the two-pass decoder -- the host reads the chunk count back (one synchronisation) and asks `aux`
+// for the record arena; 3 (the default): the element-length probe of the block API's auto mode decides between the two.  A chunk holds at most
+// 64 KiB: the block codec's arena per block.
 hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
-    uint8_t* base = (uint8_t*)scratch;
-    int32_t* counters = (int32_t*)base;
+    lists::Carver k(scratch);
+    snf::ChunkList L;
+    L.carve(k, a.nBlocks);
+    int32_t* counters = L.counters;
     hipError_t e = hipMemsetAsync(counters, 0, 4096, stream);
     if (e != hipSuccess) return e;
     const int32_t maxWaves = 256 * 8;
@@ -772,98 +750,14 @@ hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream
         hipLaunchKernelGGL(snappyframed_decompress_kernel, dim3(grid), dim3(64), 0, stream, a, counters + 32, (const int32_t*)nullptr);
         return hipGetLastError();
     }
-    // carve the lists out of the scratch
-    snf::ChunkList L;
-    uint8_t* p = base + 4096;
-    const int64_t n = a.nBlocks;
-    auto take = [&](int64_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 15) & ~(int64_t)15;
-        return r;
-    };
-    L.counters = counters;
-    L.sErrOff = (int64_t*)take(8 * n);
-    L.sFirst = (int32_t*)take(4 * n);
-    L.sCount = (int32_t*)take(4 * n);
-    L.sStatus = (int32_t*)take(4 * n);
-    L.sOut = (int32_t*)take(4 * n);
-    L.sSerial = (int32_t*)take(4 * n);
-    const int64_t C = snf::MAX_CHUNKS;
-    L.cSrcOff = (int64_t*)take(8 * C);
-    L.cDstOff = (int64_t*)take(8 * C);
-    L.cErrOff = (int64_t*)take(8 * C);
-    L.cSrcLen = (int32_t*)take(4 * C);
-    L.cDstCap = (int32_t*)take(4 * C);
-    L.cOutLen = (int32_t*)take(4 * C);
-    L.cStatus = (int32_t*)take(4 * C);
-    L.cCrc = (uint32_t*)take(4 * C);
-    L.cRawLen = (int32_t*)take(4 * C);
-    L.cPos = (int32_t*)take(4 * C);
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
     hipLaunchKernelGGL(snf::snappyframed_walk_kernel, dim3(perStream), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(snf::snappyframed_seal_kernel, dim3(1), dim3(1), 0, stream, L);
-    // the chunks as a batch of Snappy blocks whose size is known on the device only: launches are sized for the arrays
-    BatchArgs c = a;  // (every field the chunk batch does not set keeps the caller's value: no filter, no device count yet)
-    c.srcBase = a.srcBase;
-    c.srcOff = L.cSrcOff;
-    c.srcLen = L.cSrcLen;
-    c.dstBase = a.dstBase;
-    c.dstOff = L.cDstOff;
-    c.dstCap = L.cDstCap;
-    c.outLen = L.cOutLen;
-    c.status = L.cStatus;
-    c.errOffset = L.cErrOff;
-    c.nBlocks = snf::MAX_CHUNKS;
-    c.ringPad = a.ringPad;
-    c.nBlocksDev = counters + 1;
-    c.only = nullptr;
-    c.onlyStats = nullptr;
-    int32_t* mixedGroups = counters + 16;
-    bool viaTwoPass = false;
-    int32_t nChunksHost = -1;  // the chunk count once the host has read it (variants 2 and 3)
-    if ((variant == 2 || variant == 3) && aux != nullptr && aux->get != nullptr) {
-        // variant 3 (the default since round 3): the element-length probe of the block API's auto mode runs on the chunk list before the
-        // one synchronisation and its verdict comes back with the chunk count: short elements (text) -> the two-pass decoder, long
-        // copies -> the rings (measured, 1024 streams x 4 MiB: rings 804 / 116 GiB/s fragments / corpus, two-pass 456 / 236)
-        int32_t head[20] = {0};
-        if (variant == 3) {
-            e = hipMemsetAsync(mixedGroups, 0, 4 * sizeof(int32_t), stream);
-            if (e == hipSuccess) e = launch_snappy_element_sample(c, stream, mixedGroups, 0, 0);
-            if (e != hipSuccess) return e;
-        }
-        e = hipMemcpyAsync(head, counters, sizeof(head), hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        const int32_t nChunks = head[1];
-        nChunksHost = nChunks;
-        const int32_t* v = head + 16;
-        const bool wantTwoPass = variant == 2 || (v[1] > 0 && (int64_t)v[2] < 6LL * (int64_t)v[1]);
-        viaTwoPass = nChunks == 0;
-        if (nChunks > 0 && wantTwoPass) {
-            const int64_t bytes = twopass_scratch_bytes(nChunks, 131072);  // (chunks hold at most 64 KiB: the block codec's arena per block)
-            void* arena = aux->get(aux->user, bytes);
-            if (arena != nullptr) {
-                BatchArgs t = c;
-                t.nBlocks = nChunks;
-                t.nBlocksDev = nullptr;
-                e = launch_snappy_decompress_twopass(t, stream, arena, bytes, 4, 0, nullptr, ks);
-                if (e != hipSuccess) return e;
-                viaTwoPass = true;
-            }
-        }
-    }
-    if (!viaTwoPass && nChunksHost > 0) {  // the host knows the count (variant 3 chose the rings): one launch of that size, no probes
-        BatchArgs t = c;
-        t.nBlocks = nChunksHost;
-        t.nBlocksDev = nullptr;
-        e = launch_snappy_decompress_rings(t, stream, snappy_ring_group_for(nChunksHost), 0, nullptr);
-        if (e != hipSuccess) return e;
-    }
-    else if (!viaTwoPass) {
-        e = launch_snappy_decompress_rings(c, stream, 4, 0, nullptr);  // (the chunk count is known on the device only: the launch is sized for the most there can be)
-        if (e != hipSuccess) return e;
-    }
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, counters, lists::CAPACITY);
+    const bool sync = (variant == 2 || variant == 3) && aux != nullptr && aux->get != nullptr;
+    const ListedWant want{sync, variant == 3, true, 1, -1};
+    bool decoded = false;
+    e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), 1, stream, counters, counters + 16, aux, ks, want, &decoded);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(snf::snappyframed_verify_kernel, dim3(maxWaves), dim3(64), 0, stream, a, L);
     hipLaunchKernelGGL(snf::snappyframed_fold_kernel, dim3(perStream), dim3(64), 0, stream, a, L);
     // streams that did not fit into the lists

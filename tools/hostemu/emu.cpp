@@ -13,7 +13,32 @@ extern "C" { long long achip_emu_counters[16]; }  // development counters of ker
 #include "../../aircompressor_amd/csrc/hadoop_streams.hip"
 #include "../../aircompressor_amd/csrc/lz4_frame.hip"
 #include "../../aircompressor_amd/csrc/snappy_frame.hip"
+#include "../../aircompressor_amd/csrc/block_decode.cpp"
+#include <cstdio>
+#include <cstdlib>
 #include <vector>
+// A scratch of exactly the size a *_scratch_bytes function names, filled with 0xCD, and a guard tail behind it: a kernel that writes beyond the
+// named size changes the tail, and check() ends the process (loud in every caller, whatever it does with a return value).
+struct GuardedScratch {
+    static constexpr size_t TAIL = 4096;
+    std::vector<uint8_t> v;
+    uint8_t* assign(int64_t bytes)
+    {
+        v.assign((size_t)bytes + TAIL, 0xCD);
+        return v.data();
+    }
+    int64_t size() const { return (int64_t)(v.size() - TAIL); }
+    int check(const char* what, int r) const
+    {
+        for (size_t i = v.size() - TAIL; i < v.size(); i++) {
+            if (v[i] != 0xCD) {
+                fprintf(stderr, "hostemu: %s wrote %zu bytes beyond its scratch of %lld bytes\n", what, i - (v.size() - TAIL), (long long)size());
+                abort();
+            }
+        }
+        return r;
+    }
+};
 // the probes of the decoders' auto mode are not built here: the probe statistics stay
 // zero, which picks the ring decoders
 hipError_t achip::launch_snappy_element_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
@@ -28,12 +53,12 @@ extern "C" int emu_batch(int op, const uint8_t* srcBase, const int64_t* srcOff, 
         achip::KernelSettings ks;
         ks.lz4Parse = op == 26 || op == 27 ? 2 : 1;
         ks.snappyParse = op == 36 || op == 37 ? 2 : 1;
-        static std::vector<uint8_t> scratch;
-        const int64_t bytes = tiny ? 4096 + ((n * 12 + 4095) & ~4095LL) + 4 * 4096 : achip::lz4_twopass_scratch_bytes(n);
-        scratch.assign((size_t)bytes, 0xCD);
+        static GuardedScratch scratch;
+        const int64_t bytes = tiny ? achip::sx::TwoPassLayout::fixed(n) + 4 * 4096 : achip::lz4_twopass_scratch_bytes(n);
+        scratch.assign(bytes);
         a.ringPad = 16;
-        return snappy ? achip::launch_snappy_decompress_twopass(a, nullptr, scratch.data(), bytes, 1, 0, nullptr, ks)
-                      : achip::launch_lz4_decompress_twopass(a, nullptr, scratch.data(), bytes, 1, 0, nullptr, ks);
+        return scratch.check("the two-pass decoder", snappy ? achip::launch_snappy_decompress_twopass(a, nullptr, scratch.v.data(), bytes, 1, 0, nullptr, ks)
+                                                            : achip::launch_lz4_decompress_twopass(a, nullptr, scratch.v.data(), bytes, 1, 0, nullptr, ks));
     }
     if (op == 16 || op == 17) {  // default ring decoders at GS = 1 (compact / large rings)
         a.ringPad = 16;
@@ -62,12 +87,13 @@ extern "C" int emu_hadoop(int op, int snappy, int bufferSize, int variant, const
                           const int64_t* dstOff, const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n)
 {
     achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, 16};
-    static std::vector<uint8_t> scratch;
-    const int64_t bytes = op == 0 ? achip::hadoop_decompress_scratch_bytes(n, bufferSize) : achip::hadoop_compress_scratch_bytes(n);
-    scratch.assign((size_t)bytes, 0xCD);
-    static std::vector<uint8_t> auxBuffer;
-    const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { auxBuffer.assign((size_t)bytes, 0xCD); return auxBuffer.data(); }, nullptr};
-    return op == 0 ? achip::launch_hadoop_decompress(a, nullptr, scratch.data(), snappy != 0, bufferSize, variant, &aux, achip::KernelSettings()) : achip::launch_hadoop_compress(a, nullptr, scratch.data(), snappy != 0, bufferSize);
+    static GuardedScratch scratch, auxBuffer;
+    scratch.assign(op == 0 ? achip::hadoop_decompress_scratch_bytes(n, bufferSize) : achip::hadoop_compress_scratch_bytes(n));
+    auxBuffer.assign(0);
+    const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { return auxBuffer.assign(bytes); }, nullptr};
+    const int r = op == 0 ? achip::launch_hadoop_decompress(a, nullptr, scratch.v.data(), snappy != 0, bufferSize, variant, &aux, achip::KernelSettings())
+                          : achip::launch_hadoop_compress(a, nullptr, scratch.v.data(), snappy != 0, bufferSize);
+    return auxBuffer.check("a Hadoop reader's record arena", scratch.check(op == 0 ? "the Hadoop reader" : "the Hadoop writer", r));
 }
 
 // the executor for records of any length (achip_seqexec2.h exec_records, used by the Zstd pipeline): one block, one wavefront
@@ -96,10 +122,12 @@ extern "C" int emu_lz4frame(int variant, const uint8_t* srcBase, const int64_t* 
                             int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n)
 {
     achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, 16};
-    static std::vector<uint8_t> scratch, auxBuffer;
-    scratch.assign((size_t)achip::lz4frame_decompress_scratch_bytes(n, variant), 0xCD);
-    const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { auxBuffer.assign((size_t)bytes, 0xCD); return auxBuffer.data(); }, nullptr};
-    return achip::launch_lz4frame_decompress(a, nullptr, scratch.data(), variant, &aux, achip::KernelSettings());
+    static GuardedScratch scratch, auxBuffer;
+    scratch.assign(achip::lz4frame_decompress_scratch_bytes(n, variant));
+    auxBuffer.assign(0);
+    const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { return auxBuffer.assign(bytes); }, nullptr};
+    const int r = achip::launch_lz4frame_decompress(a, nullptr, scratch.v.data(), variant, &aux, achip::KernelSettings());
+    return auxBuffer.check("the LZ4 frame reader's record arena", scratch.check("the LZ4 frame reader", r));
 }
 
 // x-snappy-framed streams (snappy_frame.hip), reader variant 2: walk, the chunks through the two-pass Snappy decoder, CRC verification, fold
@@ -107,8 +135,10 @@ extern "C" int emu_snappyframed(int variant, const uint8_t* srcBase, const int64
                                 int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n)
 {
     achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, 16};
-    static std::vector<uint8_t> scratch, auxBuffer;
-    scratch.assign((size_t)achip::snappyframed_decompress_scratch_bytes(n), 0xCD);
-    const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { auxBuffer.assign((size_t)bytes, 0xCD); return auxBuffer.data(); }, nullptr};
-    return achip::launch_snappyframed_decompress(a, nullptr, scratch.data(), variant, &aux, achip::KernelSettings());
+    static GuardedScratch scratch, auxBuffer;
+    scratch.assign(achip::snappyframed_decompress_scratch_bytes(n));
+    auxBuffer.assign(0);
+    const achip::AuxScratch aux{[](void*, int64_t bytes) -> void* { return auxBuffer.assign(bytes); }, nullptr};
+    const int r = achip::launch_snappyframed_decompress(a, nullptr, scratch.v.data(), variant, &aux, achip::KernelSettings());
+    return auxBuffer.check("the x-snappy-framed reader's record arena", scratch.check("the x-snappy-framed reader", r));
 }

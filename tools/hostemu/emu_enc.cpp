@@ -47,12 +47,14 @@ extern "C" int emu_encode(int op, const uint8_t* srcBase, const int64_t* srcOff,
         return achip::launch_lz4frame_compress(a, nullptr, scratch.data(), (int64_t)scratch.size());
     }
     if (op == 9) {
-        scratch.assign((size_t)achip::snappyframed_compress_scratch_bytes(n), 0xCD);
-        return achip::launch_snappyframed_compress(a, nullptr, scratch.data(), option);
+        static GuardedScratch guarded;
+        guarded.assign(achip::snappyframed_compress_scratch_bytes(n));
+        return guarded.check("the x-snappy-framed writer", achip::launch_snappyframed_compress(a, nullptr, guarded.v.data(), option));
     }
     if (op == 11 || op == 13) {
-        scratch.assign((size_t)achip::hadoop_compress_scratch_bytes(n), 0xCD);
-        return achip::launch_hadoop_compress(a, nullptr, scratch.data(), op == 13, bufferSize);
+        static GuardedScratch guarded;
+        guarded.assign(achip::hadoop_compress_scratch_bytes(n));
+        return guarded.check("a Hadoop writer", achip::launch_hadoop_compress(a, nullptr, guarded.v.data(), op == 13, bufferSize));
     }
     return -1;
 }

@@ -13,18 +13,9 @@ extern "C" { long long achip_emu_counters[16]; }
 #include "../../aircompressor_amd/csrc/hadoop_streams.hip"
 #include "../../aircompressor_amd/csrc/zstd_decompress.hip"
 #include <vector>
-// the list paths' launchers and the Zstd pipeline (not part of this library: the wavefront-per-item kernels only).  Qualified definitions: each must
+// the list paths' decode and the Zstd pipeline (not part of this library: the wavefront-per-item kernels only).  Qualified definitions: each must
 // match its declaration in achip_launch.h
-hipError_t achip::launch_lz4_decompress_twopass(const BatchArgs&, hipStream_t, void*, int64_t, int, int, const int32_t*, const KernelSettings&) { return hipSuccess; }
-hipError_t achip::launch_snappy_decompress_twopass(const BatchArgs&, hipStream_t, void*, int64_t, int, int, const int32_t*, const KernelSettings&) { return hipSuccess; }
-int64_t achip::twopass_scratch_bytes(int32_t, int64_t) { return 0; }
-hipError_t achip::launch_lz4_decompress_rings(const BatchArgs&, hipStream_t, int, int, const int32_t*) { return hipSuccess; }
-int achip::lz4_ring_group_for(int32_t) { return 4; }
-int achip::snappy_ring_group_for(int32_t) { return 4; }
-hipError_t achip::launch_lz4_sequence_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
-hipError_t achip::launch_snappy_decompress_rings(const BatchArgs&, hipStream_t, int, int, const int32_t*) { return hipSuccess; }
-hipError_t achip::launch_snappy_element_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }
-hipError_t achip::launch_lz4_mixed_groups(const BatchArgs&, hipStream_t, int32_t*, int32_t) { return hipSuccess; }
+hipError_t achip::launch_listed_decode(const BatchArgs&, int, hipStream_t, const int32_t*, int32_t*, const AuxScratch*, const KernelSettings&, const ListedWant&, bool*) { return hipSuccess; }
 int64_t achip::zstd_decompress_pipe_scratch_bytes(int32_t, int32_t) { return 0; }
 hipError_t achip::launch_zstd_decompress_pipe(const BatchArgs&, hipStream_t, void*, void*, int32_t, const ZstdMbProvider*, const KernelSettings&) { return hipSuccess; }
 void* achip::zstd_decompress_pipe_general_scratch(void* scratch, int32_t, int32_t) { return scratch; }
