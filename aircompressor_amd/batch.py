@@ -126,6 +126,46 @@ class HipBatchCodec:
     def synchronize(self):
         self.native.synchronize()
 
+    def decoded_sizes(self, op, src, src_off, src_len, out_size, status, err_off, n_blocks):
+        """achip_decoded_size_batch: out_size[i] (int64) = what item i decodes to under decode op `op`, found on the device without decoding; status[i] /
+        err_off[i] report a structural fault (out_size[i] is then 0).  Asynchronous on the context stream; all arguments device-accessible."""
+        r = self.lib.achip_decoded_size_batch(self.native.ctx, int(op), _ptr(src), _ptr(src_off), _ptr(src_len), _ptr(out_size), _ptr(status), _ptr(err_off), int(n_blocks))
+        if r < 0:
+            native.raise_for_status(r)
+
+    def plan_outputs(self, out_size, status, n_blocks, align, dst_off, dst_cap, total):
+        """achip_plan_outputs: dst_cap[i] = out_size[i], dst_off[i] = the running sum of the capacities, each rounded up to `align`; items with a status or
+        beyond INT32_MAX take no room.  total (two int64): bytes of output, items left out.  Asynchronous on the context stream."""
+        r = self.lib.achip_plan_outputs(self.native.ctx, _ptr(out_size), _ptr(status), int(n_blocks), int(align), _ptr(dst_off), _ptr(dst_cap), _ptr(total))
+        if r < 0:
+            native.raise_for_status(r)
+
+    def decompress_unsized(self, op, src, src_off, src_len, n_blocks, alloc, align=16):
+        """Decodes a device-resident batch whose decoded sizes nobody knows: size, plan, ONE 16-byte readback (the total -- the only point where this call waits
+        for the device), `alloc(total)`, decode.  `alloc(nbytes)` is the caller's device allocator (it returns something with data_ptr(), or an address): it gives
+        the output buffer and the per-item arrays, all of which come back in the result:
+          dst, total_bytes, left_out                     the output, its planned size, the items sizing left out of it
+          dst_off, dst_cap, out_len, status, err_off     the decode's arrays (int64 / int32 / int32 / int32 / int64), the decode still in flight on the stream
+          out_size, size_status, size_err_off            what sizing said (int64 / int32 / int64): an item with size_status != 0 was given no room
+        """
+        n = int(n_blocks)
+        wide, narrow = max(8 * n, 16), max(4 * n, 16)
+        r = {"out_size": alloc(wide), "size_status": alloc(narrow), "size_err_off": alloc(wide), "dst_off": alloc(wide), "dst_cap": alloc(narrow),
+             "out_len": alloc(narrow), "status": alloc(narrow), "err_off": alloc(wide)}
+        total = alloc(16)
+        self.decoded_sizes(op, src, src_off, src_len, r["out_size"], r["size_status"], r["size_err_off"], n)
+        self.plan_outputs(r["out_size"], r["size_status"], n, align, r["dst_off"], r["dst_cap"], total)
+        host = np.zeros(2, dtype=np.int64)
+        if n > 0:
+            e = self.lib.achip_memcpy_d2h(self.native.ctx, host.ctypes.data, _ptr(total), 16)
+            if e < 0:
+                native.raise_for_status(e)
+            self.synchronize()
+        r["total_bytes"], r["left_out"] = int(host[0]), int(host[1])
+        r["dst"] = alloc(max(r["total_bytes"], 16))
+        self.launch(op, src, src_off, src_len, r["dst"], r["dst_off"], r["dst_cap"], r["out_len"], r["status"], r["err_off"], n)
+        return r
+
     def run_host_mixed(self, ops, src, src_off, src_len, dst, dst_off, dst_cap):
         """Host numpy arrays in/out through achip_mixed_batch_host: one op per item."""
         n = len(src_off)

@@ -1209,6 +1209,60 @@ int32_t achip_mixed_batch(achip_ctx* ctx, const int32_t* codecOp, const void* sr
     return 0;
 }
 
+// ---- decoded sizes and the output planner (decoded_size.hip) ----
+namespace {
+// the context's scratch for a sizing or planning call; the statistics the last decode left at its head are gone with it (achip_ctx_get_stat: -1)
+int32_t sizing_scratch(achip_ctx* ctx, int64_t bytes)
+{
+    if (bytes <= 0) return 0;
+    ctx->lastTwopass = false;
+    ctx->lastLz4dAuto = false;
+    ctx->lastRemembered = -1;
+    ctx->lastZstddBlocks = 0;
+    return ensure_scratch(ctx, bytes);
+}
+}  // namespace
+
+// (the value arguments are checked before the context is looked at: a caller's mistake is reported the same with and without a device)
+int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t* outSize, int32_t* status,
+                                 int64_t* errOffset, int32_t nBlocks)
+{
+    switch (codecOp) {
+        case ACHIP_OP_LZ4_DECOMPRESS:
+        case ACHIP_OP_SNAPPY_DECOMPRESS:
+        case ACHIP_OP_ZSTD_DECOMPRESS:
+        case ACHIP_OP_LZ4FRAME_DECOMPRESS:
+        case ACHIP_OP_SNAPPYFRAMED_DECOMPRESS:
+        case ACHIP_OP_LZ4HADOOP_DECOMPRESS:
+        case ACHIP_OP_SNAPPYHADOOP_DECOMPRESS: break;
+        default: return bad_argument("codecOp is not a decode op");
+    }
+    if (nBlocks < 0) return bad_argument("nBlocks < 0");
+    if (nBlocks == 0) return 0;
+    if (!ctx) return bad_argument("ctx is null");
+    if (!srcOff || !srcLen || !outSize || !status || !errOffset) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int32_t r = sizing_scratch(ctx, achip::decoded_size_scratch_bytes(codecOp, nBlocks));
+    if (r < 0) return r;
+    achip::SizeArgs s{(const uint8_t*)srcBase, srcOff, srcLen, outSize, status, errOffset, nBlocks};
+    HIP_TRY(achip::launch_decoded_size(codecOp, s, ctx->stream, ctx->scratch));
+    return 0;
+}
+
+int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t* status, int32_t nBlocks, int32_t align, int64_t* dstOff, int32_t* dstCap, int64_t* total)
+{
+    if (align < 1 || align > 4096 || (align & (align - 1)) != 0) return bad_argument("align must be a power of two in 1..4096");
+    if (nBlocks < 0) return bad_argument("nBlocks < 0");
+    if (nBlocks == 0) return 0;
+    if (!ctx) return bad_argument("ctx is null");
+    if (!outSize || !status || !dstOff || !dstCap || !total) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int32_t r = sizing_scratch(ctx, achip::plan_outputs_scratch_bytes(nBlocks));
+    if (r < 0) return r;
+    HIP_TRY(achip::launch_plan_outputs(outSize, status, nBlocks, align, dstOff, dstCap, total, ctx->scratch, ctx->stream));
+    return 0;
+}
+
 // ---- xxhash -------------------------------------------
 int32_t achip_xxhash64_batch(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t seed, int64_t* outHash, int32_t nBuffers)
 {

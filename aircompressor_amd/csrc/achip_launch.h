@@ -102,6 +102,26 @@ int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize);
 hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize);
 int64_t hadoop_compress_scratch_bytes(int32_t nStreams);
 
+// ---- decoded sizes and the output planner (decoded_size.hip) ----
+// A batch to be sized: item i reads srcBase[srcOff[i] .. + srcLen[i]) and reports outSize[i], status[i], errOffset[i]
+struct SizeArgs {
+    const uint8_t* __restrict__ srcBase;
+    const int64_t* __restrict__ srcOff;
+    const int32_t* __restrict__ srcLen;
+    int64_t* __restrict__ outSize;
+    int32_t* __restrict__ status;
+    int64_t* __restrict__ errOffset;
+    int32_t nBlocks;
+    const int32_t* nBlocksDev = nullptr;  // when set: the number of items is this device word (<= nBlocks): the LZ4 blocks a container's streams listed
+};
+// `op`: one of the seven ACHIP_OP_*_DECOMPRESS (anything else is an error); scratch: decoded_size_scratch_bytes(op, nBlocks) bytes
+hipError_t launch_decoded_size(int32_t op, const SizeArgs& s, hipStream_t stream, void* scratch);
+int64_t decoded_size_scratch_bytes(int32_t op, int32_t nBlocks);
+// align: a power of two; total[0] = bytes of output, total[1] = items left out
+hipError_t launch_plan_outputs(const int64_t* outSize, const int32_t* status, int32_t nBlocks, int32_t align, int64_t* dstOff, int32_t* dstCap, int64_t* total, void* scratch,
+                               hipStream_t stream);
+int64_t plan_outputs_scratch_bytes(int32_t nBlocks);
+
 // ---- mixed batches, host-pointer staging, hashes (batch_mix.hip, xxhash.hip, xxhash3.hip) ----
 hipError_t launch_mix_gather(const int32_t* perm, int32_t n, const BatchArgs& a, int64_t* gSrcOff, int32_t* gSrcLen, int64_t* gDstOff, int32_t* gDstCap, hipStream_t stream);
 hipError_t launch_mix_scatter(const int32_t* perm, int32_t n, const int32_t* gOutLen, const int32_t* gStatus, const int64_t* gErr, const BatchArgs& a, hipStream_t stream);

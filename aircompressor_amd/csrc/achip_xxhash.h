@@ -5,6 +5,27 @@
 
 namespace achip {
 
+// XXH32 (seed 0) of fewer than 16 bytes by ONE lane: the LZ4 frame descriptor (XxHash32JavaHasher.java:92-110; lz4_frame.hip, decoded_size.hip)
+__device__ __forceinline__ uint32_t xxh32_short(const uint8_t* p, int32_t len)
+{
+    constexpr uint32_t P1 = 0x9E3779B1u, P2 = 0x85EBCA77u, P3 = 0xC2B2AE3Du, P4 = 0x27D4EB2Fu, P5 = 0x165667B1u;
+    auto rotl = [](uint32_t x, int r) { return (x << r) | (x >> (32 - r)); };
+    uint32_t h = P5 + (uint32_t)len;
+    int32_t i = 0;
+    for (; i + 4 <= len; i += 4) {
+        h = rotl(h + ld4(p + i) * P3, 17) * P4;
+    }
+    for (; i < len; i++) {
+        h = rotl(h + (uint32_t)p[i] * P5, 11) * P1;
+    }
+    h ^= h >> 15;
+    h *= P2;
+    h ^= h >> 13;
+    h *= P3;
+    h ^= h >> 16;
+    return h;
+}
+
 // XXH64 of [p, p + len): the calling lane is accumulator s (0..3) of its buffer; `base` is the first lane of the buffer's
 // quad.  All four lanes return the hash.  (The same routine checks Zstd frame checksums in zstd_decompress_pipe.hip.)
 __device__ __forceinline__ uint64_t quad_xxh64(const uint8_t* __restrict__ p, int32_t len, uint64_t seed, int s, int base)

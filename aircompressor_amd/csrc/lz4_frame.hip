@@ -23,27 +23,6 @@ constexpr uint32_t UNCOMPRESSED_FLAG = 0x80000000u;
 constexpr int IN_RING = 2048, OUT_RING = 4096;
 using FR = Rings<64, IN_RING, OUT_RING, 1>;
 
-// XXH32 (seed 0) of fewer than 16 bytes: the frame descriptor (XxHash32JavaHasher.java:92-110)
-__device__ __forceinline__ uint32_t xxh32_short(const uint8_t* p, int32_t len)
-{
-    constexpr uint32_t P1 = 0x9E3779B1u, P2 = 0x85EBCA77u, P3 = 0xC2B2AE3Du, P4 = 0x27D4EB2Fu, P5 = 0x165667B1u;
-    auto rotl = [](uint32_t x, int r) { return (x << r) | (x >> (32 - r)); };
-    uint32_t h = P5 + (uint32_t)len;
-    int32_t i = 0;
-    for (; i + 4 <= len; i += 4) {
-        h = rotl(h + ld4(p + i) * P3, 17) * P4;
-    }
-    for (; i < len; i++) {
-        h = rotl(h + (uint32_t)p[i] * P5, 11) * P1;
-    }
-    h ^= h >> 15;
-    h *= P2;
-    h ^= h >> 13;
-    h *= P3;
-    h ^= h >> 16;
-    return h;
-}
-
 #define LZ4F_FAIL(detail, off)                            \
     {                                                     \
         eo = (int64_t)(off);                              \

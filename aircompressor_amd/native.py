@@ -100,6 +100,8 @@ SIGNATURES = {
     "achip_zstdstream_compress_feed": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "achip_zstdstream_compress_finish": (_i32, [_vp, _vp, _vp, _i64, ctypes.POINTER(_i64)]),
     "achip_zstdstream_compress_end": (_i32, [_vp, _vp]),
+    "achip_decoded_size_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "achip_plan_outputs": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "achip_multi_batch_host": (_i32, [_vp, _i32, _i32, _vp] + _BATCH[1:] + [_vp]),
     "achip_partition_blocks": (_i32, [_vp, _i32, _i32, _vp]),
 }

@@ -384,6 +384,31 @@ int32_t achip_mixed_batch(achip_ctx* ctx, const int32_t* codecOp, const void* sr
 int32_t achip_mixed_batch_host(achip_ctx* ctx, const int32_t* codecOp, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, void* dstBase,
                                const int64_t* dstOff, const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t nBlocks);
 
+/* ---- Sizing a batch on the device: for a caller that holds compressed items in device memory and knows nothing else ----
+ * achip_decoded_size_batch: outSize[i] = the bytes item i decodes to under `codecOp`, one of the seven decode ops (LZ4, SNAPPY, ZSTD, LZ4FRAME, SNAPPYFRAMED,
+ *   LZ4HADOOP, SNAPPYHADOOP _DECOMPRESS; any other op is INVALID_ARGUMENT), found without decoding: what a Java caller asks
+ *     SnappyJavaDecompressor.getUncompressedLength   M/snappy/SnappyJavaDecompressor.java (-> SnappyRawDecompressor.java:30-33,277-321)      Snappy: the preamble
+ *     ZstdJavaDecompressor.getDecompressedSize       M/zstd/ZstdJavaDecompressor.java   (-> ZstdFrameDecompressor.java:942-947)              Zstd: here the walk of
+ *         the frames' blocks (block headers, literals headers, the match lengths of the sequence sections): frames without a content size are sized too, and the
+ *         header's field, which the decoder never checks, is not trusted
+ *   for, one buffer at a time on the host; for LZ4 raw blocks there is no counterpart: the Java caller must know (here: the token walk of
+ *   M/lz4/Lz4RawDecompressor.java:59-195).  Containers: the reader's loop over the stream's headers, the LZ4 walk / the Snappy preamble per chunk where the
+ *   loop needs it (an LZ4 frame that announces its content size is that size).
+ *   R1  if the op's decoder, given dstCap = the item's true plaintext length, succeeds, then status[i] == 0 and outSize[i] is that length;
+ *   R2  if status[i] == 0, the decoder run with dstCap = outSize[i] returns exactly outSize[i] or fails -- it never succeeds with another length.
+ *   status[i] != 0 (errOffset[i] set, outSize[i] = 0): the walk met a structural fault, reported as the op's reader reports it.  Faults only the payload decode
+ *   sees (checksums, Huffman literals, a block the walk does not enter) leave status 0.  (An LZ4 block that ends in a match decodes with room to spare and
+ *   fails with exact room, Lz4RawDecompressor.java:168-171: it is sized with status 0.)
+ * achip_plan_outputs: the decoders' dstOff[] / dstCap[] from the sizes: dstCap[i] = outSize[i], dstOff[i] = the running sum of the capacities in front of i, each
+ *   rounded up to `align` (a power of two in 1 .. 4096; else INVALID_ARGUMENT).  An item with status[i] != 0 or outSize[i] > INT32_MAX is left out: dstCap[i] = 0,
+ *   it takes no room, dstOff[i] is the running offset.  total[0] = the bytes the output buffer must have, total[1] = the items left out.
+ * All arrays device-accessible; both calls asynchronous on the ctx stream (scratch from the context); nBlocks == 0 launches nothing; the return value reports
+ * launch and argument failures only.  size -> plan -> a 16-byte readback of total -> allocate -> decode: one synchronisation, no host walk. */
+int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen,
+                                 int64_t* outSize, int32_t* status, int64_t* errOffset, int32_t nBlocks);
+int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t* status, int32_t nBlocks, int32_t align,
+                           int64_t* dstOff, int32_t* dstCap, int64_t* total /* [2] */);
+
 /* One process, several devices: the batch is cut into nCtx contiguous slices balanced by srcLen[i] + dstCap[i] (the rule of
  * achip_partition_blocks) and slice d runs through achip_batch_host (codecOps == NULL: every item is `codecOp`) or
  * achip_mixed_batch_host (codecOps[i] per item) on ctxs[d], each slice in a host thread of its own, all inside this call -- what

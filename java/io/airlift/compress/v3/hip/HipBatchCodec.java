@@ -136,6 +136,66 @@ public final class HipBatchCodec
         return new Result(outputLength, status, errorOffset);
     }
 
+    /**
+     * A batch decoded without anybody knowing its sizes: the output, the planned places and the decode's per-item arrays, all in device memory of
+     * {@code context} (the decode may still be in flight on its stream); {@code sizeStatus[i] != 0}: sizing found item i damaged and gave it no room.
+     */
+    public record Unsized(HipNative.Context context, MemorySegment destination, long totalBytes, long leftOut, MemorySegment destinationOffset,
+            MemorySegment destinationCapacity, MemorySegment outputLength, MemorySegment status, MemorySegment errorOffset, MemorySegment decodedSize,
+            MemorySegment sizeStatus, MemorySegment sizeErrorOffset) {}
+
+    /** achip_decoded_size_batch on the first device: thin and asynchronous like {@link HipNative.Context#launchBatch}; all segments device-accessible. */
+    public void decodedSizes(int op, MemorySegment source, MemorySegment sourceOffset, MemorySegment sourceLength, MemorySegment decodedSize, MemorySegment status,
+            MemorySegment errorOffset, int blocks)
+    {
+        contexts[0].decodedSizes(op, source, sourceOffset, sourceLength, decodedSize, status, errorOffset, blocks);
+    }
+
+    /** achip_plan_outputs on the first device: the decoders' offsets and capacities from the sizes; {@code total} receives two longs. */
+    public void planOutputs(MemorySegment decodedSize, MemorySegment status, int blocks, int align, MemorySegment destinationOffset, MemorySegment destinationCapacity,
+            MemorySegment total)
+    {
+        contexts[0].planOutputs(decodedSize, status, blocks, align, destinationOffset, destinationCapacity, total);
+    }
+
+    /**
+     * Size, plan, ONE 16-byte readback of the total (the only call here that waits for the device), allocate, decode: for a caller that holds compressed
+     * items in device memory and knows nothing else.  The caller frees the segments of the result with {@link HipNative.Context#freeDevice}.
+     */
+    public Unsized decompressUnsized(int op, MemorySegment source, MemorySegment sourceOffset, MemorySegment sourceLength, int blocks, int align)
+    {
+        HipNative.Context context = contexts[0];
+        long wide = Math.max(8L * blocks, 16);
+        long narrow = Math.max(4L * blocks, 16);
+        MemorySegment decodedSize = context.allocateDevice(wide);
+        MemorySegment sizeStatus = context.allocateDevice(narrow);
+        MemorySegment sizeErrorOffset = context.allocateDevice(wide);
+        MemorySegment destinationOffset = context.allocateDevice(wide);
+        MemorySegment destinationCapacity = context.allocateDevice(narrow);
+        MemorySegment outputLength = context.allocateDevice(narrow);
+        MemorySegment status = context.allocateDevice(narrow);
+        MemorySegment errorOffset = context.allocateDevice(wide);
+        MemorySegment total = context.allocateDevice(16);
+        long totalBytes = 0;
+        long leftOut = 0;
+        context.decodedSizes(op, source, sourceOffset, sourceLength, decodedSize, sizeStatus, sizeErrorOffset, blocks);
+        context.planOutputs(decodedSize, sizeStatus, blocks, align, destinationOffset, destinationCapacity, total);
+        if (blocks > 0) {
+            try (Arena arena = Arena.ofConfined()) {
+                MemorySegment host = arena.allocate(JAVA_LONG, 2);
+                context.copyToHost(host, total, 16);
+                context.synchronize();
+                totalBytes = host.getAtIndex(JAVA_LONG, 0);
+                leftOut = host.getAtIndex(JAVA_LONG, 1);
+            }
+        }
+        context.freeDevice(total);
+        MemorySegment destination = context.allocateDevice(Math.max(totalBytes, 16));
+        context.launchBatch(op, source, sourceOffset, sourceLength, destination, destinationOffset, destinationCapacity, outputLength, status, errorOffset, blocks);
+        return new Unsized(context, destination, totalBytes, leftOut, destinationOffset, destinationCapacity, outputLength, status, errorOffset, decodedSize,
+                sizeStatus, sizeErrorOffset);
+    }
+
     /** Contiguous split balanced by bytes moved (source + destination): achip_partition_blocks itself, so that the split is the library's by construction. */
     static int[] partition(int[] sourceLength, int[] destinationCapacity, int parts)
     {

@@ -270,7 +270,13 @@ public final class HipNative
             @NativeSignature(name = "achip_event_elapsed_ms", returnType = float.class, argumentTypes = {MemorySegment.class, MemorySegment.class})
             MethodHandle eventElapsedMs,
             @NativeSignature(name = "achip_partition_blocks", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, MemorySegment.class})
-            MethodHandle partitionBlocks) {}
+            MethodHandle partitionBlocks,
+            // sizing a device-resident batch: (ctx, codecOp, srcBase, srcOff*, srcLen*, outSize*, status*, errOffset*, nBlocks) and the planner
+            // (ctx, outSize*, status*, nBlocks, align, dstOff*, dstCap*, total*)
+            @NativeSignature(name = "achip_decoded_size_batch", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
+            MethodHandle decodedSizeBatch,
+            @NativeSignature(name = "achip_plan_outputs", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle planOutputs) {}
 
     private static final Optional<LinkageError> LINKAGE_ERROR;
     private static final MethodHandles HANDLES;
@@ -970,6 +976,48 @@ public final class HipNative
             if (result < 0) {
                 throw toException(result, 0);
             }
+        }
+
+        /**
+         * achip_decoded_size_batch: what every item of a device-resident batch decodes to under decode op {@code op}, found on the device without decoding --
+         * {@code outSize[i]} (long), {@code status[i]} / {@code errOffset[i]} for a structural fault.  What {@code SnappyJavaDecompressor.getUncompressedLength} and
+         * {@code ZstdJavaDecompressor.getDecompressedSize} answer for one host buffer; for LZ4 raw blocks there is no Java counterpart.  Asynchronous on this
+         * context's stream; all segments device-accessible.
+         */
+        public void decodedSizes(int op, MemorySegment srcBase, MemorySegment srcOff, MemorySegment srcLen, MemorySegment outSize, MemorySegment status,
+                MemorySegment errOffset, int blocks)
+        {
+            int result;
+            try {
+                result = (int) HANDLES.decodedSizeBatch().invokeExact(handle(), op, srcBase, srcOff, srcLen, outSize, status, errOffset, blocks);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /**
+         * achip_plan_outputs: {@code dstCap[i] = outSize[i]}, {@code dstOff[i]} = the running sum of the capacities, each rounded up to {@code align} (a power of
+         * two in 1 .. 4096); an item with a status or beyond Integer.MAX_VALUE takes no room.  {@code total}: two longs, the bytes of output and the items left
+         * out.  Asynchronous on this context's stream.
+         */
+        public void planOutputs(MemorySegment outSize, MemorySegment status, int blocks, int align, MemorySegment dstOff, MemorySegment dstCap, MemorySegment total)
+        {
+            int result;
+            try {
+                result = (int) HANDLES.planOutputs().invokeExact(handle(), outSize, status, blocks, align, dstOff, dstCap, total);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
         }
 
         /**
