@@ -166,6 +166,64 @@ class HipBatchCodec:
         self.launch(op, src, src_off, src_len, r["dst"], r["dst_off"], r["dst_cap"], r["out_len"], r["status"], r["err_off"], n)
         return r
 
+    def compress_bounds(self, op, src_len, out_size, status, n_blocks):
+        """achip_compress_bound_batch: out_size[i] (int64) = what compress op `op` asks of dst_cap for src_len[i] bytes (the op's max_compressed_length, the Hadoop
+        ops with the context's hadoop.buffer_size); a negative length or a bound beyond INT32_MAX gives status[i] of class INVALID_ARGUMENT and out_size[i] = 0.
+        The pair feeds `plan_outputs` unchanged.  Asynchronous on the context stream; all arguments device-accessible."""
+        r = self.lib.achip_compress_bound_batch(self.native.ctx, int(op), _ptr(src_len), _ptr(out_size), _ptr(status), int(n_blocks))
+        if r < 0:
+            native.raise_for_status(r)
+
+    def pack_outputs(self, src, src_off, out_len, status, n_blocks, align, packed, packed_cap, packed_off, packed_len, total, raw=None, raw_off=None, raw_len=None,
+                     stored=None):
+        """achip_pack_outputs: a compress call's dst / dst_off / out_len / status as one dense stream.  packed_len[i] = the bytes taken (0 for an item with a
+        status or a negative length), packed_off[i] = the sum of the lengths in front, each rounded up to `align`; with raw / raw_off / raw_len / stored (all
+        four or none) an item whose compressed form is no smaller is taken from `raw` and stored[i] = 1.  total (three int64): bytes of the stream, items left
+        out, 1 if the bytes were copied -- which happens iff `packed` is not None and total[0] <= packed_cap, decided on the device.  Asynchronous on the
+        context stream."""
+        r = self.lib.achip_pack_outputs(self.native.ctx, _ptr(src), _ptr(src_off), _ptr(out_len), _ptr(status), _ptr(raw), _ptr(raw_off), _ptr(raw_len), int(n_blocks),
+                                        int(align), _ptr(packed), int(packed_cap), _ptr(packed_off), _ptr(packed_len), _ptr(stored), _ptr(total))
+        if r < 0:
+            native.raise_for_status(r)
+
+    def _read_totals(self, total, words):
+        host = np.zeros(words, dtype=np.int64)
+        e = self.lib.achip_memcpy_d2h(self.native.ctx, host.ctypes.data, _ptr(total), 8 * words)
+        if e < 0:
+            native.raise_for_status(e)
+        self.synchronize()
+        return host
+
+    def compress_packed(self, op, src, src_off, src_len, n_blocks, alloc, align=1, raw_fallback=False):
+        """Compresses a device-resident batch into ONE dense buffer, the twin of `decompress_unsized`: bounds, plan, a readback of the slots' total, `alloc` the
+        slot buffer, compress, pack (plan only), a readback of the dense total, `alloc` exactly that, pack.  It waits for the device at the two readbacks and
+        walks nothing on the host.  `alloc(nbytes)` is the caller's device allocator (it returns something with data_ptr(), or an address).  What it returns must be
+        ready for the context's stream: an allocator that fills its memory on another stream finishes the fill first.
+        raw_fallback: an item whose compressed form is no smaller than its plaintext is taken from src / src_off / src_len instead (stored[i] = 1).  The result:
+          packed, total_bytes, left_out                  the dense buffer (total_bytes bytes; the pack still in flight on the stream), the items without a place in it
+          packed_off, packed_len, stored                 where item i lies and how many bytes (int64 / int32); int32 flags, None without raw_fallback
+          slots, slot_bytes, dst_off, dst_cap            the compress call's worst-case buffer and its plan (the caller may free `slots` once the stream is idle)
+          out_len, status, err_off                       the compress call's arrays (int32 / int32 / int64)
+          bound, bound_status                            what the bounds said (int64 / int32): an item with bound_status != 0 was given no slot
+        """
+        n = int(n_blocks)
+        wide, narrow = max(8 * n, 16), max(4 * n, 16)
+        r = {"bound": alloc(wide), "bound_status": alloc(narrow), "dst_off": alloc(wide), "dst_cap": alloc(narrow), "out_len": alloc(narrow), "status": alloc(narrow),
+             "err_off": alloc(wide), "packed_off": alloc(wide), "packed_len": alloc(narrow), "stored": alloc(narrow) if raw_fallback else None}
+        total = alloc(24)
+        raw = {"raw": src, "raw_off": src_off, "raw_len": src_len, "stored": r["stored"]} if raw_fallback else {}
+        self.compress_bounds(op, src_len, r["bound"], r["bound_status"], n)
+        self.plan_outputs(r["bound"], r["bound_status"], n, 1, r["dst_off"], r["dst_cap"], total)
+        r["slot_bytes"] = int(self._read_totals(total, 2)[0]) if n > 0 else 0
+        r["slots"] = alloc(max(r["slot_bytes"], 16))
+        self.launch(op, src, src_off, src_len, r["slots"], r["dst_off"], r["dst_cap"], r["out_len"], r["status"], r["err_off"], n)
+        self.pack_outputs(r["slots"], r["dst_off"], r["out_len"], r["status"], n, align, None, 0, r["packed_off"], r["packed_len"], total, **raw)
+        host = self._read_totals(total, 3) if n > 0 else np.zeros(3, dtype=np.int64)
+        r["total_bytes"], r["left_out"] = int(host[0]), int(host[1])
+        r["packed"] = alloc(max(r["total_bytes"], 16))
+        self.pack_outputs(r["slots"], r["dst_off"], r["out_len"], r["status"], n, align, r["packed"], r["total_bytes"], r["packed_off"], r["packed_len"], total, **raw)
+        return r
+
     def run_host_mixed(self, ops, src, src_off, src_len, dst, dst_off, dst_cap):
         """Host numpy arrays in/out through achip_mixed_batch_host: one op per item."""
         n = len(src_off)

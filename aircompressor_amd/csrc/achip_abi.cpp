@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "achip_bounds.h"
 #include "achip_launch.h"
 
 // A context: its settings (achip_settings.h: what achip_ctx_set_option writes) and the state it owns.
@@ -648,15 +649,14 @@ int32_t achip_device_count(void)
 
 const char* achip_last_error(void) { return g_lastError.c_str(); }
 
-// ---- size helpers -------------------------------------------------------
-int32_t achip_lz4_max_compressed_length(int32_t n) { return n + n / 255 + 16; }
-int32_t achip_snappy_max_compressed_length(int32_t n) { return 32 + n + n / 6; }
+// ---- size helpers (the formulas: achip_bounds.h, which the bound kernel of achip_compress_bound_batch calls too) ----
+int32_t achip_lz4_max_compressed_length(int32_t n) { return (int32_t)achip::bound::lz4(n); }
+int32_t achip_snappy_max_compressed_length(int32_t n) { return (int32_t)achip::bound::snappy(n); }
 int32_t achip_lz4frame_max_compressed_length(int32_t n)
 {
     // Lz4FrameCompression.maxCompressedLength  M/lz4/Lz4FrameCompression.java:70-83
     if (n < 0) return bad_argument("uncompressedSize is negative");
-    const int64_t blocks = ((int64_t)n + (4 << 20) - 1) / (4 << 20);
-    const int64_t maxLength = 7 + 4 + (int64_t)n + 4 * blocks;
+    const int64_t maxLength = achip::bound::lz4frame(n);
     if (maxLength > 0x7FFFFFFF) return bad_argument("Maximum compressed length exceeds Integer.MAX_VALUE");
     return (int32_t)maxLength;
 }
@@ -665,8 +665,7 @@ int32_t achip_snappyframed_max_compressed_length(int32_t n)
     // stream header + per 64 KiB block a chunk header, the masked CRC and at most the block itself (a compressed chunk is kept
     // only at <= 0.85 of its block: M/snappy/SnappyFramedOutputStream.java:214)
     if (n < 0) return bad_argument("uncompressedSize is negative");
-    const int64_t blocks = ((int64_t)n + 65535) / 65536;
-    const int64_t maxLength = 10 + 8 * blocks + (int64_t)n;
+    const int64_t maxLength = achip::bound::snappyframed(n);
     if (maxLength > 0x7FFFFFFF) return bad_argument("Maximum compressed length exceeds Integer.MAX_VALUE");
     return (int32_t)maxLength;
 }
@@ -676,30 +675,21 @@ int32_t achip_hadoop_max_compressed_length(int32_t codec, int32_t n, int32_t buf
     // (M/lz4/Lz4HadoopOutputStream.java:44-46, 107-118, 128-131; M/snappy/SnappyHadoopOutputStream.java likewise)
     if (n < 0) return bad_argument("uncompressedSize is negative");
     if (codec != 0 && codec != 1) return bad_argument("codec must be 0 (LZ4) or 1 (Snappy)");
-    const bool snappy = codec == 1;
-    const int64_t overhead = snappy ? bufferSize / 6 + 32 : ((int32_t)(bufferSize * 0.01) > 10 ? (int32_t)(bufferSize * 0.01) : 10);
-    const int64_t chunk = (int64_t)bufferSize - overhead;
-    if (bufferSize <= 0 || chunk <= 0) return bad_argument("bufferSize too small");
-    auto bound = [&](int64_t m) { return snappy ? 32 + m + m / 6 : m + m / 255 + 16; };
-    const int64_t rest = (int64_t)n % chunk;
-    const int64_t maxLength = ((int64_t)n / chunk) * (8 + bound(chunk)) + (rest > 0 ? 8 + bound(rest) : 0);
+    const int64_t maxLength = achip::bound::hadoop(codec == 1, n, bufferSize);
+    if (maxLength < 0) return bad_argument("bufferSize too small");
     if (maxLength > 0x7FFFFFFF) return bad_argument("Maximum compressed length exceeds Integer.MAX_VALUE");
     return (int32_t)maxLength;
 }
 int32_t achip_zstdstream_max_compressed_length(int32_t n)
 {
     if (n < 0) return bad_argument("uncompressedSize is negative");
-    const int64_t r = (int64_t)achip_zstd_max_compressed_length(n) + 16;
+    const int64_t r = (int64_t)achip_zstd_max_compressed_length(n) + 16;  // (bound::zstdstream with the Zstd bound as the int the host function returns)
     if (r > 0x7FFFFFFF) return bad_argument("Maximum compressed length exceeds Integer.MAX_VALUE");
     return (int32_t)r;
 }
 int32_t achip_zstd_max_compressed_length(int32_t n)
 {
-    int32_t result = n + (int32_t)((uint32_t)n >> 8);
-    if (n < 128 * 1024) {
-        result += (int32_t)((uint32_t)(128 * 1024 - n) >> 11);
-    }
-    return result;
+    return (int32_t)achip::bound::zstd(n);
 }
 
 int64_t achip_snappy_uncompressed_length(const void* src, int64_t srcLen, int64_t* errOffset)
@@ -912,6 +902,7 @@ int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name)
         if (hipMemcpy(&v, ctx->scratch, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
         return v;
     }
+    if (k == "pack.tile_bytes") return achip::PACK_TILE_BYTES;  // the unit of achip_pack_outputs' copy (a constant of the build)
     if (k == "host.gather_us") return ctx->hostGatherUs;          // the gather thread copying the caller's inputs into pinned slots
     if (k == "host.scatter_us") return ctx->hostScatterUs;        // the finalizer thread copying outputs to the caller's buffers
     if (k == "host.wait_slot_us") return ctx->hostWaitSlotUs;     // the gather thread waiting for a free slot (the pipeline behind it is the limit)
@@ -1260,6 +1251,51 @@ int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t
     const int32_t r = sizing_scratch(ctx, achip::plan_outputs_scratch_bytes(nBlocks));
     if (r < 0) return r;
     HIP_TRY(achip::launch_plan_outputs(outSize, status, nBlocks, align, dstOff, dstCap, total, ctx->scratch, ctx->stream));
+    return 0;
+}
+
+// ---- compress bounds and the dense copy of a compressed batch (pack_outputs.hip) ----
+int32_t achip_compress_bound_batch(achip_ctx* ctx, int32_t codecOp, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks)
+{
+    switch (codecOp) {
+        case ACHIP_OP_LZ4_COMPRESS:
+        case ACHIP_OP_SNAPPY_COMPRESS:
+        case ACHIP_OP_ZSTD_COMPRESS:
+        case ACHIP_OP_LZ4FRAME_COMPRESS:
+        case ACHIP_OP_SNAPPYFRAMED_COMPRESS:
+        case ACHIP_OP_LZ4HADOOP_COMPRESS:
+        case ACHIP_OP_SNAPPYHADOOP_COMPRESS:
+        case ACHIP_OP_ZSTDSTREAM_COMPRESS: break;
+        default: return bad_argument("codecOp is not a compress op");
+    }
+    if (nBlocks < 0) return bad_argument("nBlocks < 0");
+    if (nBlocks == 0) return 0;
+    if (!ctx) return bad_argument("ctx is null");
+    if (!srcLen || !outSize || !status) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_compress_bound(codecOp, srcLen, outSize, status, nBlocks, ctx->hadoopBufferSize, ctx->stream));
+    return 0;
+}
+
+int32_t achip_pack_outputs(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* outLen, const int32_t* status, const void* rawBase, const int64_t* rawOff,
+                           const int32_t* rawLen, int32_t nBlocks, int32_t align, void* packedBase, int64_t packedCap, int64_t* packedOff, int32_t* packedLen, int32_t* stored,
+                           int64_t* total)
+{
+    if (align < 1 || align > 4096 || (align & (align - 1)) != 0) return bad_argument("align must be a power of two in 1..4096");
+    if (nBlocks < 0) return bad_argument("nBlocks < 0");
+    const int rawGiven = (rawBase != nullptr ? 1 : 0) + (rawOff != nullptr ? 1 : 0) + (rawLen != nullptr ? 1 : 0);
+    if (rawGiven != 0 && rawGiven != 3) return bad_argument("rawBase, rawOff and rawLen must all be given or all be null");
+    if ((stored != nullptr) != (rawGiven == 3)) return bad_argument("stored must be given exactly when the raw arrays are");
+    if (packedBase != nullptr && packedCap < 0) return bad_argument("packedCap < 0");
+    if (nBlocks == 0) return 0;
+    if (!ctx) return bad_argument("ctx is null");
+    if (!srcOff || !outLen || !status || !packedOff || !packedLen || !total) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int32_t r = sizing_scratch(ctx, achip::pack_outputs_scratch_bytes(nBlocks));
+    if (r < 0) return r;
+    const achip::PackArgs p{(const uint8_t*)srcBase, srcOff, outLen, status, (const uint8_t*)rawBase, rawOff, rawLen, nBlocks, align, (uint8_t*)packedBase, packedCap,
+                            packedOff, packedLen, stored, total};
+    HIP_TRY(achip::launch_pack_outputs(p, ctx->scratch, ctx->stream));
     return 0;
 }
 

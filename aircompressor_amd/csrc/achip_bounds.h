@@ -1,0 +1,56 @@
+// achip_bounds.h -- what the eight compress ops ask of dstCap, stated once: the host functions achip_*_max_compressed_length (achip_abi.cpp) and the bound
+// kernel of achip_compress_bound_batch (pack_outputs.hip) call these, so the two cannot drift.  Every helper takes a length n >= 0 and computes in 64 bits:
+// a result above INT32_MAX is the caller's to refuse (the host functions with their message, the kernel with a status).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace achip {
+namespace bound {
+
+// Lz4RawCompressor.maxCompressedLength  M/lz4/Lz4RawCompressor.java:56-59
+__host__ __device__ inline int64_t lz4(int64_t n) { return n + n / 255 + 16; }
+// SnappyRawCompressor.maxCompressedLength  M/snappy/SnappyRawCompressor.java:47-70
+__host__ __device__ inline int64_t snappy(int64_t n) { return 32 + n + n / 6; }
+// ZstdFrameCompressor's compressBound as ZstdJavaCompressor.maxCompressedLength states it (the shifts are those of the Java ints: for 0 <= n <= INT32_MAX
+// they are the plain ones; a negative n, which only the host function can be handed, wraps as it does there)
+__host__ __device__ inline int64_t zstd(int32_t n)
+{
+    int64_t result = (int64_t)n + (int64_t)((uint32_t)n >> 8);
+    if (n < 128 * 1024) {
+        result += (int64_t)((uint32_t)(128 * 1024 - (int64_t)n) >> 11);
+    }
+    return result;
+}
+// the stream writer's frame around the same blocks: header without a content size, the last block's header, the checksum
+__host__ __device__ inline int64_t zstdstream(int32_t n) { return zstd(n) + 16; }
+// Lz4FrameCompression.maxCompressedLength  M/lz4/Lz4FrameCompression.java:70-83
+__host__ __device__ inline int64_t lz4frame(int64_t n)
+{
+    const int64_t blocks = (n + (4 << 20) - 1) / (4 << 20);
+    return 7 + 4 + n + 4 * blocks;
+}
+// stream header + per 64 KiB block a chunk header, the masked CRC and at most the block itself (a compressed chunk is kept only at <= 0.85 of its
+// block: M/snappy/SnappyFramedOutputStream.java:214)
+__host__ __device__ inline int64_t snappyframed(int64_t n)
+{
+    const int64_t blocks = (n + 65535) / 65536;
+    return 10 + 8 * blocks + n;
+}
+// per chunk of bufferSize - overhead plaintext bytes: two big-endian ints and at most the codec's maxCompressedLength (M/lz4/Lz4HadoopOutputStream.java:44-46,
+// 107-118, 128-131; M/snappy/SnappyHadoopOutputStream.java likewise).  -1: the buffer leaves a chunk no room
+__host__ __device__ inline int64_t hadoop(bool snappyCodec, int64_t n, int32_t bufferSize)
+{
+    const int64_t overhead = snappyCodec ? bufferSize / 6 + 32 : ((int32_t)(bufferSize * 0.01) > 10 ? (int32_t)(bufferSize * 0.01) : 10);
+    const int64_t chunk = (int64_t)bufferSize - overhead;
+    if (bufferSize <= 0 || chunk <= 0) {
+        return -1;
+    }
+    const int64_t rest = n % chunk;
+    const int64_t full = snappyCodec ? snappy(chunk) : lz4(chunk);
+    const int64_t last = snappyCodec ? snappy(rest) : lz4(rest);
+    return (n / chunk) * (8 + full) + (rest > 0 ? 8 + last : 0);
+}
+
+}  // namespace bound
+}  // namespace achip

@@ -122,6 +122,33 @@ hipError_t launch_plan_outputs(const int64_t* outSize, const int32_t* status, in
                                hipStream_t stream);
 int64_t plan_outputs_scratch_bytes(int32_t nBlocks);
 
+// ---- compress bounds and the dense copy of a compressed batch (pack_outputs.hip) ----
+// `op`: one of the eight ACHIP_OP_*_COMPRESS (achip_compress_bound_batch has refused any other); hadoopBufferSize: the context's, for the two Hadoop ops
+hipError_t launch_compress_bound(int32_t op, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks, int32_t hadoopBufferSize, hipStream_t stream);
+// The copy's unit of work: this many bytes of destination address.  Chosen by the kernel's shape, not by a sweep: a workgroup of 256 lanes keeps eight 16-byte
+// loads per lane in flight (8 x 256 x 16), which amortises the two searches a tile costs and still cuts a 64 KiB-block batch's ~1.5 GiB stream into ~50 000 tiles,
+// 25 per workgroup of the grid.  Not tuned on a device (profiles/pack_rate.txt).
+constexpr int64_t PACK_TILE_BYTES = 32768;
+struct PackArgs {
+    const uint8_t* srcBase;  // a compress call's dstBase / dstOff / outLen / status
+    const int64_t* srcOff;
+    const int32_t* outLen;
+    const int32_t* status;
+    const uint8_t* rawBase;  // all three null, or the plaintexts: an item whose compressed form is no smaller is taken from here
+    const int64_t* rawOff;
+    const int32_t* rawLen;
+    int32_t nBlocks, align;
+    uint8_t* packedBase;  // null: plan only
+    int64_t packedCap;
+    int64_t* packedOff;
+    int32_t* packedLen;
+    int32_t* stored;  // null iff the raw arrays are
+    int64_t* total;   // [0] bytes of the dense stream, [1] items left out, [2] 1: the bytes were copied
+};
+// scan (achip_plan.h) and, if packedBase is given, the copy, which reads total[0] on the device and returns at once when the stream does not fit
+hipError_t launch_pack_outputs(const PackArgs& p, void* scratch, hipStream_t stream);
+int64_t pack_outputs_scratch_bytes(int32_t nBlocks);
+
 // ---- mixed batches, host-pointer staging, hashes (batch_mix.hip, xxhash.hip, xxhash3.hip) ----
 hipError_t launch_mix_gather(const int32_t* perm, int32_t n, const BatchArgs& a, int64_t* gSrcOff, int32_t* gSrcLen, int64_t* gDstOff, int32_t* gDstCap, hipStream_t stream);
 hipError_t launch_mix_scatter(const int32_t* perm, int32_t n, const int32_t* gOutLen, const int32_t* gStatus, const int64_t* gErr, const BatchArgs& a, hipStream_t stream);

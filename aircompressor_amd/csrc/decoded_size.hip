@@ -19,6 +19,7 @@
 #include "zstd_dec_common.h"
 #include "achip_launch.h"
 #include "achip_lists.h"
+#include "achip_plan.h"
 
 namespace achip {
 
@@ -975,131 +976,40 @@ __global__ __launch_bounds__(64) void container_size_kernel(SizeArgs s, ds::Size
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the planner: dstCap[i] = outSize[i], dstOff[i] = the sum of the capacities in front of i, each rounded up to `align`; an item with a status or beyond
-// INT32_MAX takes no room.  Reduce per tile, scan of the tile sums by one workgroup, scan per tile.
+// INT32_MAX takes no room.  The scan itself is achip_plan.h's.
 namespace ds {
-constexpr int PLAN_THREADS = 256, PLAN_PER_THREAD = 4, PLAN_TILE = PLAN_THREADS * PLAN_PER_THREAD;
-
-__device__ __forceinline__ int64_t plan_room(const int64_t* __restrict__ outSize, const int32_t* __restrict__ status, int64_t i, int64_t n, int64_t mask, int32_t& cap, int32_t& leftOut)
-{
-    cap = 0;
-    leftOut = 0;
-    if (i >= n) {
-        return 0;
-    }
-    const int64_t size = outSize[i];
-    if (status[i] != 0 || size < 0 || size > 0x7FFFFFFF) {
-        leftOut = 1;
-        return 0;
-    }
-    cap = (int32_t)size;
-    return (size + mask) & ~mask;
-}
-
-__device__ __forceinline__ int64_t wave_scan_incl64(int64_t v, int lane)
-{
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t t = __shfl_up(v, d);
-        if (lane >= d) {
-            v += t;
+struct PlanRoom {
+    const int64_t* __restrict__ outSize;
+    const int32_t* __restrict__ status;
+    int64_t* dstOff;
+    int32_t* dstCap;
+    __device__ __forceinline__ int64_t room(int64_t i, int64_t n, int64_t mask, int32_t& cap, int32_t& leftOut) const
+    {
+        cap = 0;
+        leftOut = 0;
+        if (i >= n) {
+            return 0;
         }
+        const int64_t size = outSize[i];
+        if (status[i] != 0 || size < 0 || size > 0x7FFFFFFF) {
+            leftOut = 1;
+            return 0;
+        }
+        cap = (int32_t)size;
+        return (size + mask) & ~mask;
     }
-    return v;
-}
-// inclusive scan over the workgroup's threads; total = the sum of all (waveSums: PLAN_THREADS / 64 words of LDS)
-__device__ __forceinline__ int64_t block_scan_incl64(int64_t v, int64_t* waveSums, int64_t& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t incl = wave_scan_incl64(v, lane);
-    __syncthreads();
-    if (lane == 63) {
-        waveSums[wave] = incl;
+    __device__ __forceinline__ void emit(int64_t i, int64_t at, int32_t cap) const
+    {
+        dstOff[i] = at;
+        dstCap[i] = cap;
     }
-    __syncthreads();
-    int64_t before = 0;
-    total = 0;
-    for (int k = 0; k < PLAN_THREADS / 64; k++) {
-        const int64_t w = waveSums[k];
-        before += k < wave ? w : 0;
-        total += w;
-    }
-    return incl + before;
-}
+    __device__ __forceinline__ void finish(int64_t*) const {}
+};
 }  // namespace ds
-
-__global__ __launch_bounds__(256) void plan_reduce_kernel(const int64_t* __restrict__ outSize, const int32_t* __restrict__ status, int32_t n, int64_t mask, int64_t* tileRoom, int64_t* tileLeftOut)
-{
-    using namespace ds;
-    __shared__ int64_t waveSums[PLAN_THREADS / 64];
-    const int64_t base = (int64_t)blockIdx.x * PLAN_TILE + (int64_t)threadIdx.x * PLAN_PER_THREAD;
-    int64_t room = 0, left = 0;
-    for (int k = 0; k < PLAN_PER_THREAD; k++) {
-        int32_t cap, leftOut;
-        room += plan_room(outSize, status, base + k, n, mask, cap, leftOut);
-        left += leftOut;
-    }
-    int64_t roomTotal = 0, leftTotal = 0;
-    block_scan_incl64(room, waveSums, roomTotal);
-    block_scan_incl64(left, waveSums, leftTotal);
-    if (threadIdx.x == 0) {
-        tileRoom[blockIdx.x] = roomTotal;
-        tileLeftOut[blockIdx.x] = leftTotal;
-    }
-}
-
-// one workgroup: tileRoom[] becomes its exclusive scan; total[0] = the bytes the output needs, total[1] = the items left out
-__global__ __launch_bounds__(256) void plan_tiles_kernel(int64_t* tileRoom, const int64_t* __restrict__ tileLeftOut, int32_t tiles, int64_t* total)
-{
-    using namespace ds;
-    __shared__ int64_t waveSums[PLAN_THREADS / 64];
-    int64_t base = 0, left = 0;
-    for (int32_t t0 = 0; t0 < tiles; t0 += PLAN_THREADS) {  // (uniform)
-        const int32_t t = t0 + (int32_t)threadIdx.x;
-        const int64_t room = t < tiles ? tileRoom[t] : 0;
-        left += t < tiles ? tileLeftOut[t] : 0;
-        int64_t sum = 0;
-        const int64_t incl = block_scan_incl64(room, waveSums, sum);
-        if (t < tiles) {
-            tileRoom[t] = base + incl - room;
-        }
-        base += sum;
-    }
-    int64_t leftTotal = 0;
-    block_scan_incl64(left, waveSums, leftTotal);
-    if (threadIdx.x == 0) {
-        total[0] = base;
-        total[1] = leftTotal;
-    }
-}
-
-__global__ __launch_bounds__(256) void plan_scan_kernel(const int64_t* __restrict__ outSize, const int32_t* __restrict__ status, int32_t n, int64_t mask, const int64_t* __restrict__ tileBase, int64_t* dstOff,
-                                                        int32_t* dstCap)
-{
-    using namespace ds;
-    __shared__ int64_t waveSums[PLAN_THREADS / 64];
-    const int64_t first = (int64_t)blockIdx.x * PLAN_TILE + (int64_t)threadIdx.x * PLAN_PER_THREAD;
-    int64_t room[PLAN_PER_THREAD];
-    int32_t cap[PLAN_PER_THREAD];
-    int64_t mine = 0;
-    for (int k = 0; k < PLAN_PER_THREAD; k++) {
-        int32_t leftOut;
-        room[k] = plan_room(outSize, status, first + k, n, mask, cap[k], leftOut);
-        mine += room[k];
-    }
-    int64_t sum = 0;
-    int64_t at = tileBase[blockIdx.x] + block_scan_incl64(mine, waveSums, sum) - mine;
-    for (int k = 0; k < PLAN_PER_THREAD; k++) {
-        if (first + k < n) {
-            dstOff[first + k] = at;
-            dstCap[first + k] = cap[k];
-        }
-        at += room[k];
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers
 namespace {
-int32_t plan_tiles(int32_t n) { return (int32_t)(((int64_t)n + ds::PLAN_TILE - 1) / ds::PLAN_TILE); }
 constexpr int64_t ZSTD_TABLES_AT = 1024;  // (the predefined tables in the scratch)
 
 // LZ4 blocks, by the batch size as the two-pass decoder's parser is chosen (lz4_decompress_v7.hip: a wavefront per block up to 16 384 blocks): a lane walks
@@ -1188,19 +1098,12 @@ hipError_t launch_decoded_size(int32_t op, const SizeArgs& s, hipStream_t stream
     }
 }
 
-int64_t plan_outputs_scratch_bytes(int32_t nBlocks) { return 2 * (int64_t)plan_tiles(nBlocks) * (int64_t)sizeof(int64_t); }
+int64_t plan_outputs_scratch_bytes(int32_t nBlocks) { return plan_scan_scratch_bytes(nBlocks); }
 
 hipError_t launch_plan_outputs(const int64_t* outSize, const int32_t* status, int32_t nBlocks, int32_t align, int64_t* dstOff, int32_t* dstCap, int64_t* total, void* scratch,
                                hipStream_t stream)
 {
-    const int32_t tiles = plan_tiles(nBlocks);
-    int64_t* tileRoom = (int64_t*)scratch;
-    int64_t* tileLeftOut = tileRoom + tiles;
-    const int64_t mask = (int64_t)align - 1;
-    hipLaunchKernelGGL(plan_reduce_kernel, dim3((unsigned)tiles), dim3(ds::PLAN_THREADS), 0, stream, outSize, status, nBlocks, mask, tileRoom, tileLeftOut);
-    hipLaunchKernelGGL(plan_tiles_kernel, dim3(1), dim3(ds::PLAN_THREADS), 0, stream, tileRoom, (const int64_t*)tileLeftOut, tiles, total);
-    hipLaunchKernelGGL(plan_scan_kernel, dim3((unsigned)tiles), dim3(ds::PLAN_THREADS), 0, stream, outSize, status, nBlocks, mask, (const int64_t*)tileRoom, dstOff, dstCap);
-    return hipGetLastError();
+    return launch_plan_scan(ds::PlanRoom{outSize, status, dstOff, dstCap}, nBlocks, align, total, scratch, stream);
 }
 
 }  // namespace achip

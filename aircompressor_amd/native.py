@@ -102,6 +102,8 @@ SIGNATURES = {
     "achip_zstdstream_compress_end": (_i32, [_vp, _vp]),
     "achip_decoded_size_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "achip_plan_outputs": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "achip_compress_bound_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32]),
+    "achip_pack_outputs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "achip_multi_batch_host": (_i32, [_vp, _i32, _i32, _vp] + _BATCH[1:] + [_vp]),
     "achip_partition_blocks": (_i32, [_vp, _i32, _i32, _vp]),
 }

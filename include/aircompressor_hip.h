@@ -409,6 +409,36 @@ int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* sr
 int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t* status, int32_t nBlocks, int32_t align,
                            int64_t* dstOff, int32_t* dstCap, int64_t* total /* [2] */);
 
+/* ---- The compress side of the same: bound -> plan -> compress -> pack, for a caller whose plaintexts and their lengths live in device memory ----
+ * achip_compress_bound_batch: outSize[i] = what `codecOp`, one of the eight compress ops (LZ4, SNAPPY, ZSTD, LZ4FRAME, SNAPPYFRAMED, LZ4HADOOP, SNAPPYHADOOP,
+ *   ZSTDSTREAM _COMPRESS; any other op is INVALID_ARGUMENT), asks of dstCap for srcLen[i] bytes: the op's achip_*_max_compressed_length(srcLen[i]), computed in
+ *   64-bit arithmetic -- what a Java caller asks Compressor.maxCompressedLength (M/Compressor.java:20) for, one int at a time on the host.  The Hadoop ops use
+ *   the context's "hadoop.buffer_size", as their compress call does.  A negative srcLen[i], or a bound above INT32_MAX, gives status[i] of class
+ *   INVALID_ARGUMENT and outSize[i] = 0; else status[i] = 0.  outSize / status feed achip_plan_outputs unchanged: its dstOff[] / dstCap[] / total are the
+ *   compress call's slots.
+ * achip_pack_outputs: the compress call's sparse result (srcBase / srcOff / outLen / status = its dstBase / dstOff / outLen / status: outLen[i] bytes at the
+ *   front of a worst-case slot each) as one dense stream -- the chunk loops of the writers (M/lz4/Lz4HadoopOutputStream.java:107-117,
+ *   M/snappy/SnappyFramedOutputStream.java:199-220: compress a chunk, append exactly what it took -- the latter also keeps the chunk itself where
+ *   compression did not pay) over a whole batch.
+ *   Item i is packed when status[i] == 0 and outLen[i] >= 0; any other item is left out: packedLen[i] = 0, it takes no room, packedOff[i] is the running offset.
+ *   Raw arrays given (all three, and `stored`; else all four NULL): a packed item with outLen[i] >= rawLen[i] is taken from rawBase[rawOff[i] .. + rawLen[i])
+ *   instead and stored[i] = 1 (an ORC writer's isOriginal chunk: keep the smaller); every other item has stored[i] = 0.
+ *   packedLen[i] = the bytes taken; packedOff[i] = the sum of the lengths in front of i, each rounded up to `align` (a power of two in 1 .. 4096; else
+ *   INVALID_ARGUMENT).  total[0] = the bytes of the dense stream (the sum of the rounded lengths), total[1] = the items left out.
+ *   packedBase == NULL: plan only (offsets, lengths, total[0..1]; total[2] = 0).  Else the bytes are copied if and only if total[0] <= packedCap -- decided on
+ *   the device, no host wait -- and total[2] = 1; if they do not fit, total[2] = 0 and not one byte of packedBase is written.  When copied, every byte of
+ *   [0, total[0]) is defined: the items at their offsets, zeros behind each up to `align`; bytes at and beyond total[0] are never written (no slack rule:
+ *   the compaction exists to give exact extents).  packedBase[0, packedCap) must not overlap any source region.
+ * Conventions as for the sizing calls above: all arrays device-accessible, asynchronous on the ctx stream, scratch from the context, nBlocks == 0 launches
+ * nothing and returns 0, value arguments are checked before the context is touched, the return value reports launch and argument failures only.
+ * bound -> plan -> readback of the total -> allocate the slots -> compress -> pack (plan only) -> readback of total[0] -> allocate exactly that -> pack:
+ * two synchronisations, no host walk. */
+int32_t achip_compress_bound_batch(achip_ctx* ctx, int32_t codecOp, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks);
+int32_t achip_pack_outputs(achip_ctx* ctx, const void* srcBase, const int64_t* srcOff, const int32_t* outLen, const int32_t* status,
+                           const void* rawBase, const int64_t* rawOff, const int32_t* rawLen, /* all three NULL, or all three set */
+                           int32_t nBlocks, int32_t align, void* packedBase, int64_t packedCap,
+                           int64_t* packedOff, int32_t* packedLen, int32_t* stored /* NULL iff raw is NULL */, int64_t* total /* [3] */);
+
 /* One process, several devices: the batch is cut into nCtx contiguous slices balanced by srcLen[i] + dstCap[i] (the rule of
  * achip_partition_blocks) and slice d runs through achip_batch_host (codecOps == NULL: every item is `codecOp`) or
  * achip_mixed_batch_host (codecOps[i] per item) on ctxs[d], each slice in a host thread of its own, all inside this call -- what

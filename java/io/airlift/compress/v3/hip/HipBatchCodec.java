@@ -196,6 +196,75 @@ public final class HipBatchCodec
                 sizeStatus, sizeErrorOffset);
     }
 
+    /**
+     * A batch compressed into one dense buffer: {@code packed} holds {@code totalBytes} bytes, item i at {@code packedOffset[i]} with {@code packedLength[i]}
+     * bytes (0: left out -- {@code status[i]} says why); {@code stored[i] == 1} (raw fallback only, else NULL): the item is its plaintext.  All in device
+     * memory of {@code context}; the pack may still be in flight on its stream.
+     */
+    public record Packed(HipNative.Context context, MemorySegment packed, long totalBytes, long leftOut, MemorySegment packedOffset, MemorySegment packedLength,
+            MemorySegment stored, MemorySegment outputLength, MemorySegment status, MemorySegment errorOffset) {}
+
+    /**
+     * Bounds, plan, a readback of the slots' total, allocate the slots, compress, pack (plan only), a readback of the dense total, allocate exactly that,
+     * pack: for a caller whose plaintexts and their lengths live in device memory.  Two calls here wait for the device; nothing is walked on the host.
+     * {@code rawFallback}: an item whose compressed form is no smaller than its plaintext is kept as the plaintext.  The caller frees the segments of the
+     * result with {@link HipNative.Context#freeDevice}.
+     */
+    public Packed compressPacked(int op, MemorySegment source, MemorySegment sourceOffset, MemorySegment sourceLength, int blocks, int align, boolean rawFallback)
+    {
+        HipNative.Context context = contexts[0];
+        long wide = Math.max(8L * blocks, 16);
+        long narrow = Math.max(4L * blocks, 16);
+        MemorySegment bound = context.allocateDevice(wide);
+        MemorySegment boundStatus = context.allocateDevice(narrow);
+        MemorySegment slotOffset = context.allocateDevice(wide);
+        MemorySegment slotCapacity = context.allocateDevice(narrow);
+        MemorySegment outputLength = context.allocateDevice(narrow);
+        MemorySegment status = context.allocateDevice(narrow);
+        MemorySegment errorOffset = context.allocateDevice(wide);
+        MemorySegment packedOffset = context.allocateDevice(wide);
+        MemorySegment packedLength = context.allocateDevice(narrow);
+        MemorySegment stored = rawFallback ? context.allocateDevice(narrow) : MemorySegment.NULL;
+        MemorySegment rawBase = rawFallback ? source : MemorySegment.NULL;
+        MemorySegment rawOffset = rawFallback ? sourceOffset : MemorySegment.NULL;
+        MemorySegment rawLength = rawFallback ? sourceLength : MemorySegment.NULL;
+        MemorySegment total = context.allocateDevice(24);
+        long slotBytes = 0;
+        long totalBytes = 0;
+        long leftOut = 0;
+        try (Arena arena = Arena.ofConfined()) {
+            MemorySegment host = arena.allocate(JAVA_LONG, 3);
+            context.compressBounds(op, sourceLength, bound, boundStatus, blocks);
+            context.planOutputs(bound, boundStatus, blocks, 1, slotOffset, slotCapacity, total);
+            if (blocks > 0) {
+                context.copyToHost(host, total, 16);
+                context.synchronize();
+                slotBytes = host.getAtIndex(JAVA_LONG, 0);
+            }
+            MemorySegment slots = context.allocateDevice(Math.max(slotBytes, 16));
+            context.launchBatch(op, source, sourceOffset, sourceLength, slots, slotOffset, slotCapacity, outputLength, status, errorOffset, blocks);
+            context.packOutputs(slots, slotOffset, outputLength, status, rawBase, rawOffset, rawLength, blocks, align, MemorySegment.NULL, 0, packedOffset, packedLength,
+                    stored, total);
+            if (blocks > 0) {
+                context.copyToHost(host, total, 24);
+                context.synchronize();
+                totalBytes = host.getAtIndex(JAVA_LONG, 0);
+                leftOut = host.getAtIndex(JAVA_LONG, 1);
+            }
+            MemorySegment packed = context.allocateDevice(Math.max(totalBytes, 16));
+            context.packOutputs(slots, slotOffset, outputLength, status, rawBase, rawOffset, rawLength, blocks, align, packed, totalBytes, packedOffset, packedLength,
+                    stored, total);
+            context.synchronize();  // (the slots are read until the copy is done)
+            context.freeDevice(slots);
+            context.freeDevice(total);
+            context.freeDevice(bound);
+            context.freeDevice(boundStatus);
+            context.freeDevice(slotOffset);
+            context.freeDevice(slotCapacity);
+            return new Packed(context, packed, totalBytes, leftOut, packedOffset, packedLength, stored, outputLength, status, errorOffset);
+        }
+    }
+
     /** Contiguous split balanced by bytes moved (source + destination): achip_partition_blocks itself, so that the split is the library's by construction. */
     static int[] partition(int[] sourceLength, int[] destinationCapacity, int parts)
     {

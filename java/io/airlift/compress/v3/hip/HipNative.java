@@ -276,7 +276,11 @@ public final class HipNative
             @NativeSignature(name = "achip_decoded_size_batch", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
             MethodHandle decodedSizeBatch,
             @NativeSignature(name = "achip_plan_outputs", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
-            MethodHandle planOutputs) {}
+            MethodHandle planOutputs,
+            @NativeSignature(name = "achip_compress_bound_batch", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
+            MethodHandle compressBoundBatch,
+            @NativeSignature(name = "achip_pack_outputs", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class, long.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle packOutputs) {}
 
     private static final Optional<LinkageError> LINKAGE_ERROR;
     private static final MethodHandles HANDLES;
@@ -1010,6 +1014,52 @@ public final class HipNative
             int result;
             try {
                 result = (int) HANDLES.planOutputs().invokeExact(handle(), outSize, status, blocks, align, dstOff, dstCap, total);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /**
+         * achip_compress_bound_batch: {@code outSize[i]} (long) = what compress op {@code op} asks of the destination capacity for {@code srcLen[i]} bytes --
+         * {@code Compressor.maxCompressedLength} for every item of a device-resident batch (the Hadoop ops with this context's hadoop.buffer_size).  A negative
+         * length or a bound beyond Integer.MAX_VALUE gives {@code status[i]} of class INVALID_ARGUMENT and {@code outSize[i] = 0}.  The pair feeds
+         * {@link #planOutputs} unchanged.  Asynchronous on this context's stream; all segments device-accessible.
+         */
+        public void compressBounds(int op, MemorySegment srcLen, MemorySegment outSize, MemorySegment status, int blocks)
+        {
+            int result;
+            try {
+                result = (int) HANDLES.compressBoundBatch().invokeExact(handle(), op, srcLen, outSize, status, blocks);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /**
+         * achip_pack_outputs: a compress call's {@code dstBase / dstOff / outLen / status} as one dense stream.  {@code packedLen[i]} = the bytes taken (0 for
+         * an item with a status or a negative length), {@code packedOff[i]} = the sum of the lengths in front, each rounded up to {@code align}.  With
+         * {@code rawBase / rawOff / rawLen / stored} (all four, or all {@code MemorySegment.NULL}) an item whose compressed form is no smaller is taken from the
+         * raw arrays and {@code stored[i] = 1}.  {@code total}: three longs -- the bytes of the stream, the items left out, 1 if the bytes were copied, which
+         * happens iff {@code packedBase} is not NULL and {@code total[0] <= packedCap} (decided on the device).  Asynchronous on this context's stream.
+         */
+        public void packOutputs(MemorySegment srcBase, MemorySegment srcOff, MemorySegment outLen, MemorySegment status, MemorySegment rawBase, MemorySegment rawOff,
+                MemorySegment rawLen, int blocks, int align, MemorySegment packedBase, long packedCap, MemorySegment packedOff, MemorySegment packedLen,
+                MemorySegment stored, MemorySegment total)
+        {
+            int result;
+            try {
+                result = (int) HANDLES.packOutputs().invokeExact(handle(), srcBase, srcOff, outLen, status, rawBase, rawOff, rawLen, blocks, align, packedBase, packedCap,
+                        packedOff, packedLen, stored, total);
             }
             catch (RuntimeException e) {
                 throw e;
