@@ -694,30 +694,11 @@ int32_t achip_zstd_max_compressed_length(int32_t n)
 
 int64_t achip_snappy_uncompressed_length(const void* src, int64_t srcLen, int64_t* errOffset)
 {
-    // SnappyRawDecompressor.readUncompressedLength  M/snappy/SnappyRawDecompressor.java:277-321
-    const uint8_t* in = (const uint8_t*)src;
-    uint32_t result = 0;
-    int64_t n = 0;
-    for (int i = 0; i < 5; i++) {
-        if (n >= srcLen) {
-            if (errOffset) *errOffset = srcLen - n;
-            return ACHIP_STATUS(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_TRUNCATED);
-        }
-        uint32_t b = in[n++];
-        result |= (b & 0x7f) << (7 * i);
-        if ((b & 0x80) == 0) {
-            break;
-        }
-        if (i == 4) {
-            if (errOffset) *errOffset = n;
-            return ACHIP_STATUS(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LEN_HIGH_BIT);
-        }
-    }
-    if ((int32_t)result < 0) {
-        if (errOffset) *errOffset = 0;
-        return ACHIP_STATUS(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_INVALID_LENGTH);
-    }
-    return (int64_t)result;
+    // SnappyRawDecompressor.readUncompressedLength  M/snappy/SnappyRawDecompressor.java:277-321 (at most 5 bytes are looked at)
+    int32_t expected = 0, nread = 0, eo = 0;
+    const int32_t st = achip::snappy_read_uncompressed_length((const uint8_t*)src, (int32_t)(srcLen > 5 ? 5 : (srcLen < 0 ? 0 : srcLen)), expected, nread, eo);
+    if (st != 0 && errOffset) *errOffset = srcLen < 0 ? srcLen : eo;
+    return st != 0 ? st : expected;
 }
 
 // An upper bound of what the frames in [src, src + srcLen) decode to -- what a one-shot decoder needs before it can read a stream

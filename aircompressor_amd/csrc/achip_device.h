@@ -43,7 +43,61 @@ struct BatchArgs {
 
 __device__ __forceinline__ int32_t batch_count(const BatchArgs& a) { return a.nBlocksDev != nullptr ? *a.nBlocksDev : a.nBlocks; }
 
-__device__ __forceinline__ constexpr int32_t mk_status(int cls, int detail) { return -(cls + 16 * detail); }
+__host__ __device__ __forceinline__ constexpr int32_t mk_status(int cls, int detail) { return -(cls + 16 * detail); }
+
+// SnappyRawDecompressor.readUncompressedLength (M/snappy/SnappyRawDecompressor.java:277-321): the little-endian base-128 length in front of a
+// raw Snappy stream, at most 5 bytes.  Returns 0 with `expected` (>= 0) and `nread` (the preamble's bytes), or the status with `eo`.  The one
+// copy: every decoder, reader and size query, and the host's achip_snappy_uncompressed_length.  (:49-50, the length against the output's
+// capacity, is the caller's where there is one.)
+__host__ __device__ __forceinline__ int32_t snappy_read_uncompressed_length(const uint8_t* in, int32_t len, int32_t& expected, int32_t& nread, int32_t& eo)
+{
+    uint32_t result = 0;
+    nread = 0;
+    for (int i = 0; i < 5; i++) {
+        if (nread >= len) {
+            eo = len - nread;
+            return mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_TRUNCATED);
+        }
+        const uint32_t b = in[nread++];
+        result |= (b & 0x7f) << (7 * i);
+        if ((b & 0x80) == 0) {
+            break;
+        }
+        if (i == 4) {
+            eo = nread;
+            return mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LEN_HIGH_BIT);
+        }
+    }
+    if ((int32_t)result < 0) {
+        eo = 0;
+        return mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_INVALID_LENGTH);
+    }
+    expected = (int32_t)result;
+    return 0;
+}
+
+// ... for callers that want the announced length alone: the length, or the (negative) status with `eo`
+__device__ __forceinline__ int32_t snappy_announced(const uint8_t* in, int32_t len, int32_t& eo)
+{
+    int32_t expected = 0, nread = 0;
+    const int32_t st = snappy_read_uncompressed_length(in, len, expected, nread, eo);
+    return st != 0 ? st : expected;
+}
+
+// SnappyRawDecompressor.opLookupTable (:223-271) as arithmetic: bits 0..7 the element's length (literals: + the trailer), 8..10 the copy
+// offset's high bits, 11.. the trailer's bytes
+__device__ __forceinline__ int32_t snappy_op_entry(int32_t op)
+{
+    const int32_t kind = op & 3;
+    const int32_t hi = op >> 2;
+    if (kind == 0) {
+        return hi < 60 ? hi + 1 : (((hi - 59) << 11) | 1);
+    }
+    if (kind == 1) {
+        return (1 << 11) | ((hi >> 3) << 8) | ((hi & 7) + 4);
+    }
+    return ((kind == 2 ? 2 : 4) << 11) | (hi + 1);
+}
 
 // LZ4 decoder choice of the auto mode: a batch is "mixed" when in more than a quarter of its groups of 16 consecutive
 // blocks (= the blocks one wavefront of the ring decoder works on) the compressed sizes differ by more than 2x

@@ -23,6 +23,14 @@ int snappy_ring_group_for(int32_t nBlocks);
 // two-pass decoders (lz4_decompress_v7.hip, snappy_decompress_v5.hip): parse to records, a wavefront per block executes them
 hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks);
 hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks);
+// what the two wrappers above share (lz4_decompress_v7.hip): memset, the parser by `parse` and the batch, the executor, the ring decoder for what is left
+namespace sx {
+struct ArenaHeader;
+}
+using TwoPassParseKernel = void (*)(BatchArgs a, sx::ArenaHeader* hdr, sx::BlockMeta* meta, int32_t* only, uint64_t* arena, int32_t maxChunks, const int32_t* stats);
+hipError_t launch_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, int parse,
+                          int32_t waveMaxBlocks, int32_t shortLimit, TwoPassParseKernel laneParser, TwoPassParseKernel waveParser,
+                          hipError_t (*rings)(const BatchArgs&, hipStream_t, int, int, const int32_t*));
 hipError_t launch_seq_execute2(const BatchArgs& a, hipStream_t stream, const sx::BlockMeta* meta, const uint64_t* arena, const int32_t* stats, int32_t shortLimit);
 int64_t twopass_scratch_bytes(int32_t nBlocks, int64_t perBlock);
 // record arena per block of the two-pass decoders (8 bytes per record; lz4_decompress_v7.hip: text-like 64 KiB blocks make 6 000 .. 8 500 LZ4

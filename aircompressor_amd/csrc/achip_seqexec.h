@@ -1,6 +1,7 @@
 // achip_seqexec.h -- what the two passes of the record-based LZ77 decoders share (lz4_decompress_v7.hip, snappy_decompress_v5.hip):
 // the 8-byte RECORD a parser writes per piece of work and the chunked arena the records live in, wave helpers, and the parser's view of
-// its compressed stream (LaneFeed).  The executor is achip_seqexec2.h.
+// its compressed stream (LaneFeed), how a sequence is cut into pieces (cut_piece), the lane parsers' record output (LaneRecordSink) and a block's
+// write-back (finish_block).  The executor is achip_seqexec2.h.
 //
 //   parse    a lane per block walks the token grammar (serial by nature) and writes one record per piece
 //            {literal length <= 16, match length <= 16, offset, header bytes skipped} into the arena -- no byte is copied;
@@ -209,6 +210,132 @@ __device__ __forceinline__ int32_t largest_multiple(int32_t off, int32_t x)
     m -= m * off > x ? 1 : 0;
     m += (m + 1) * off <= x ? 1 : 0;
     return m * off;
+}
+
+// ---- pieces: a sequence (lit literal bytes, then ml match bytes at offset off) is cut into records of at most 16 literal + 16 match bytes.
+// Pieces 0 .. litFull - 1 are 16 literal bytes each, piece litFull holds the rest of the literals (1..16, or 0 when there are none) and
+// the match's first 16 bytes, the pieces behind it 16 match bytes each.  A match's later pieces name the largest multiple of its offset
+// that stays inside the match's periodic source region [start - offset, ..): the same bytes, but never the output of the piece before
+// (no chains of dependent pieces). ----
+__device__ __forceinline__ int32_t lit_full(int32_t lit) { return lit > 16 ? (lit + 15) / 16 - 1 : 0; }
+__device__ __forceinline__ int32_t piece_count(int32_t lit, int32_t ml) { return lit_full(lit) + 1 + (ml > 16 ? (ml - 16 + 15) / 16 : 0); }
+// piece k (< piece_count) of the sequence: pl literal bytes, pm match bytes at offset o.  (off > 0 wherever o is used -- pm > 0 --: the
+// guard only keeps the division defined for a sequence without a match)
+__device__ __forceinline__ void cut_piece(int32_t lit, int32_t ml, int32_t off, int32_t litFull, int32_t k, int32_t& pl, int32_t& pm, int32_t& o)
+{
+    o = off;
+    if (k < litFull) {
+        pl = 16;
+        pm = 0;
+    }
+    else if (k == litFull) {
+        pl = lit - 16 * litFull;
+        pm = ml < 16 ? ml : 16;
+    }
+    else {
+        const int32_t m = k - litFull;  // match pieces before this one
+        pl = 0;
+        pm = ml - 16 * m < 16 ? ml - 16 * m : 16;
+        const int32_t xm = 16 * m + off;
+        o = largest_multiple(off > 0 ? off : 1, xm < 65535 ? xm : 65535);
+    }
+}
+// ... as a record; skip0: the compressed bytes in front of the sequence's literals (the first piece carries them)
+__device__ __forceinline__ uint64_t piece_record(int32_t lit, int32_t ml, int32_t off, int32_t litFull, int32_t k, int32_t skip0)
+{
+    int32_t pl, pm, o;
+    cut_piece(lit, ml, off, litFull, k, pl, pm, o);
+    return rec_pack((uint32_t)pl, (uint32_t)pm, pm > 0 ? (uint32_t)o : 0u, k == 0 ? (uint32_t)skip0 : 0u);
+}
+
+// What the lanes of a lane-per-block parser that request nothing read (LaneFeed's `anywhere`): one address per WAVEFRONT (one request per
+// load instruction, hot in this CU's L1) -- the start of the first non-empty stream of the wavefront, `fallback` when all are empty; a
+// single address for the whole grid would queue every wavefront of the chip at one L2 channel.
+__device__ __forceinline__ const uint8_t* idle_address(const uint8_t* srcBase, const uint8_t* in, int32_t inLimit, const void* fallback)
+{
+    const unsigned long long nonEmpty = __ballot(inLimit > 0);
+    const uint8_t* anywhere = (const uint8_t*)fallback;
+    if (nonEmpty != 0) {  // (uniform)
+        // (an offset from the batch's base travels, not a pointer: the loads stay global_load, not flat_load)
+        anywhere = srcBase + (int64_t)shfl_u64((uint64_t)((in - srcBase) - (int64_t)((uintptr_t)in & 31)), __builtin_ctzll(nonEmpty));
+    }
+    return anywhere;
+}
+
+// ---- the record output of a lane-per-block parser: exactly one record per lane and trip (an empty one when there is nothing to say),
+// eight trips to a 64-byte piece, kept in registers; the pieces go to 4 KiB chunks of the arena ----
+struct LaneRecordSink {
+    int32_t firstChunk, chunk, fill, count;
+    __device__ __forceinline__ void init()
+    {
+        firstChunk = -1;
+        chunk = -1;
+        fill = CHUNK_RECS;
+        count = 0;
+    }
+    // the group of eight leaves: a chunk for every lane that needs one (one atomic per wavefront), then one 64-byte piece per lane.
+    // Called by the whole wavefront; groupAny: the group holds a record of this lane.
+    __device__ __forceinline__ void flush(ArenaHeader* hdr, uint64_t* arena, int32_t maxChunks, int lane, const uint64_t (&rec)[8], int32_t groupAny, int32_t& fallback,
+                                          int32_t& finished)
+    {
+        const bool flush = groupAny != 0 && fallback == 0;
+        const bool need = flush && fill == CHUNK_RECS;
+        const unsigned long long nm = __ballot(need);
+        if (nm != 0) {  // (uniform)
+            int32_t base = 0;
+            if (lane == __builtin_ctzll(nm)) {
+                base = atomicAdd(&hdr->nextChunk, (int32_t)__popcll(nm));
+            }
+            base = wave_bcast(base, __builtin_ctzll(nm));
+            if (need) {
+                const int32_t c = base + (int32_t)__popcll(nm & ((1ull << lane) - 1));
+                if (c >= maxChunks) {  // the arena is exhausted: the ring decoder takes the block
+                    fallback = 1;
+                    finished = 1;
+                }
+                else {
+                    if (chunk >= 0) {
+                        arena[(int64_t)chunk * CHUNK_SLOTS + CHUNK_RECS] = (uint64_t)(uint32_t)c;  // link
+                    }
+                    else {
+                        firstChunk = c;
+                    }
+                    chunk = c;
+                    fill = 0;
+                }
+            }
+        }
+        if (flush && fallback == 0) {
+            uint8_t* const dst = (uint8_t*)(arena + (int64_t)chunk * CHUNK_SLOTS + fill);
+#pragma unroll
+            for (int k = 0; k < 8; k += 2) {
+                st16(dst + 8 * k, u32x4{(uint32_t)rec[k], (uint32_t)(rec[k] >> 32), (uint32_t)rec[k + 1], (uint32_t)(rec[k + 1] >> 32)});
+            }
+            fill += 8;
+            count += 8;
+        }
+    }
+};
+
+// A parsed block's results, by the one lane that holds them: a block whose records did not fit (or cannot be expressed) goes to the ring
+// decoder (`only`), any other gets its record chain and -- the parse pass decides them -- output length, status and error offset.
+__device__ __forceinline__ void finish_block(const BatchArgs& a, ArenaHeader* hdr, BlockMeta* meta, int32_t* only, int64_t block, bool fallback, int32_t firstChunk, int32_t count,
+                                             int32_t st, int32_t eo, int32_t op)
+{
+    if (fallback) {
+        only[block] = 1;
+        meta[block].firstChunk = 0;
+        meta[block].count = 0;
+        atomicAdd(&hdr->fallbackBlocks, 1);
+    }
+    else {
+        only[block] = 0;
+        meta[block].firstChunk = firstChunk < 0 ? 0 : firstChunk;
+        meta[block].count = st == 0 ? count : 0;
+        a.outLen[block] = st == 0 ? op : 0;
+        a.status[block] = st;
+        a.errOffset[block] = (int64_t)eo;
+    }
 }
 
 }  // namespace sx

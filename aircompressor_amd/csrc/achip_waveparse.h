@@ -1,6 +1,6 @@
 // achip_waveparse.h -- what the wavefront-per-block parsers of the two-pass decoders share (lz4_decompress_v7.hip lz4_parse_wave_kernel,
 // snappy_decompress_v5.hip snappy_parse_wave_kernel): the stream's bytes passing through a staging area in LDS, and the sink that writes a
-// block's records into chunks of the arena.
+// block's records into chunks of the arena, and what a window position holds when read as the start of a Snappy element (wp::SnappyPeek).
 #pragma once
 #include "achip_seqexec.h"
 
@@ -23,6 +23,16 @@ struct WaveStage {
     int32_t b0;        // (uniform) stream position of lds[0]; -1: nothing staged
     u32x4 pend[2];     // this lane's 2 x 16 bytes of [b0 + CAP, b0 + CAP + SLAB)
     int lane;
+    __device__ __forceinline__ void init(uint8_t* ldsArea, const uint8_t* stream, int32_t streamLimit, int laneId)
+    {
+        lds = ldsArea;
+        in = stream;
+        inLimit = streamLimit;
+        b0 = -1;
+        pend[0] = u32x4{0, 0, 0, 0};
+        pend[1] = u32x4{0, 0, 0, 0};
+        lane = laneId;
+    }
     __device__ __forceinline__ u32x4 fetch(int32_t pos) const
     {
         return pos + 16 <= inLimit ? ld16(in + pos) : u32x4{0, 0, 0, 0};  // (what lies beyond the block is never looked at: windows stay 8 bytes clear of the end)
@@ -80,6 +90,18 @@ struct WaveRecordSink {  // the block's records: chunks of the arena, claimed on
     // A batch of n (<= 64, uniform) records: begin(n) makes room (false: nothing may be stored -- the arena is exhausted), store() places one record at index
     // idx (< n) of the batch -- a lane may store several --, end(n) moves on.
     int32_t fresh;  // (uniform) the chunk a batch under way reaches into, or -1
+    __device__ __forceinline__ void init(sx::ArenaHeader* header, uint64_t* arenaBase, int32_t chunkLimit)
+    {
+        hdr = header;
+        arena = arenaBase;
+        maxChunks = chunkLimit;
+        firstChunk = -1;
+        chunk = -1;
+        fill = sx::CHUNK_RECS;
+        count = 0;
+        fallback = false;
+        fresh = -1;
+    }
     __device__ __forceinline__ bool begin(int32_t n, int lane)
     {
         fresh = -1;
@@ -140,6 +162,44 @@ struct WaveRecordSink {  // the block's records: chunks of the arena, claimed on
         }
     }
 };
+
+namespace wp {
+// What a window's position p holds, read AS IF an element started there.  Window mode asks with p = lane; serial mode asks every lane for p = 0 and has
+// the values made wave-uniform (UNI).  Positions are relative to the window.  (Snappy only: the LZ4 twin was written and measured, and both kernels that
+// would use it -- lz4_parse_wave_kernel, lz4_size_wave_kernel -- were slower on it beyond the old code's spread; they state their window reads themselves.)
+
+// Snappy: a run with its length in the tag and the 1- or 2-byte-offset copy behind it (one record), a run alone, or a copy alone
+struct SnappyPeek {
+    int32_t nLit;  // the run's bytes (0: no run at p)
+    int32_t q;     // the element behind the run (<= 124 for p < 64); the copy itself when there is no run
+    bool isRun, isCopy;
+    int32_t cLen, cOff, next;
+    bool stop;     // a run with length bytes, a copy with a 4-byte offset: not for the fast paths
+    template <bool UNI>
+    __device__ __forceinline__ void read(const uint8_t* stage, int32_t p)
+    {
+        uint32_t x;
+        __builtin_memcpy(&x, stage + p, 4);
+        const uint32_t tag = x & 0xFF;
+        isRun = (tag & 3) == 0;
+        nLit = isRun ? (int32_t)(tag >> 2) + 1 : 0;
+        nLit = UNI ? uni(nLit) : nLit;
+        q = p + (isRun ? 1 + nLit : 0);
+        uint32_t y;
+        __builtin_memcpy(&y, stage + q, 4);
+        const uint32_t tag2 = y & 0xFF, kind2 = tag2 & 3;
+        isCopy = kind2 == 1 || kind2 == 2;
+        const int32_t len1 = (int32_t)((tag2 >> 2) & 7) + 4, off1 = (int32_t)(((tag2 >> 5) << 8) | ((y >> 8) & 0xFF));
+        const int32_t len2 = (int32_t)(tag2 >> 2) + 1, off2 = (int32_t)((y >> 8) & 0xFFFF);
+        cLen = isCopy ? (kind2 == 1 ? len1 : len2) : 0;
+        cLen = UNI ? uni(cLen) : cLen;
+        cOff = kind2 == 1 ? off1 : off2;
+        cOff = UNI ? uni(cOff) : cOff;
+        next = q + (isCopy ? (kind2 == 1 ? 2 : 3) : 0);
+        stop = isRun ? (tag >> 2) >= 60 : (tag & 3) == 3;
+    }
+};
+}  // namespace wp
 
 // The chain of a window: lane p holds `next` = where the sequence after the one at p would begin (>= 64: beyond the window), `stop` = p cannot be on the chain.
 // members = the positions 0 -> next[0] -> next[next[0]] ... up to, not including, the first one that stops or lies beyond the window; cur = that position.

@@ -132,19 +132,6 @@ hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32
     return hipGetLastError();
 }
 
-__device__ __forceinline__ int32_t snappy_op_entry_probe(int32_t op)  // opLookupTable layout :223-271
-{
-    const int32_t kind = op & 3;
-    const int32_t hi = op >> 2;
-    if (kind == 0) {
-        return hi < 60 ? hi + 1 : (((hi - 59) << 11) | 1);
-    }
-    if (kind == 1) {
-        return (1 << 11) | ((hi >> 3) << 8) | ((hi & 7) + 4);
-    }
-    return ((kind == 2 ? 2 : 4) << 11) | (hi + 1);
-}
-
 // auto mode: how long are the elements?  1024 sampled blocks, the elements in the first 768 bytes of each (at most 192; a lane per sample;
 // tags only), parsed from an LDS copy of the block's head (the reason: lz4_sequence_sample_kernel above)
 __global__ __launch_bounds__(64) void snappy_element_sample_kernel(BatchArgs a, int32_t* stats, int32_t minBlocks, int32_t shortLimit)
@@ -181,7 +168,7 @@ __global__ __launch_bounds__(64) void snappy_element_sample_kernel(BatchArgs a, 
     ip++;
     while (ip < inLimit && elements < 192) {
         const int32_t opc = h[ip++];
-        const int32_t entry = snappy_op_entry_probe(opc);
+        const int32_t entry = snappy_op_entry(opc);
         const int32_t trailerBytes = entry >> 11;
         if (ip + trailerBytes > inLimit) {
             break;

@@ -68,33 +68,6 @@ __device__ __forceinline__ void wr_be(uint8_t* p, int32_t v)
     p[3] = (uint8_t)v;
 }
 
-// readUncompressedLength (M/snappy/SnappyRawDecompressor.java:277-321) of a chunk's data; returns the length or a status
-__device__ __forceinline__ int32_t snappy_announced(const uint8_t* in, int32_t len, int32_t& eoOut)
-{
-    uint32_t expected = 0;
-    int32_t nread = 0;
-    for (int i = 0; i < 5; i++) {
-        if (nread >= len) {
-            eoOut = len - nread;
-            return mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_TRUNCATED);
-        }
-        const uint32_t b = in[nread++];
-        expected |= (b & 0x7f) << (7 * i);
-        if ((b & 0x80) == 0) {
-            break;
-        }
-        if (i == 4) {
-            eoOut = nread;
-            return mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LEN_HIGH_BIT);
-        }
-    }
-    if ((int32_t)expected < 0) {
-        eoOut = 0;
-        return mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_INVALID_LENGTH);
-    }
-    return (int32_t)expected;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // the general reader: one wavefront per stream (everything wave-uniform)
 struct Reader {

@@ -35,7 +35,29 @@ extern "C" long long achip_emu_counters[16];
 #endif
 struct Lz4ParseState {
     int32_t ip, op, st, eo, litEndPrev;
-    bool done, fallback;
+    bool done;
+    // a block's start: the Java method's prologue :48-57 (have = false: no block, nothing to parse)
+    __device__ __forceinline__ void begin(const uint8_t* in, int32_t inLimit, int32_t outLimit, bool have)
+    {
+        ip = 0;
+        op = 0;
+        st = 0;
+        eo = 0;
+        litEndPrev = 0;
+        done = !have;
+        if (have) {
+            if (inLimit == 0) {  // :48-50
+                st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_LZ4_INPUT_EMPTY);
+                done = true;
+            }
+            else if (outLimit == 0) {  // :52-57 (the Java method returns -1 here)
+                if (!(inLimit == 1 && in[0] == 0)) {
+                    st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_LZ4_EMPTY_OUTPUT);
+                }
+                done = true;
+            }
+        }
+    }
 };
 
 // one sequence, the general way (M/lz4/Lz4RawDecompressor.java:59-195 without the copies); returns true when a record is to be emitted
@@ -125,38 +147,9 @@ __global__ __launch_bounds__(64) void lz4_parse2_kernel(BatchArgs a, sx::ArenaHe
     const int32_t outLimit = have ? a.dstCap[block] : 0;
 
     Feed L;
-    {
-        // what lanes that request nothing read: one address per WAVEFRONT (one request per load instruction, hot in this CU's L1) -- the
-        // start of the first non-empty stream of the wavefront; a single address for the whole grid would queue every wavefront of the
-        // chip at one L2 channel
-        const unsigned long long nonEmpty = __ballot(inLimit > 0);
-        const uint8_t* anywhere = (const uint8_t*)hdr;
-        if (nonEmpty != 0) {  // (uniform)
-            // (an offset from the batch's base travels, not a pointer: the loads stay global_load, not flat_load)
-            anywhere = a.srcBase + (int64_t)sx::shfl_u64((uint64_t)((in - a.srcBase) - (int64_t)((uintptr_t)in & 31)), __builtin_ctzll(nonEmpty));
-        }
-        L.init(ldsIn, lane, in, inLimit, anywhere);
-    }
+    L.init(ldsIn, lane, in, inLimit, sx::idle_address(a.srcBase, in, inLimit, hdr));
     Lz4ParseState S;
-    S.ip = 0;
-    S.op = 0;
-    S.st = 0;
-    S.eo = 0;
-    S.litEndPrev = 0;
-    S.done = !have;
-    S.fallback = false;
-    if (have) {
-        if (inLimit == 0) {  // :48-50
-            S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_LZ4_INPUT_EMPTY);
-            S.done = true;
-        }
-        else if (outLimit == 0) {  // :52-57 (the Java method returns -1 here)
-            if (!(inLimit == 1 && in[0] == 0)) {
-                S.st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_LZ4_EMPTY_OUTPUT);
-            }
-            S.done = true;
-        }
-    }
+    S.begin(in, inLimit, outLimit, have);
     const int32_t B = L.inBase;
     const int32_t fastIn = inLimit - 8;        // a literal run may end here at the latest (:82)
     const int32_t fastOut = outLimit - 8 - 4;  // a match may end here at the latest (:82, :168)
@@ -172,11 +165,11 @@ __global__ __launch_bounds__(64) void lz4_parse2_kernel(BatchArgs a, sx::ArenaHe
     int32_t sLast = 0;                                         // the block ends behind this sequence
     int32_t finished = S.done ? 1 : 0;                         // nothing more to emit
     int32_t fallback = 0;
-    // ---- the record output: exactly one record per lane and trip (an empty one when there is nothing to say), eight trips to a
-    // 64-byte piece, kept in registers ----
+    // ---- the record output (sx::LaneRecordSink) ----
     uint64_t rec[8];
     int32_t groupAny = 0;  // this group of eight holds a record of this lane
-    int32_t firstChunk = -1, chunk = -1, fill = sx::CHUNK_RECS, count = 0;
+    sx::LaneRecordSink K;
+    K.init();
 
     auto trip = [&](auto tTag) {
         constexpr int T = decltype(tTag)::value;
@@ -237,9 +230,9 @@ __global__ __launch_bounds__(64) void lz4_parse2_kernel(BatchArgs a, sx::ArenaHe
             finished = emit ? 0 : 1;  // (no record: the end of the block, or an error -- S.st)
             L.restart(S.ip + B, emit && !S.done && S.ip + B >= L.issueV + 64);
         }
-        // ---- phase 2: one piece -- at most 16 literal bytes and, behind a sequence's last literal bytes, at most 16 match bytes.  A
-        // match's later pieces name the largest multiple of its offset that stays inside the match's periodic source region
-        // [start - offset, ..): the same bytes, but never the output of the piece before (no chains of dependent pieces) ----
+        // ---- phase 2: one piece -- at most 16 literal bytes and, behind a sequence's last literal bytes, at most 16 match bytes:
+        // sx::cut_piece is the closed form; here the pieces come one per trip, from what is left of the sequence (sLit, sMl) and the
+        // match pieces made so far (sK) ----
         const bool do2 = finished == 0 && phase == 2;
         const int32_t pl = sLit < 16 ? sLit : 16;
         const int32_t pm = sLit > 16 ? 0 : (sMl < 16 ? sMl : 16);
@@ -272,59 +265,12 @@ __global__ __launch_bounds__(64) void lz4_parse2_kernel(BatchArgs a, sx::ArenaHe
         trip(std::integral_constant<int, 5>{});
         trip(std::integral_constant<int, 6>{});
         trip(std::integral_constant<int, 7>{});
-        // ---- the group leaves: a chunk for every lane that needs one (one atomic per wavefront), then one 64-byte piece per lane ----
-        const bool flush = groupAny != 0 && fallback == 0;
-        const bool need = flush && fill == sx::CHUNK_RECS;
-        const unsigned long long nm = __ballot(need);
-        if (nm != 0) {  // (uniform)
-            int32_t base = 0;
-            if (lane == __builtin_ctzll(nm)) {
-                base = atomicAdd(&hdr->nextChunk, (int32_t)__popcll(nm));
-            }
-            base = sx::wave_bcast(base, __builtin_ctzll(nm));
-            if (need) {
-                const int32_t c = base + (int32_t)__popcll(nm & ((1ull << lane) - 1));
-                if (c >= maxChunks) {  // the arena is exhausted: the ring decoder takes the block
-                    fallback = 1;
-                    finished = 1;
-                }
-                else {
-                    if (chunk >= 0) {
-                        arena[(int64_t)chunk * sx::CHUNK_SLOTS + sx::CHUNK_RECS] = (uint64_t)(uint32_t)c;  // link
-                    }
-                    else {
-                        firstChunk = c;
-                    }
-                    chunk = c;
-                    fill = 0;
-                }
-            }
-        }
-        if (flush && fallback == 0) {
-            uint8_t* const dst = (uint8_t*)(arena + (int64_t)chunk * sx::CHUNK_SLOTS + fill);
-#pragma unroll
-            for (int k = 0; k < 8; k += 2) {
-                st16(dst + 8 * k, u32x4{(uint32_t)rec[k], (uint32_t)(rec[k] >> 32), (uint32_t)rec[k + 1], (uint32_t)(rec[k + 1] >> 32)});
-            }
-            fill += 8;
-            count += 8;
-        }
+        K.flush(hdr, arena, maxChunks, lane, rec, groupAny, fallback, finished);
     }
+    // (`have` by a.nBlocks, not batch_count(a) as in snappy_parse2_kernel: no caller hands this kernel a batch counted on the device -- the
+    // container readers' launch_listed_decode brings the count home before it calls the two passes and passes it as nBlocks)
     if (have) {
-        if (fallback != 0) {
-            only[block] = 1;
-            meta[block].firstChunk = 0;
-            meta[block].count = 0;
-            atomicAdd(&hdr->fallbackBlocks, 1);
-        }
-        else {
-            only[block] = 0;
-            meta[block].firstChunk = firstChunk < 0 ? 0 : firstChunk;
-            meta[block].count = S.st == 0 ? count : 0;
-            a.outLen[block] = S.st == 0 ? S.op : 0;
-            a.status[block] = S.st;
-            a.errOffset[block] = (int64_t)S.eo;
-        }
+        sx::finish_block(a, hdr, meta, only, block, fallback != 0, K.firstChunk, K.count, S.st, S.eo, S.op);
     }
 }
 
@@ -344,6 +290,10 @@ __global__ __launch_bounds__(64) void lz4_parse2_kernel(BatchArgs a, sx::ArenaHe
 // written by the whole wavefront (a literal run of megabytes is 64 records per step).  Same records, same statuses and error offsets as the
 // parser above: the executor does not know which of the two wrote them.
 
+// (Set-up and write-back come from the shared headers -- WaveStage::init, WaveRecordSink::init, sx::finish_block: the same instructions.  The prologue, the two
+// window reads and the three piece blocks are stated here again, not taken from Lz4ParseState::begin and sx::piece_record: every one of them changes this kernel's
+// code, and the corpus batch of 8 192 blocks then decoded at 156.43 GiB/s (pieces and prologue shared) and 157.14 (the window reads as well) against 158.69, medians
+// of three with the old code's runs within 0.50 -- profiles/twopass_refactor_ab.txt.  A change to sx::cut_piece or Lz4ParseState::begin belongs here as well.)
 __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::ArenaHeader* hdr, sx::BlockMeta* meta, int32_t* only, uint64_t* arena, int32_t maxChunks, const int32_t* stats)
 {
     if (stats != nullptr && lz4_pick(stats, a.nBlocks) != LZ4_PICK_TWOPASS) {  // auto mode: the ring decoder takes this batch
@@ -355,13 +305,7 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
     const uint8_t* __restrict__ in = a.srcBase + a.srcOff[block];
     const int32_t inLimit = uni(a.srcLen[block]);
     WaveStage<wp::LZ4_STAGE> W;
-    W.lds = stageLds;
-    W.in = in;
-    W.inLimit = inLimit;
-    W.b0 = -1;
-    W.pend[0] = u32x4{0, 0, 0, 0};
-    W.pend[1] = u32x4{0, 0, 0, 0};
-    W.lane = lane;
+    W.init(stageLds, in, inLimit, lane);
     const int32_t outLimit = uni(a.dstCap[block]);
     Lz4ParseState S;
     S.ip = 0;
@@ -370,7 +314,6 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
     S.eo = 0;
     S.litEndPrev = 0;
     S.done = false;
-    S.fallback = false;
     if (inLimit == 0) {  // :48-50
         S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_LZ4_INPUT_EMPTY);
         S.done = true;
@@ -382,15 +325,7 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
         S.done = true;
     }
     WaveRecordSink K;
-    K.hdr = hdr;
-    K.arena = arena;
-    K.maxChunks = maxChunks;
-    K.firstChunk = -1;
-    K.chunk = -1;
-    K.fill = sx::CHUNK_RECS;
-    K.count = 0;
-    K.fallback = false;
-    K.fresh = -1;
+    K.init(hdr, arena, maxChunks);
     const int32_t fastOut = outLimit - 8 - 4;  // a match may end here at the latest (:82, :168)
     bool finished = S.done;                    // (uniform)
     bool serial = false;                       // (uniform) the sequences are long: one at a time (below)
@@ -441,7 +376,7 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
                     pl = 0;
                     pm = ml - 16 * m < 16 ? ml - 16 * m : 16;
                     const int32_t xm = 16 * m + offset;
-                    o = sx::largest_multiple(offset, xm < 65535 ? xm : 65535);
+                    o = sx::largest_multiple(offset, xm < 65535 ? xm : 65535);  // (no divisor guard as in sx::cut_piece: `ok` holds, so offset != 0)
                 }
                 K.put(sx::rec_pack((uint32_t)pl, (uint32_t)pm, pm > 0 ? (uint32_t)o : 0u, k == 0 ? (uint32_t)skip : 0u), k < pieces, lane, pieces, lane);
                 if (!K.fallback) {
@@ -553,6 +488,7 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
                 }
                 for (int32_t k0 = 0; k0 < pieces && !K.fallback; k0 += 64) {  // (uniform)
                     const int32_t k = k0 + lane;
+                    const int32_t left = pieces - k0;
                     int32_t pl, pm, o = sOff;
                     if (k < litFull) {
                         pl = 16;
@@ -569,7 +505,6 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
                         const int32_t xm = 16 * m + sOff;
                         o = sx::largest_multiple(sOff > 0 ? sOff : 1, xm < 65535 ? xm : 65535);
                     }
-                    const int32_t left = pieces - k0;
                     K.put(sx::rec_pack((uint32_t)pl, (uint32_t)pm, pm > 0 ? (uint32_t)o : 0u, k == 0 ? (uint32_t)skip0 : 0u), k < pieces, lane, left < 64 ? left : 64, lane);
                 }
                 S.litEndPrev = rStart + sLit;
@@ -578,20 +513,7 @@ __global__ __launch_bounds__(64) void lz4_parse_wave_kernel(BatchArgs a, sx::Are
         }
     }
     if (lane == 0) {
-        if (K.fallback) {
-            only[block] = 1;
-            meta[block].firstChunk = 0;
-            meta[block].count = 0;
-            atomicAdd(&hdr->fallbackBlocks, 1);
-        }
-        else {
-            only[block] = 0;
-            meta[block].firstChunk = K.firstChunk < 0 ? 0 : K.firstChunk;
-            meta[block].count = S.st == 0 ? K.count : 0;
-            a.outLen[block] = S.st == 0 ? S.op : 0;
-            a.status[block] = S.st;
-            a.errOffset[block] = (int64_t)S.eo;
-        }
+        sx::finish_block(a, hdr, meta, only, block, K.fallback, K.firstChunk, K.count, S.st, S.eo, S.op);
     }
 }
 
@@ -638,7 +560,11 @@ hipError_t launch_seq_execute2(const BatchArgs& a, hipStream_t stream, const sx:
 // helper streams, so that one part's parse could share the chip with another part's execute; measured in round 3 on the corpus batch
 // (profiles/r03_notes.md): 2 parts 520 GiB/s against 517, 4 parts 456, 8 parts 363: the two kernels compete for the same issue slots.
 // Removed, with the 8 KiB-window executor (489) and the register-capped one.)
-hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks)
+// (parse: 0 = the parser by the batch -- a wavefront per block up to waveMaxBlocks blocks with a count known to the host, a lane per block above --, 1 / 2 = that
+// parser; shortLimit: lz4_pick's, 12 for LZ4 sequences and 6 for Snappy elements; blocks whose records did not fit go to `rings` afterwards)
+hipError_t launch_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, int parse,
+                          int32_t waveMaxBlocks, int32_t shortLimit, TwoPassParseKernel laneParser, TwoPassParseKernel waveParser,
+                          hipError_t (*rings)(const BatchArgs&, hipStream_t, int, int, const int32_t*))
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
@@ -647,21 +573,26 @@ hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream,
     hipError_t e = hipMemsetAsync(s.hdr, 0, sizeof(sx::ArenaHeader), stream);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((a.nBlocks + 63) / 64)), wg(64);
-    const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.lz4Parse == 2 || (ks.lz4Parse == 0 && a.nBlocks <= LZ4_WAVE_PARSE_MAX_BLOCKS));
+    const bool wavePerBlock = a.nBlocksDev == nullptr && (parse == 2 || (parse == 0 && a.nBlocks <= waveMaxBlocks));
     if (wavePerBlock) {
-        hipLaunchKernelGGL(lz4_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
+        hipLaunchKernelGGL(waveParser, dim3((unsigned)a.nBlocks), wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
     }
     else {
-        hipLaunchKernelGGL(lz4_parse2_kernel, grid, wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
+        hipLaunchKernelGGL(laneParser, grid, wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
     }
-    e = launch_seq_execute2(a, stream, s.meta, s.arena, stats, 12);
+    e = launch_seq_execute2(a, stream, s.meta, s.arena, stats, shortLimit);
     if (e != hipSuccess) return e;
     BatchArgs f = a;
     f.only = s.only;
     f.onlyStats = stats;
-    f.onlyShortLimit = 12;
-    e = launch_lz4_decompress_rings(f, stream, groupSize, ringClass, nullptr);
+    f.onlyShortLimit = shortLimit;
+    e = rings(f, stream, groupSize, ringClass, nullptr);
     return e != hipSuccess ? e : hipGetLastError();
+}
+hipError_t launch_lz4_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks)
+{
+    return launch_twopass(a, stream, scratch, scratchBytes, groupSize, ringClass, stats, ks.lz4Parse, LZ4_WAVE_PARSE_MAX_BLOCKS, 12, lz4_parse2_kernel, lz4_parse_wave_kernel,
+                          launch_lz4_decompress_rings);
 }
 
 }  // namespace achip

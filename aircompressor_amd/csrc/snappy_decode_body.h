@@ -6,19 +6,6 @@
 
 namespace achip {
 
-__device__ __forceinline__ int32_t snappy_op_entry2(int32_t op)  // opLookupTable layout :223-271
-{
-    const int32_t kind = op & 3;
-    const int32_t hi = op >> 2;
-    if (kind == 0) {
-        return hi < 60 ? hi + 1 : (((hi - 59) << 11) | 1);
-    }
-    if (kind == 1) {
-        return (1 << 11) | ((hi >> 3) << 8) | ((hi & 7) + 4);
-    }
-    return ((kind == 2 ? 2 : 4) << 11) | (hi + 1);
-}
-
 // `ldsIn` / `ldsOut` / `ldsStage` (may be null): the group's rings.  On return st / eo hold the status and error offset, op the
 // bytes produced (flushed).  All lanes of the group return the same values.
 template <int GS, int IN_RING, int OUT_RING, int GPL, int PHASED = 0>
@@ -30,6 +17,8 @@ __device__ __forceinline__ void snappy_buffer_decode(uint8_t* ldsIn, uint8_t* ld
     int32_t op = 0;
 
     // readUncompressedLength :277-321 (at most 5 bytes: read straight from HBM)
+    // (The one restatement of snappy_read_uncompressed_length, achip_device.h, left in place: with the call here every instantiation of the
+    // ring kernels, the headline's among them, compiles to other instructions (tools/isa_diff.py).  A change to either goes into both.)
     uint32_t expected = 0;
     int32_t nread = 0;
     for (int i = 0; i < 5; i++) {
@@ -80,7 +69,7 @@ __device__ __forceinline__ void snappy_buffer_decode(uint8_t* ldsIn, uint8_t* ld
         // element header :84-110 at ip (tag already peeked): false = malformed at eo
         auto header = [&](int32_t opc, int32_t& entry, int32_t& trailer) -> bool {
             ip++;
-            entry = snappy_op_entry2(opc);
+            entry = snappy_op_entry(opc);
             const int32_t trailerBytes = entry >> 11;
             if (!(ip + 4 < inLimit)) {  // :90-92
                 if (ip + trailerBytes > inLimit) {
@@ -144,7 +133,7 @@ __device__ __forceinline__ void snappy_buffer_decode(uint8_t* ldsIn, uint8_t* ld
                             if ((opc2 & 3) == 0) {
                                 break;
                             }
-                            const int32_t entry2 = snappy_op_entry2(opc2);
+                            const int32_t entry2 = snappy_op_entry(opc2);
                             const int32_t tb2 = entry2 >> 11;
                             const int32_t trailer2 = (int32_t)(R.template ring_ld4<IN_RING>(R.inRing, ip + 1 + R.inBase) & (0xFFFFFFFFu >> (32 - 8 * tb2)));
                             const int32_t length2 = entry2 & 0xff;

@@ -14,19 +14,6 @@
 
 namespace achip {
 
-__device__ __forceinline__ int32_t snappy_op_entry5(int32_t op)  // opLookupTable layout :223-271
-{
-    const int32_t kind = op & 3;
-    const int32_t hi = op >> 2;
-    if (kind == 0) {
-        return hi < 60 ? hi + 1 : (((hi - 59) << 11) | 1);
-    }
-    if (kind == 1) {
-        return (1 << 11) | ((hi >> 3) << 8) | ((hi & 7) + 4);
-    }
-    return ((kind == 2 ? 2 : 4) << 11) | (hi + 1);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The parse pass: the structure of lz4_parse2_kernel (lz4_decompress_v7.hip has the reasons) -- the
 // stream through sx::LaneFeed (loads in flight for four trips), exactly one record per lane and trip kept in registers, flags in vector
@@ -53,7 +40,7 @@ __device__ __forceinline__ int snappy_parse_general(const uint8_t* __restrict__ 
         S.eo = (int32_t)(off);                                             \
         return 0;                                                          \
     }
-    const int32_t entry = snappy_op_entry5(opc);
+    const int32_t entry = snappy_op_entry(opc);
     const int32_t trailerBytes = entry >> 11;
     if (!(ip + 4 < inLimit)) {  // :90-92
         if (ip + trailerBytes > inLimit) SN_FAIL2(ip);
@@ -116,30 +103,10 @@ __global__ __launch_bounds__(64) void snappy_parse2_kernel(BatchArgs a, sx::Aren
     int32_t finished = have ? 0 : 1;
 
     // readUncompressedLength :277-321 (at most 5 bytes: read straight from the input buffer)
-    uint32_t expected = 0;
-    int32_t nread = 0;
+    int32_t expected = 0, nread = 0;
     if (have) {
-        for (int i = 0; i < 5; i++) {
-            if (nread >= inLen0) {
-                S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_TRUNCATED);
-                S.eo = inLen0 - nread;
-                break;
-            }
-            const uint32_t b = in0[nread++];
-            expected |= (b & 0x7f) << (7 * i);
-            if ((b & 0x80) == 0) {
-                break;
-            }
-            if (i == 4) {
-                S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LEN_HIGH_BIT);
-                S.eo = nread;
-            }
-        }
-        if (S.st == 0 && (int32_t)expected < 0) {
-            S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_INVALID_LENGTH);
-            S.eo = 0;
-        }
-        if (S.st == 0 && (int64_t)expected > (int64_t)outLimit) {  // :49-50
+        S.st = snappy_read_uncompressed_length(in0, inLen0, expected, nread, S.eo);
+        if (S.st == 0 && expected > outLimit) {  // :49-50
             S.st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_SNAPPY_OUTPUT_TOO_SMALL);
             S.eo = 0;
         }
@@ -152,14 +119,7 @@ __global__ __launch_bounds__(64) void snappy_parse2_kernel(BatchArgs a, sx::Aren
     const uint8_t* const in = in0 + (finished != 0 ? 0 : nread);
     const int32_t inLimit = finished != 0 ? 0 : inLen0 - nread;
     Feed L;
-    {
-        const unsigned long long nonEmpty = __ballot(inLimit > 0);
-        const uint8_t* anywhere = (const uint8_t*)hdr;
-        if (nonEmpty != 0) {  // (uniform) one idle address per wavefront, as an offset from the batch's base (the loads stay global_load)
-            anywhere = a.srcBase + (int64_t)sx::shfl_u64((uint64_t)((in - a.srcBase) - (int64_t)((uintptr_t)in & 31)), __builtin_ctzll(nonEmpty));
-        }
-        L.init(ldsIn, lane, in, inLimit, anywhere);
-    }
+    L.init(ldsIn, lane, in, inLimit, sx::idle_address(a.srcBase, in, inLimit, hdr));
     const int32_t B = L.inBase;
     const int32_t fastOutLimit = outLimit - 8;
 
@@ -172,7 +132,8 @@ __global__ __launch_bounds__(64) void snappy_parse2_kernel(BatchArgs a, sx::Aren
     int32_t fallback = 0;
     uint64_t rec[8];
     int32_t groupAny = 0;
-    int32_t firstChunk = -1, chunk = -1, fill = sx::CHUNK_RECS, count = 0;
+    sx::LaneRecordSink K;
+    K.init();
 
     auto trip = [&](auto tTag) {
         constexpr int T = decltype(tTag)::value;
@@ -251,7 +212,7 @@ __global__ __launch_bounds__(64) void snappy_parse2_kernel(BatchArgs a, sx::Aren
             finished |= fallback;
             L.restart(S.ip + B, finished == 0 && S.ip + B >= L.issueV + 64);
         }
-        // ---- phase 2: one piece (see lz4_parse2_kernel) ----
+        // ---- phase 2: one piece per trip (see lz4_parse2_kernel; sx::cut_piece is the closed form) ----
         const bool do2 = finished == 0 && phase == 2;
         const int32_t pl = sLit < 16 ? sLit : 16;
         const int32_t pm = sLit > 16 ? 0 : (sMl < 16 ? sMl : 16);
@@ -283,43 +244,7 @@ __global__ __launch_bounds__(64) void snappy_parse2_kernel(BatchArgs a, sx::Aren
         trip(std::integral_constant<int, 5>{});
         trip(std::integral_constant<int, 6>{});
         trip(std::integral_constant<int, 7>{});
-        // ---- the group leaves: a chunk for every lane that needs one (one atomic per wavefront), then one 64-byte piece per lane ----
-        const bool flush = groupAny != 0 && fallback == 0;
-        const bool need = flush && fill == sx::CHUNK_RECS;
-        const unsigned long long nm = __ballot(need);
-        if (nm != 0) {  // (uniform)
-            int32_t base = 0;
-            if (lane == __builtin_ctzll(nm)) {
-                base = atomicAdd(&hdr->nextChunk, (int32_t)__popcll(nm));
-            }
-            base = sx::wave_bcast(base, __builtin_ctzll(nm));
-            if (need) {
-                const int32_t c = base + (int32_t)__popcll(nm & ((1ull << lane) - 1));
-                if (c >= maxChunks) {  // the arena is exhausted: the ring decoder takes the block
-                    fallback = 1;
-                    finished = 1;
-                }
-                else {
-                    if (chunk >= 0) {
-                        arena[(int64_t)chunk * sx::CHUNK_SLOTS + sx::CHUNK_RECS] = (uint64_t)(uint32_t)c;  // link
-                    }
-                    else {
-                        firstChunk = c;
-                    }
-                    chunk = c;
-                    fill = 0;
-                }
-            }
-        }
-        if (flush && fallback == 0) {
-            uint8_t* const dst = (uint8_t*)(arena + (int64_t)chunk * sx::CHUNK_SLOTS + fill);
-#pragma unroll
-            for (int k = 0; k < 8; k += 2) {
-                st16(dst + 8 * k, u32x4{(uint32_t)rec[k], (uint32_t)(rec[k] >> 32), (uint32_t)rec[k + 1], (uint32_t)(rec[k + 1] >> 32)});
-            }
-            fill += 8;
-            count += 8;
-        }
+        K.flush(hdr, arena, maxChunks, lane, rec, groupAny, fallback, finished);
     }
     if (!have && block < a.nBlocks) {  // (a batch assembled on the device may hold fewer blocks than the launch was sized for)
         only[block] = 0;
@@ -327,24 +252,11 @@ __global__ __launch_bounds__(64) void snappy_parse2_kernel(BatchArgs a, sx::Aren
         meta[block].count = 0;
     }
     if (have) {
-        if (fallback != 0) {
-            only[block] = 1;
-            meta[block].firstChunk = 0;
-            meta[block].count = 0;
-            atomicAdd(&hdr->fallbackBlocks, 1);
+        if (S.st == 0 && expected != S.op) {  // :61-65
+            S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LENGTH_MISMATCH);
+            S.eo = 0;
         }
-        else {
-            if (S.st == 0 && (int64_t)expected != (int64_t)S.op) {  // :61-65
-                S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LENGTH_MISMATCH);
-                S.eo = 0;
-            }
-            only[block] = 0;
-            meta[block].firstChunk = firstChunk < 0 ? 0 : firstChunk;
-            meta[block].count = S.st == 0 ? count : 0;
-            a.outLen[block] = S.st == 0 ? S.op : 0;
-            a.status[block] = S.st;
-            a.errOffset[block] = (int64_t)S.eo;
-        }
+        sx::finish_block(a, hdr, meta, only, block, fallback != 0, K.firstChunk, K.count, S.st, S.eo, S.op);
     }
 }
 
@@ -375,30 +287,13 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
     S.st = 0;
     S.eo = 0;
     // readUncompressedLength :277-321 (uniform: every lane reads the same bytes)
-    uint32_t expected = 0;
-    int32_t nread = 0;
-    for (int i = 0; i < 5; i++) {
-        if (nread >= inLen0) {
-            S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_TRUNCATED);
-            S.eo = inLen0 - nread;
-            break;
-        }
-        const uint32_t b = (uint32_t)uni((int32_t)in0[nread]);
-        nread++;
-        expected |= (b & 0x7f) << (7 * i);
-        if ((b & 0x80) == 0) {
-            break;
-        }
-        if (i == 4) {
-            S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LEN_HIGH_BIT);
-            S.eo = nread;
-        }
-    }
-    if (S.st == 0 && (int32_t)expected < 0) {
-        S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_INVALID_LENGTH);
-        S.eo = 0;
-    }
-    if (S.st == 0 && (int64_t)expected > (int64_t)outLimit) {  // :49-50
+    int32_t expected = 0, nread = 0;
+    S.st = snappy_read_uncompressed_length(in0, inLen0, expected, nread, S.eo);
+    S.st = uni(S.st);
+    S.eo = uni(S.eo);
+    expected = uni(expected);
+    nread = uni(nread);
+    if (S.st == 0 && expected > outLimit) {  // :49-50
         S.st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_SNAPPY_OUTPUT_TOO_SMALL);
         S.eo = 0;
     }
@@ -407,23 +302,9 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
     const uint8_t* const in = in0 + (finished ? 0 : nread);
     const int32_t inLimit = finished ? 0 : inLen0 - nread;
     Stage W;
-    W.lds = stageLds;
-    W.in = in;
-    W.inLimit = inLimit;
-    W.b0 = -1;
-    W.pend[0] = u32x4{0, 0, 0, 0};
-    W.pend[1] = u32x4{0, 0, 0, 0};
-    W.lane = lane;
+    W.init(stageLds, in, inLimit, lane);
     WaveRecordSink K;
-    K.hdr = hdr;
-    K.arena = arena;
-    K.maxChunks = maxChunks;
-    K.firstChunk = -1;
-    K.chunk = -1;
-    K.fill = sx::CHUNK_RECS;
-    K.count = 0;
-    K.fallback = false;
-    K.fresh = -1;
+    K.init(hdr, arena, maxChunks);
     const int32_t fastOutLimit = outLimit - 8;
     int32_t litEndPrev = 0;  // (uniform) position (counted from in0) the executor's literal cursor stands at behind the records so far
     bool serial = false;                // (uniform) the elements are long: one pair at a time (lz4_parse_wave_kernel has the reasons)
@@ -434,47 +315,17 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
             // the element (pair) at the window's first position, read by every lane at once; lane k makes its piece k (at most seven)
             const int32_t base = S.ip;
             const uint8_t* const stage = W.window(base);
-            uint32_t x;
-            __builtin_memcpy(&x, stage, 4);
-            const uint32_t tag = x & 0xFF;
-            const bool isRun = (tag & 3) == 0;
-            const int32_t nLit = uni(isRun ? (int32_t)(tag >> 2) + 1 : 0);
-            const int32_t q = isRun ? 1 + nLit : 0;
-            uint32_t y;
-            __builtin_memcpy(&y, stage + q, 4);
-            const uint32_t tag2 = y & 0xFF, kind2 = tag2 & 3;
-            const bool isCopy = kind2 == 1 || kind2 == 2;
-            const int32_t len1 = (int32_t)((tag2 >> 2) & 7) + 4, off1 = (int32_t)(((tag2 >> 5) << 8) | ((y >> 8) & 0xFF));
-            const int32_t len2 = (int32_t)(tag2 >> 2) + 1, off2 = (int32_t)((y >> 8) & 0xFFFF);
-            const int32_t cLen = uni(isCopy ? (kind2 == 1 ? len1 : len2) : 0), cOff = uni(kind2 == 1 ? off1 : off2);
-            const int32_t next = q + (isCopy ? (kind2 == 1 ? 2 : 3) : 0);
-            const bool stop = isRun ? (tag >> 2) >= 60 : (tag & 3) == 3;
+            wp::SnappyPeek P;
+            P.read<true>(stage, 0);
+            const bool isRun = P.isRun, isCopy = P.isCopy, stop = P.stop;
+            const int32_t nLit = P.nLit, q = P.q, cLen = P.cLen, cOff = P.cOff, next = P.next;
             const int32_t opCopy = S.op + nLit, opEnd = opCopy + cLen;
             const int32_t skip = nread + base + (isRun ? 1 : 0) - litEndPrev;
             const bool ok = !stop && !(isRun && opCopy > fastOutLimit) && !(isCopy && (cOff == 0 || cOff > opCopy || opEnd > outLimit)) && skip <= sx::MAX_SKIP;
             serial = false;
             if (uni(ok ? 1 : 0) != 0) {  // (uniform)
-                const int32_t litFull = nLit > 16 ? (nLit + 15) / 16 - 1 : 0;
-                const int32_t matchRest = cLen > 16 ? (cLen - 16 + 15) / 16 : 0;
-                const int32_t pieces = litFull + 1 + matchRest;
-                const int32_t k = lane;
-                int32_t pl, pm, o = cOff;
-                if (k < litFull) {
-                    pl = 16;
-                    pm = 0;
-                }
-                else if (k == litFull) {
-                    pl = nLit - 16 * litFull;
-                    pm = cLen < 16 ? cLen : 16;
-                }
-                else {
-                    const int32_t m = k - litFull;
-                    pl = 0;
-                    pm = cLen - 16 * m < 16 ? cLen - 16 * m : 16;
-                    const int32_t xm = 16 * m + cOff;
-                    o = sx::largest_multiple(cOff > 0 ? cOff : 1, xm < 65535 ? xm : 65535);
-                }
-                K.put(sx::rec_pack((uint32_t)pl, (uint32_t)pm, pm > 0 ? (uint32_t)o : 0u, k == 0 ? (uint32_t)skip : 0u), k < pieces, lane, pieces, lane);
+                const int32_t pieces = sx::piece_count(nLit, cLen);
+                K.put(sx::piece_record(nLit, cLen, cOff, sx::lit_full(nLit), lane, skip), lane < pieces, lane, pieces, lane);
                 if (!K.fallback) {
                     S.op = opEnd;
                     litEndPrev = nread + base + q;
@@ -488,32 +339,20 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
             const int32_t base = S.ip;
             const uint8_t* const stage = W.window(base);
             // what an element at position `lane` of the window would be
-            uint32_t x;
-            __builtin_memcpy(&x, stage + lane, 4);
-            const uint32_t tag = x & 0xFF;
-            const bool isRun = (tag & 3) == 0;
-            const int32_t nLit = isRun ? (int32_t)(tag >> 2) + 1 : 0;  // (a run with its length in the tag)
-            const int32_t q = lane + (isRun ? 1 + nLit : 0);           // the element behind the run (<= 124); the copy itself when there is no run
-            uint32_t y;
-            __builtin_memcpy(&y, stage + q, 4);
-            const uint32_t tag2 = y & 0xFF, kind2 = tag2 & 3;
-            const bool isCopy = kind2 == 1 || kind2 == 2;
-            const int32_t len1 = (int32_t)((tag2 >> 2) & 7) + 4, off1 = (int32_t)(((tag2 >> 5) << 8) | ((y >> 8) & 0xFF));
-            const int32_t len2 = (int32_t)(tag2 >> 2) + 1, off2 = (int32_t)((y >> 8) & 0xFFFF);
-            const int32_t cLen = isCopy ? (kind2 == 1 ? len1 : len2) : 0, cOff = kind2 == 1 ? off1 : off2;
-            const int32_t next = q + (isCopy ? (kind2 == 1 ? 2 : 3) : 0);
+            wp::SnappyPeek P;
+            P.read<false>(stage, lane);
+            const bool isRun = P.isRun, isCopy = P.isCopy, stop = P.stop;
+            const int32_t nLit = P.nLit, q = P.q, cLen = P.cLen, cOff = P.cOff, next = P.next;
             // not for the chain: a run with length bytes, a copy with a 4-byte offset
-            const bool stop = isRun ? (tag >> 2) >= 60 : (tag & 3) == 3;
             const unsigned long long stopMask = __ballot(stop);
             unsigned long long members = 0;
             int32_t cur = 0;
             wave_chain(next, stop, stopMask, lane, members, cur);
             // the members' places in the output, and the checks that need them (the lane parser's runFast / copyFast; the input-side conditions hold in a window)
             const bool member = ((members >> lane) & 1ull) != 0;
-            const int32_t litFull = nLit > 16 ? (nLit + 15) / 16 - 1 : 0;
-            const int32_t matchRest = cLen > 16 ? (cLen - 16 + 15) / 16 : 0;
+            const int32_t litFull = sx::lit_full(nLit), allPieces = sx::piece_count(nLit, cLen);
             // one scan for both: output bytes in the low half (at most 64 x 124), pieces in the high half (at most 64 x 7)
-            const int32_t scanned = sx::wave_scan_incl(member ? ((nLit + cLen) | ((litFull + 1 + matchRest) << 16)) : 0, lane);
+            const int32_t scanned = sx::wave_scan_incl(member ? ((nLit + cLen) | (allPieces << 16)) : 0, lane);
             const int32_t endRel = scanned & 0xFFFF, pieceEnd = scanned >> 16;
             const int32_t opEnd = S.op + endRel, opCopy = opEnd - cLen;
             const bool wrong = member && ((isRun && opCopy > fastOutLimit) || (isCopy && (cOff == 0 || cOff > opCopy || opEnd > outLimit)));
@@ -531,30 +370,14 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
                 const int32_t litStart = nread + base + lane + (isRun ? 1 : 0);
                 const int32_t skip = litStart - (below != 0 ? nread + base + prevQ : litEndPrev);
                 const int last = 63 - __builtin_clzll(members);
-                const int32_t pieces = mine ? litFull + 1 + matchRest : 0;
+                const int32_t pieces = mine ? allPieces : 0;
                 const int32_t n = sx::wave_bcast(pieceEnd, last);
                 if (__ballot(mine && skip > sx::MAX_SKIP) != 0) {  // (a gap beyond the record field) the ring decoder takes the block
                     K.fallback = true;
                 }
                 else if (K.begin(n, lane)) {
                     for (int32_t k = 0; __ballot(k < pieces) != 0; k++) {  // (uniform) piece k of every element that has one: at most seven rounds, one or two on text
-                        int32_t pl, pm, o = cOff;
-                        if (k < litFull) {
-                            pl = 16;
-                            pm = 0;
-                        }
-                        else if (k == litFull) {
-                            pl = nLit - 16 * litFull;
-                            pm = cLen < 16 ? cLen : 16;
-                        }
-                        else {
-                            const int32_t m = k - litFull;  // copy pieces before this one
-                            pl = 0;
-                            pm = cLen - 16 * m < 16 ? cLen - 16 * m : 16;
-                            const int32_t xm = 16 * m + cOff;
-                            o = sx::largest_multiple(cOff > 0 ? cOff : 1, xm < 65535 ? xm : 65535);
-                        }
-                        K.store(sx::rec_pack((uint32_t)pl, (uint32_t)pm, pm > 0 ? (uint32_t)o : 0u, k == 0 ? (uint32_t)skip : 0u), k < pieces, pieceEnd - pieces + k);
+                        K.store(sx::piece_record(nLit, cLen, cOff, litFull, k, skip), k < pieces, pieceEnd - pieces + k);
                     }
                     K.end(n);
                     S.op += sx::wave_bcast(endRel, last);
@@ -580,33 +403,15 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
                 }
                 else if (kindG != 0) {
                     const int32_t sLit = kindG == 1 ? rLen : 0, sMl = kindG == 2 ? rLen : 0, sOff = kindG == 2 ? rOff : 0;
-                    const int32_t litFull = sLit > 16 ? (sLit + 15) / 16 - 1 : 0;
-                    const int32_t matchRest = sMl > 16 ? (sMl - 16 + 15) / 16 : 0;
-                    const int32_t pieces = litFull + 1 + matchRest;
+                    const int32_t pieces = sx::piece_count(sLit, sMl);
                     const int32_t skip0 = nread + rStart - litEndPrev;
                     if (skip0 > sx::MAX_SKIP) {
                         K.fallback = true;
                     }
                     for (int32_t k0 = 0; k0 < pieces && !K.fallback; k0 += 64) {  // (uniform)
                         const int32_t k = k0 + lane;
-                        int32_t pl, pm, o = sOff;
-                        if (k < litFull) {
-                            pl = 16;
-                            pm = 0;
-                        }
-                        else if (k == litFull) {
-                            pl = sLit - 16 * litFull;
-                            pm = sMl < 16 ? sMl : 16;
-                        }
-                        else {
-                            const int32_t m = k - litFull;
-                            pl = 0;
-                            pm = sMl - 16 * m < 16 ? sMl - 16 * m : 16;
-                            const int32_t xm = 16 * m + sOff;
-                            o = sx::largest_multiple(sOff > 0 ? sOff : 1, xm < 65535 ? xm : 65535);
-                        }
                         const int32_t left = pieces - k0;
-                        K.put(sx::rec_pack((uint32_t)pl, (uint32_t)pm, pm > 0 ? (uint32_t)o : 0u, k == 0 ? (uint32_t)skip0 : 0u), k < pieces, lane, left < 64 ? left : 64, lane);
+                        K.put(sx::piece_record(sLit, sMl, sOff, sx::lit_full(sLit), k, skip0), k < pieces, lane, left < 64 ? left : 64, lane);
                     }
                     litEndPrev = nread + rStart + sLit;
                 }
@@ -614,24 +419,11 @@ __global__ __launch_bounds__(64) void snappy_parse_wave_kernel(BatchArgs a, sx::
         }
     }
     if (lane == 0) {
-        if (K.fallback) {
-            only[block] = 1;
-            meta[block].firstChunk = 0;
-            meta[block].count = 0;
-            atomicAdd(&hdr->fallbackBlocks, 1);
+        if (S.st == 0 && expected != S.op) {  // :61-65
+            S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LENGTH_MISMATCH);
+            S.eo = 0;
         }
-        else {
-            if (S.st == 0 && (int64_t)expected != (int64_t)S.op) {  // :61-65
-                S.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNAPPY_LENGTH_MISMATCH);
-                S.eo = 0;
-            }
-            only[block] = 0;
-            meta[block].firstChunk = K.firstChunk < 0 ? 0 : K.firstChunk;
-            meta[block].count = S.st == 0 ? K.count : 0;
-            a.outLen[block] = S.st == 0 ? S.op : 0;
-            a.status[block] = S.st;
-            a.errOffset[block] = (int64_t)S.eo;
-        }
+        sx::finish_block(a, hdr, meta, only, block, K.fallback, K.firstChunk, K.count, S.st, S.eo, S.op);
     }
 }
 
@@ -644,28 +436,8 @@ int64_t snappy_twopass_scratch_bytes(int32_t nBlocks) { return twopass_scratch_b
 
 hipError_t launch_snappy_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int groupSize, int ringClass, const int32_t* stats, const KernelSettings& ks)
 {
-    if (a.nBlocks <= 0) {
-        return hipSuccess;
-    }
-    const sx::TwoPassLayout s(scratch, scratchBytes, a.nBlocks);
-    hipError_t e = hipMemsetAsync(s.hdr, 0, sizeof(sx::ArenaHeader), stream);
-    if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)((a.nBlocks + 63) / 64)), wg(64);
-    const bool wavePerBlock = a.nBlocksDev == nullptr && (ks.snappyParse == 2 || (ks.snappyParse == 0 && a.nBlocks <= SNAPPY_WAVE_PARSE_MAX_BLOCKS));
-    if (wavePerBlock) {
-        hipLaunchKernelGGL(snappy_parse_wave_kernel, dim3((unsigned)a.nBlocks), wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
-    }
-    else {
-        hipLaunchKernelGGL(snappy_parse2_kernel, grid, wg, 0, stream, a, s.hdr, s.meta, s.only, s.arena, s.maxChunks, stats);
-    }
-    e = launch_seq_execute2(a, stream, s.meta, s.arena, stats, 6);
-    if (e != hipSuccess) return e;
-    BatchArgs f = a;
-    f.only = s.only;
-    f.onlyStats = stats;
-    f.onlyShortLimit = 6;
-    e = launch_snappy_decompress_rings(f, stream, groupSize, ringClass, nullptr);
-    return e != hipSuccess ? e : hipGetLastError();
+    return launch_twopass(a, stream, scratch, scratchBytes, groupSize, ringClass, stats, ks.snappyParse, SNAPPY_WAVE_PARSE_MAX_BLOCKS, 6, snappy_parse2_kernel,
+                          snappy_parse_wave_kernel, launch_snappy_decompress_rings);
 }
 
 }  // namespace achip

@@ -31,7 +31,9 @@ constexpr int IN_RING = 2048, OUT_RING = 4096;
         return mk_status(ACHIP_CLASS_MALFORMED, detail); \
     }
 
-// readUncompressedLength (M/snappy/SnappyRawDecompressor.java:277-321) of a chunk's data
+// readUncompressedLength of a chunk's data, for decompress_item alone: a restatement of snappy_read_uncompressed_length (achip_device.h; walk_stream below
+// calls that one) kept because with the call snappyframed_decompress_kernel -- one instruction more -- read 1 024 streams of 4 MiB in 63.51 ms against 63.04
+// and 408.12 against 407.16 (medians of three; the old code's runs lay within 0.27 and 0.64), profiles/twopass_refactor_ab.txt.  A change there belongs here too.
 __device__ __forceinline__ int32_t read_uncompressed_length(const uint8_t* in, int32_t len, int32_t& expectedOut, int32_t& eoOut)
 {
     uint32_t expected = 0;
@@ -575,8 +577,8 @@ __device__ void walk_stream(const BatchArgs& a, const ChunkList& L, int32_t stre
         const int32_t dlen = length - 4;
         int32_t produced, limit, rawLen;
         if (flag == COMPRESSED_DATA_FLAG) {
-            int32_t ulen = 0, beo = 0;
-            const int32_t pst = read_uncompressed_length(in + pos + 4, dlen, ulen, beo);
+            int32_t ulen = 0, beo = 0, preamble = 0;
+            const int32_t pst = snappy_read_uncompressed_length(in + pos + 4, dlen, ulen, preamble, beo);
             if (pst != 0) {  // the block codec's own exception, before any byte is decoded
                 stOut = pst;
                 eoOut = (int64_t)beo;

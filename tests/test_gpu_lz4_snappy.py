@@ -207,6 +207,80 @@ def test_snappy_two_pass_decoder(gb, o, variant, parse):
             assert outs[i] == eout, "case %d" % i
 
 
+# the two-pass parsers cut a sequence into pieces of at most 16 literal + 16 match bytes: lengths at, one under and one over the cuts; offsets shorter than a
+# piece (a match's later pieces then name a multiple of the offset), around a piece, and one beyond the executor's 4 KiB window
+EDGE_LITS = (15, 16, 17, 31, 32, 33, 48, 49)
+EDGE_MATCHES = (4, 15, 16, 17, 20, 32, 33, 64, 65)
+EDGE_OFFSETS = (1, 2, 3, 15, 16, 17, 4097)
+
+
+def _edge_streams(rng):
+    """(plaintext, LZ4 stream, Snappy stream) with exactly these sequences: every EDGE_MATCHES x EDGE_OFFSETS pair, each behind a literal run from EDGE_LITS in
+    turn (the first far match behind a run of 4 200 bytes, which puts 4 097 bytes in front of it).  Written by hand because the reference encoders do not write
+    all of them: the LZ4 one hashes five bytes and finds no match of four, the Snappy one probes every second byte from the 33rd of a run on."""
+    spec = [[m, off] for off in EDGE_OFFSETS for m in EDGE_MATCHES]
+    for k, q in enumerate(spec):
+        q.insert(0, 4200 if q[1] == 4097 and q[0] == EDGE_MATCHES[0] else EDGE_LITS[k % len(EDGE_LITS)])
+    plain, lz4, snappy = bytearray(), bytearray(), bytearray()
+
+    def length_bytes(n):  # LZ4: what of a length does not fit the token's nibble
+        return bytes([255] * ((n - 15) // 255) + [(n - 15) % 255]) if n >= 15 else b""
+
+    def snappy_run(data):
+        n = len(data) - 1
+        return (bytes([n << 2]) if n < 60 else bytes([61 << 2]) + n.to_bytes(2, "little")) + data
+
+    for lit, m, off in spec:
+        data = bytes(rng.integers(0, 256, lit, dtype=np.uint8))
+        plain += data
+        for _ in range(m):
+            plain.append(plain[-off])
+        lz4 += bytes([(min(lit, 15) << 4) | min(m - 4, 15)]) + length_bytes(lit) + data + off.to_bytes(2, "little") + length_bytes(m - 4)
+        snappy += snappy_run(data)
+        for n in (m,) if m <= 64 else (64, m - 64):
+            snappy += bytes([1 | ((n - 4) << 2) | ((off >> 8) << 5), off & 0xFF]) if 4 <= n <= 11 and off < 2048 else bytes([2 | ((n - 1) << 2)]) + off.to_bytes(2, "little")
+    tail = bytes(rng.integers(0, 256, 16, dtype=np.uint8))  # (LZ4: a block ends with literals, no match within its last bytes)
+    plain += tail
+    lz4 += bytes([15 << 4]) + length_bytes(len(tail)) + tail
+    snappy += snappy_run(tail)
+    pre, v = bytearray(), len(plain)
+    while v >= 0x80:
+        pre.append((v & 0x7F) | 0x80)
+        v >>= 7
+    pre.append(v)
+    return bytes(plain), bytes(lz4), bytes(pre + snappy)
+
+
+@pytest.mark.parametrize("parse", [1, 2], ids=["lane-per-block-parse", "wavefront-per-block-parse"])
+@pytest.mark.parametrize("codec", ["lz4", "snappy"])
+def test_two_pass_piece_and_chunk_edges(gb, o, codec, parse):
+    """variant 7 with either parser over 65 blocks -- one more than a wavefront of the lane parser holds, so the last block sits alone among 63 idle lanes --: pieces
+    at, under and over the 16-byte cuts with offsets shorter than, around and far beyond a piece (EDGE_*: the plaintext compressed by the oracle, and once more as
+    the hand-written stream that holds every pair exactly -- the last block), and word-like text of 8 KiB and 20 KiB, whose records need one and two chunk links
+    (over 504 and over 1 008 records).  Plaintext, status 0 and the exact length for every block; nothing is handed to the ring decoder."""
+    rng = np.random.default_rng(65)
+    plain, lz4, snappy = _edge_streams(rng)
+    text = b"".join(d for _, d, _ in common.corpus_sample()[:2])
+    assert len(text) >= 20480 + 61 * 331
+    # (records, counted from the oracle's streams by sx::piece_count per sequence -- what the wavefront parser writes; the lane parser adds empty ones --:
+    # the 8 KiB block 702 for LZ4 and 1 047 for Snappy, the 20 KiB block 1 895 and 3 073; a chunk holds 504)
+    blocks = [plain, text[:8192], text[:20480]] + [text[20480 + 331 * i:20480 + 331 * i + 1 + 37 * i] for i in range(61)] + [plain]
+    comp = [o.compress(codec, b) for b in blocks[:-1]] + [lz4 if codec == "lz4" else snappy]
+    assert len(blocks) == 65 and o.decompress(codec, comp[-1], len(plain)) == plain
+    configure(gb, codec, (7, 4, 0))
+    gb.set_option("%s.decompress.parse" % codec, parse)
+    try:
+        outs, status, _ = gb.run(CODECS[codec]["d"], comp, [len(b) for b in blocks], unaligned=True)
+        fallback = gb.codec.native.get_stat("decompress.twopass_fallback_blocks")
+    finally:
+        gb.set_option("%s.decompress.parse" % codec, 0)
+        configure(gb, codec, DECODERS[0])
+    assert status == [0] * 65, status
+    assert [len(x) for x in outs] == [len(b) for b in blocks]
+    assert outs == blocks
+    assert fallback == 0
+
+
 @pytest.mark.parametrize("codec", ["lz4", "snappy"])
 def test_auto_mode_picks_a_decoder_on_the_device(gb, o, codec):
     """variant 5 (the default): batches of at least auto_min_blocks blocks are probed on the device -- groups of 16 consecutive blocks
