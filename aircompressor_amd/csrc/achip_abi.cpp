@@ -19,6 +19,7 @@
 
 #include "achip_bounds.h"
 #include "achip_launch.h"
+#include "achip_xxh_stream.h"
 
 // A context: its settings (achip_settings.h: what achip_ctx_set_option writes) and the state it owns.
 struct achip_ctx : achip::Settings {
@@ -1387,6 +1388,148 @@ int32_t achip_xxhash3_128(achip_ctx* ctx, const void* src, int64_t srcLen, int64
 {
     if (!outHash) return bad_argument("outHash is null");
     return hash_host(ctx, src, srcLen, seed, HostHash::XXH3_128, outHash);
+}
+
+// ---- streaming hashers (xxhash_stream.hip): states in device memory, reset / update / digest ----
+int64_t achip_hash_state_size(int32_t algo)
+{
+    const int64_t n = achip::hash_state_size(algo);
+    return n > 0 ? n : bad_argument("unknown hash algorithm");
+}
+
+int32_t achip_hash_states_reset(achip_ctx* ctx, int32_t algo, void* states, int32_t nStates, int64_t seed)
+{
+    if (achip::hash_state_size(algo) < 0) return bad_argument("unknown hash algorithm");
+    if (!ctx) return bad_argument("ctx is null");
+    if (nStates < 0) return bad_argument("nStates < 0");
+    if (nStates == 0) return 0;
+    if (!states) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_hash_states_reset(algo, states, nStates, (uint64_t)seed, ctx->stream));
+    return 0;
+}
+
+int32_t achip_hash_states_update(achip_ctx* ctx, int32_t algo, void* states, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t nStates)
+{
+    if (achip::hash_state_size(algo) < 0) return bad_argument("unknown hash algorithm");
+    if (!ctx) return bad_argument("ctx is null");
+    if (nStates < 0) return bad_argument("nStates < 0");
+    if (nStates == 0) return 0;
+    if (!states || !srcOff || !srcLen) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_hash_states_update(algo, states, srcBase, srcOff, srcLen, nStates, ctx->stream));
+    return 0;
+}
+
+int32_t achip_hash_states_digest(achip_ctx* ctx, int32_t algo, const void* states, int64_t* outHash, int32_t nStates)
+{
+    if (achip::hash_state_size(algo) < 0) return bad_argument("unknown hash algorithm");
+    if (!ctx) return bad_argument("ctx is null");
+    if (nStates < 0) return bad_argument("nStates < 0");
+    if (nStates == 0) return 0;
+    if (!states || !outHash) return bad_argument("null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_hash_states_digest(algo, states, outHash, nStates, ctx->stream));
+    return 0;
+}
+
+// One stream fed from HOST memory: a single state in device memory of its own, and the context's pinned staging for the bytes (a chunk at a
+// time: the staging is the context's, so a chunk is absorbed before the next one overwrites it).
+namespace {
+constexpr int64_t kHasherChunk = 1 << 20;
+struct HostHasher {
+    achip_ctx* ctx;
+    int32_t algo;
+    uint8_t* dev;  // the state, then srcOff (8), srcLen (4 + 4), the result (16)
+    int64_t stateBytes;
+};
+}  // namespace
+
+void* achip_hasher_create(achip_ctx* ctx, int32_t algo, int64_t seed)
+{
+    const int64_t stateBytes = achip::hash_state_size(algo);
+    if (stateBytes < 0) {
+        bad_argument("unknown hash algorithm");
+        return nullptr;
+    }
+    if (!ctx) {
+        bad_argument("ctx is null");
+        return nullptr;
+    }
+    HostHasher* h = new HostHasher{ctx, algo, nullptr, stateBytes};
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dev, (size_t)(stateBytes + 32));
+    if (e == hipSuccess) e = achip::launch_hash_states_reset(algo, h->dev, 1, (uint64_t)seed, ctx->stream);
+    if (e != hipSuccess) {
+        device_failure("achip_hasher_create", e);
+        if (h->dev) (void)hipFree(h->dev);
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+
+int32_t achip_hasher_update(void* hasher, const void* src, int64_t srcLen)
+{
+    HostHasher* h = (HostHasher*)hasher;
+    if (!h) return bad_argument("hasher is null");
+    if (srcLen < 0) return bad_argument("srcLen < 0");
+    if (srcLen > 0 && !src) return bad_argument("src is null");
+    achip_ctx* ctx = h->ctx;
+    for (int64_t at = 0; at < srcLen; at += kHasherChunk) {
+        const int64_t n = std::min(kHasherChunk, srcLen - at);
+        const int32_t r = ensure_stage(ctx, kHasherChunk + 64);
+        if (r < 0) return r;
+        uint8_t* hs = ctx->hostStage;
+        uint8_t* ds = ctx->devStage;
+        memcpy(hs, (const uint8_t*)src + at, (size_t)n);
+        *(int64_t*)(hs + kHasherChunk) = 0;               // srcOff
+        *(int32_t*)(hs + kHasherChunk + 8) = (int32_t)n;  // srcLen
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipMemcpyAsync(ds, hs, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ds + kHasherChunk, hs + kHasherChunk, 16, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(achip::launch_hash_states_update(h->algo, h->dev, ds, (const int64_t*)(ds + kHasherChunk), (const int32_t*)(ds + kHasherChunk + 8), 1, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+}
+
+int32_t achip_hasher_digest(void* hasher, int64_t* out)
+{
+    HostHasher* h = (HostHasher*)hasher;
+    if (!h) return bad_argument("hasher is null");
+    if (!out) return bad_argument("out is null");
+    achip_ctx* ctx = h->ctx;
+    int64_t* dOut = (int64_t*)(h->dev + h->stateBytes + 16);
+    int64_t got[2] = {0, 0};
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(achip::launch_hash_states_digest(h->algo, h->dev, dOut, 1, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(got, dOut, h->algo == achip::HASH_XXH3_128 ? 16 : 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    out[0] = got[0];
+    out[1] = got[1];
+    return 0;
+}
+
+int32_t achip_hasher_reset(void* hasher, int64_t seed)
+{
+    HostHasher* h = (HostHasher*)hasher;
+    if (!h) return bad_argument("hasher is null");
+    HIP_TRY(hipSetDevice(h->ctx->device));
+    HIP_TRY(achip::launch_hash_states_reset(h->algo, h->dev, 1, (uint64_t)seed, h->ctx->stream));
+    return 0;
+}
+
+int32_t achip_hasher_destroy(void* hasher)
+{
+    HostHasher* h = (HostHasher*)hasher;
+    if (!h) return bad_argument("hasher is null");
+    achip_ctx* ctx = h->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipFree(h->dev));
+    delete h;
+    return 0;
 }
 
 // ---- host-pointer batches: chunked, double-buffered staging (H2D || kernels || D2H || host copies) ---------------

@@ -66,6 +66,15 @@ SIGNATURES = {
     "achip_xxhash3_128_batch": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32]),
     "achip_xxhash3_64": (_i32, [_vp, _vp, _i64, _i64, _vp]),
     "achip_xxhash3_128": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "achip_hash_state_size": (_i64, [_i32]),
+    "achip_hash_states_reset": (_i32, [_vp, _i32, _vp, _i32, _i64]),
+    "achip_hash_states_update": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32]),
+    "achip_hash_states_digest": (_i32, [_vp, _i32, _vp, _vp, _i32]),
+    "achip_hasher_create": (_vp, [_vp, _i32, _i64]),
+    "achip_hasher_update": (_i32, [_vp, _vp, _i64]),
+    "achip_hasher_digest": (_i32, [_vp, _vp]),
+    "achip_hasher_reset": (_i32, [_vp, _i64]),
+    "achip_hasher_destroy": (_i32, [_vp]),
     "achip_device_alloc": (_vp, [_vp, _i64]),
     "achip_device_free": (_i32, [_vp, _vp]),
     "achip_host_alloc_pinned": (_vp, [_i64]),

@@ -4,9 +4,12 @@
 int length, long seed)` (M/xxhash/XxHash64Hasher.java:55-86) and `XxHash32Hasher.hash(...)` (M/xxhash/XxHash32Hasher.java):
 same argument order, same range check, and the result is the Java `long` / `int` (signed).  `hash_batch` hashes many
 device-resident buffers per call.  `XxHash3HipHasher` adds XXH3 (64- and 128-bit, the reference's XxHash3Native with a `long` seed;
-`XxHash128` is its record of two signed longs).  HIP only: no CPU fallback.
+`XxHash128` is its record of two signed longs).  The streaming form of the same hashers (`create(seed)` / `new_hasher(seed)`, then
+`update` / `update_le_long` / `update_le_int` / `digest` / `reset` / `close`, M/xxhash/XxHash64Hasher.java:91-169) is `HipStreamHasher`;
+`HipHashStates` is a batch of such states in device memory.  HIP only: no CPU fallback.
 """
 import ctypes
+import struct
 from collections import namedtuple
 
 import numpy as np
@@ -64,14 +67,154 @@ def _as_signed(v, bits):
     return v - (1 << bits) if v >> (bits - 1) else v
 
 
+HASH_XXH32, HASH_XXH64, HASH_XXH3_64, HASH_XXH3_128 = 0, 1, 2, 3
+
+
+class HipStreamHasher:
+    """A streaming hasher on the GPU: the reference's hasher object (XxHash64Hasher.java:91-169; XxHash32Hasher, XxHash3Hasher and
+    XxHash3Hasher128 have the same methods).  The bytes of `update` are staged to the device in chunks and absorbed there, so one update
+    may be longer than 2 GiB; `update` and `digest` block, `reset` does not.  `digest()` leaves the state as it is: it may be called
+    mid-stream and twice.  Returns what the one-shot twins return: a signed long, a signed int (XXH32) or an XxHash128."""
+
+    def __init__(self, algo, seed=DEFAULT_SEED, device=0, native_ctx=None):
+        self.native = native_ctx or native.HipNative(device)
+        self._lib = self.native.lib
+        self._algo = algo
+        self._h = self._lib.achip_hasher_create(self.native.ctx, algo, ctypes.c_int64(_as_signed(seed, 64)))
+        if not self._h:
+            raise native.HipUnavailableError("achip_hasher_create failed: %s" % self._lib.achip_last_error().decode())
+
+    def _check_not_closed(self):
+        # checkNotClosed (M/xxhash/XxHash3Native.java:330-334: IllegalStateException)
+        if self._h is None:
+            raise RuntimeError("Hasher has been closed")
+
+    def update(self, input, offset=0, length=None):
+        self._check_not_closed()
+        view = np.frombuffer(input, dtype=np.uint8)
+        if length is None:
+            length = view.size - offset
+        _check_from_index_size(view, offset, length)
+        src = view[offset:offset + length]
+        r = self._lib.achip_hasher_update(self._h, src.ctypes.data if src.size else None, int(src.size))
+        if r < 0:
+            native.raise_for_status(r)
+        return self
+
+    def update_le_long(self, v):
+        """updateLE(long): the value's eight bytes, little-endian"""
+        return self.update(struct.pack("<Q", v & ((1 << 64) - 1)))
+
+    def update_le_int(self, v):
+        """updateLE(int): the value's four bytes, little-endian"""
+        return self.update(struct.pack("<I", v & 0xFFFFFFFF))
+
+    def digest(self):
+        self._check_not_closed()
+        out = (ctypes.c_int64 * 2)()
+        r = self._lib.achip_hasher_digest(self._h, out)
+        if r < 0:
+            native.raise_for_status(r)
+        if self._algo == HASH_XXH3_128:
+            return XxHash128(int(out[0]), int(out[1]))
+        return _as_signed(int(out[0]), 32) if self._algo == HASH_XXH32 else int(out[0])
+
+    def reset(self, seed=DEFAULT_SEED):
+        self._check_not_closed()
+        r = self._lib.achip_hasher_reset(self._h, ctypes.c_int64(_as_signed(seed, 64)))
+        if r < 0:
+            native.raise_for_status(r)
+        return self
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            self._lib.achip_hasher_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipHashStates:
+    """`n` hasher states of one algorithm in device memory (achip_hash_states_*): the batch form.  reset / update / digest take device
+    pointers (ints or objects with data_ptr()) and are asynchronous on the context's stream.  update: state i absorbs
+    src_base[src_off[i] .. + src_len[i]) (int64 offsets, int32 lengths; a length <= 0 leaves the state alone).  digest: out holds n int64
+    (XXH32 zero-extended), 2n for XXH3-128 (low, high).  reset(seed, first, count) resets a sub-range: one array may mix seeds."""
+
+    def __init__(self, algo, n, native_ctx=None, device=0):
+        self.native = native_ctx or native.HipNative(device)
+        self._lib = self.native.lib
+        self.algo, self.n = algo, int(n)
+        self.state_size = int(self._lib.achip_hash_state_size(algo))
+        if self.state_size < 0:
+            native.raise_for_status(self.state_size)
+        self.ptr = self._lib.achip_device_alloc(self.native.ctx, max(1, self.state_size * self.n))
+        if not self.ptr:
+            raise native.HipUnavailableError("achip_device_alloc failed: %s" % self._lib.achip_last_error().decode())
+
+    @staticmethod
+    def _p(x):
+        return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+
+    def reset(self, seed=DEFAULT_SEED, first=0, count=None):
+        count = self.n - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.n:
+            raise IndexError("Range [%d, %d + %d) out of bounds for length %d" % (first, first, count, self.n))
+        r = self._lib.achip_hash_states_reset(self.native.ctx, self.algo, ctypes.c_void_p(self.ptr + first * self.state_size), count, ctypes.c_int64(_as_signed(seed, 64)))
+        if r < 0:
+            native.raise_for_status(r)
+        return self
+
+    def update(self, src_base, src_off, src_len):
+        r = self._lib.achip_hash_states_update(self.native.ctx, self.algo, ctypes.c_void_p(self.ptr), self._p(src_base), self._p(src_off), self._p(src_len), self.n)
+        if r < 0:
+            native.raise_for_status(r)
+        return self
+
+    def digest(self, out):
+        r = self._lib.achip_hash_states_digest(self.native.ctx, self.algo, ctypes.c_void_p(self.ptr), self._p(out), self.n)
+        if r < 0:
+            native.raise_for_status(r)
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.native.synchronize()
+            self._lib.achip_device_free(self.native.ctx, self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class XxHash64HipHasher(_HipHasher):
-    """One-shot XXH64 (XxHash64Hasher.hash, M/xxhash/XxHash64Hasher.java:55-86); returns the Java long."""
+    """One-shot XXH64 (XxHash64Hasher.hash, M/xxhash/XxHash64Hasher.java:55-86); returns the Java long.  `create(seed)` gives the streaming
+    hasher (XxHash64Hasher.create, :91-101)."""
     _wide = True
+
+    @staticmethod
+    def create(seed=DEFAULT_SEED, device=0, native_ctx=None):
+        return HipStreamHasher(HASH_XXH64, seed, device, native_ctx)
 
 
 class XxHash32HipHasher(_HipHasher):
-    """One-shot XXH32 (XxHash32Hasher.hash, M/xxhash/XxHash32Hasher.java); returns the Java int."""
+    """One-shot XXH32 (XxHash32Hasher.hash, M/xxhash/XxHash32Hasher.java); returns the Java int.  `create(seed)` gives the streaming hasher."""
     _wide = False
+
+    @staticmethod
+    def create(seed=DEFAULT_SEED, device=0, native_ctx=None):
+        return HipStreamHasher(HASH_XXH32, seed, device, native_ctx)
 
 
 class XxHash128(namedtuple("XxHash128", ["low", "high"])):
@@ -89,6 +232,16 @@ class XxHash3HipHasher:
     def __init__(self, device=0, native_ctx=None):
         self.native = native_ctx or native.HipNative(device)
         self._lib = self.native.lib
+
+    @staticmethod
+    def new_hasher(seed=DEFAULT_SEED, device=0, native_ctx=None):
+        """the streaming 64-bit hasher (XxHash3Native.newHasher, M/xxhash/XxHash3Native.java:77-105)"""
+        return HipStreamHasher(HASH_XXH3_64, seed, device, native_ctx)
+
+    @staticmethod
+    def new_hasher128(seed=DEFAULT_SEED, device=0, native_ctx=None):
+        """the streaming 128-bit hasher (XxHash3Native.newHasher128); digest() returns an XxHash128"""
+        return HipStreamHasher(HASH_XXH3_128, seed, device, native_ctx)
 
     def _one(self, fn, words, input, offset, length, seed):
         view = np.frombuffer(input, dtype=np.uint8)
@@ -123,4 +276,5 @@ class XxHash3HipHasher:
         self._batch(self._lib.achip_xxhash3_128_batch, src_base, src_off, src_len, out_hash, n_buffers, seed)
 
 
-__all__ = ["XxHash64HipHasher", "XxHash32HipHasher", "XxHash3HipHasher", "XxHash128", "DEFAULT_SEED", "IllegalArgumentException"]
+__all__ = ["XxHash64HipHasher", "XxHash32HipHasher", "XxHash3HipHasher", "XxHash128", "HipStreamHasher", "HipHashStates",
+           "HASH_XXH32", "HASH_XXH64", "HASH_XXH3_64", "HASH_XXH3_128", "DEFAULT_SEED", "IllegalArgumentException"]

@@ -345,6 +345,42 @@ int32_t achip_xxhash3_128_batch(achip_ctx* ctx, const void* srcBase, const int64
 int32_t achip_xxhash3_64(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash);
 int32_t achip_xxhash3_128(achip_ctx* ctx, const void* src, int64_t srcLen, int64_t seed, int64_t* outHash);
 
+/* ---- streaming hashers (xxhash_stream.hip): the update / digest form of the four hashers ----
+ * Replace the streaming half of the reference's hasher objects, for MANY streams per call:
+ *   XxHash64Hasher.create(seed) / update / updateLE / digest / reset / close   M/xxhash/XxHash64Hasher.java:91-169
+ *   the same interface of XxHash32Hasher.java, XxHash3Hasher.java and XxHash3Hasher128.java
+ *   XxHash3Native.newHasher / newHasher128 (:77-105), Hasher64Impl (:220-344) and its 128-bit twin.
+ * A hasher is a fixed-size record in device memory whose layout is private; `algo` is one of ACHIP_HASH_*.  State i of a batch lies at
+ * states + i * achip_hash_state_size(algo).  A state carries its seed (XXH3: the secret derived from it), so one array may hold states
+ * reset with different seeds (reset sub-ranges through pointer arithmetic) and update / digest take none. */
+#define ACHIP_HASH_XXH32 0
+#define ACHIP_HASH_XXH64 1
+#define ACHIP_HASH_XXH3_64 2  /* 2 and 3 share the record and the update; only the digest differs */
+#define ACHIP_HASH_XXH3_128 3
+/* bytes of one state: a multiple of 16, below 1024; an unknown algo gives the (negative) INVALID_ARGUMENT status */
+int64_t achip_hash_state_size(int32_t algo);
+/* The batch calls: all arrays device-accessible, asynchronous on the context's stream, nStates == 0 launches nothing and returns 0.
+ * reset  (create(seed) / reset(seed), XxHash64Hasher.java:91-101,150-160): every state becomes a fresh hasher with `seed` (XXH32: its low 32 bits).
+ * update (update(MemorySegment), :103-140): state i absorbs srcBase[srcOff[i] .. + srcLen[i]); srcLen[i] <= 0 leaves it untouched.  Two
+ *        items of one call must not name the same state (there is no state index: item i IS state i); overlapping state arrays in one call are
+ *        the caller's error and the result is undefined.
+ * digest (digest(), :142-148): outHash[i] = the hash of everything state i absorbed since its last reset (XXH32: zero-extended;
+ *        XXH3-128: outHash[2i] = low, outHash[2i + 1] = high, as achip_xxhash3_128_batch).  Reads the states, never writes them. */
+int32_t achip_hash_states_reset(achip_ctx* ctx, int32_t algo, void* states, int32_t nStates, int64_t seed);
+int32_t achip_hash_states_update(achip_ctx* ctx, int32_t algo, void* states, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t nStates);
+int32_t achip_hash_states_digest(achip_ctx* ctx, int32_t algo, const void* states, int64_t* outHash, int32_t nStates);
+/* One stream fed from HOST memory -- the literal twin of a reference hasher object (XxHash3Native.java:220-344): one state of its own on the
+ * device, the bytes staged through the context's pinned buffer in chunks, so srcLen may exceed INT32_MAX.
+ * create  NULL on failure (achip_last_error); asynchronous.
+ * update  BLOCKS until the bytes are absorbed (src may be reused on return); srcLen == 0 does nothing.
+ * digest  BLOCKS; out[0] = the hash (XXH32 zero-extended), out[1] = the high half of XXH3-128 (0 otherwise); the state is unchanged.
+ * reset   asynchronous.   destroy  (close(), :162-169) BLOCKS until the context's stream is idle, then frees the state. */
+void* achip_hasher_create(achip_ctx* ctx, int32_t algo, int64_t seed);
+int32_t achip_hasher_update(void* hasher, const void* src, int64_t srcLen);
+int32_t achip_hasher_digest(void* hasher, int64_t* out);
+int32_t achip_hasher_reset(void* hasher, int64_t seed);
+int32_t achip_hasher_destroy(void* hasher);
+
 /* Host-pointer batch: nBlocks independent blocks described by HOST arrays of HOST
  * pointers' offsets relative to srcBase/dstBase (host).  Stages in, launches the
  * device batch for `codecOp`, stages out, synchronizes.  codecOp: see below. */

@@ -165,6 +165,25 @@ public final class HipNative
             MethodHandle xxhash3Batch,
             @NativeSignature(name = "achip_xxhash3_128_batch", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, long.class, MemorySegment.class, int.class})
             MethodHandle xxhash3Hash128Batch,
+            // streaming hashers (xxhash_stream.hip): states in device memory (batch calls) and one stream fed from host memory (hasher calls)
+            @NativeSignature(name = "achip_hash_state_size", returnType = long.class, argumentTypes = int.class)
+            MethodHandle hashStateSize,
+            @NativeSignature(name = "achip_hash_states_reset", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, int.class, long.class})
+            MethodHandle hashStatesReset,
+            @NativeSignature(name = "achip_hash_states_update", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
+            MethodHandle hashStatesUpdate,
+            @NativeSignature(name = "achip_hash_states_digest", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, int.class})
+            MethodHandle hashStatesDigest,
+            @NativeSignature(name = "achip_hasher_create", returnType = MemorySegment.class, argumentTypes = {MemorySegment.class, int.class, long.class})
+            MethodHandle hasherCreate,
+            @NativeSignature(name = "achip_hasher_update", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, long.class})
+            MethodHandle hasherUpdate,
+            @NativeSignature(name = "achip_hasher_digest", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class})
+            MethodHandle hasherDigest,
+            @NativeSignature(name = "achip_hasher_reset", returnType = int.class, argumentTypes = {MemorySegment.class, long.class})
+            MethodHandle hasherReset,
+            @NativeSignature(name = "achip_hasher_destroy", returnType = int.class, argumentTypes = MemorySegment.class)
+            MethodHandle hasherDestroy,
             // batched, device-resident: (op, ctx, srcBase, srcOff*, srcLen*, dstBase, dstOff*, dstCap*, outLen*, status*, errOffset*, nBlocks)
             @NativeSignature(name = "achip_batch_host", returnType = int.class, argumentTypes = {int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class,
                     MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
@@ -662,6 +681,51 @@ public final class HipNative
     public static MethodHandle xxhash3Hash128Batch()
     {
         return HANDLES.xxhash3Hash128Batch();
+    }
+
+    public static MethodHandle hashStateSize()
+    {
+        return HANDLES.hashStateSize();
+    }
+
+    public static MethodHandle hashStatesReset()
+    {
+        return HANDLES.hashStatesReset();
+    }
+
+    public static MethodHandle hashStatesUpdate()
+    {
+        return HANDLES.hashStatesUpdate();
+    }
+
+    public static MethodHandle hashStatesDigest()
+    {
+        return HANDLES.hashStatesDigest();
+    }
+
+    public static MethodHandle hasherCreate()
+    {
+        return HANDLES.hasherCreate();
+    }
+
+    public static MethodHandle hasherUpdate()
+    {
+        return HANDLES.hasherUpdate();
+    }
+
+    public static MethodHandle hasherDigest()
+    {
+        return HANDLES.hasherDigest();
+    }
+
+    public static MethodHandle hasherReset()
+    {
+        return HANDLES.hasherReset();
+    }
+
+    public static MethodHandle hasherDestroy()
+    {
+        return HANDLES.hasherDestroy();
     }
 
     /** throws what {@link #toException} builds when {@code status} is negative */

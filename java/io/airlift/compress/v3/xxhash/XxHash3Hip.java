@@ -86,6 +86,18 @@ public final class XxHash3Hip
         HipNative.throwIfError(status, 0);
     }
 
+    /** {@code XxHash3Native.newHasher(seed)} on the GPU: the streaming form (update / updateLE / digest / reset / close). */
+    public Hasher newHasher(long seed)
+    {
+        return new Hasher(context, seed);
+    }
+
+    /** {@code XxHash3Native.newHasher128(seed)} on the GPU. */
+    public Hasher128 newHasher128(long seed)
+    {
+        return new Hasher128(context, seed);
+    }
+
     private static int invoke(MethodHandle handle, Object... arguments)
     {
         try {
@@ -93,6 +105,50 @@ public final class XxHash3Hip
         }
         catch (Throwable t) {
             throw new AssertionError("should not reach here", t);
+        }
+    }
+
+    /** The GPU sibling of {@code XxHash3Native.Hasher64Impl} ({@code XxHash3Native.java:220-344}). */
+    public static final class Hasher
+            extends XxHashHip.StreamingHasher<Hasher>
+    {
+        Hasher(HipNative.Context context, long seed)
+        {
+            super(context, XXH3_64, seed);
+        }
+
+        @Override
+        Hasher self()
+        {
+            return this;
+        }
+
+        public long digest()
+        {
+            long[] words = digestWords();
+            return words[0];
+        }
+    }
+
+    /** The GPU sibling of the 128-bit streaming hasher of {@code XxHash3Native}: same state and update as {@link Hasher}, another digest. */
+    public static final class Hasher128
+            extends XxHashHip.StreamingHasher<Hasher128>
+    {
+        Hasher128(HipNative.Context context, long seed)
+        {
+            super(context, XXH3_128, seed);
+        }
+
+        @Override
+        Hasher128 self()
+        {
+            return this;
+        }
+
+        public XxHash128 digest()
+        {
+            long[] words = digestWords();
+            return new XxHash128(words[0], words[1]);
         }
     }
 }
