@@ -1,4 +1,4 @@
-// achip_bounds.h -- what the eight compress ops ask of dstCap, stated once: the host functions achip_*_max_compressed_length (achip_abi.cpp) and the bound
+// achip_bounds.h -- what the eight compress ops ask of dstCap, stated once: the host functions achip_*_max_compressed_length (abi_context.cpp) and the bound
 // kernel of achip_compress_bound_batch (pack_outputs.hip) call these, so the two cannot drift.  Every helper takes a length n >= 0 and computes in 64 bits:
 // a result above INT32_MAX is the caller's to refuse (the host functions with their message, the kernel with a status).
 #pragma once

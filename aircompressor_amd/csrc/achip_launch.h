@@ -1,4 +1,4 @@
-// achip_launch.h -- the host launchers one translation unit calls in another: achip_abi.cpp calls them all, the container readers hand their
+// achip_launch.h -- the host launchers one translation unit calls in another: the host units (abi_*.cpp, over achip_host.h) call them all, the container readers hand their
 // listed blocks to launch_listed_decode (block_decode.cpp), which calls the block decoders, the Zstd decoder's two halves call each other, and
 // tools/hostemu calls them on the CPU.  Every file that defines or calls one includes this header.
 #pragma once
@@ -41,7 +41,7 @@ constexpr int64_t SNAPPY_RECORD_BYTES_PER_BLOCK = 131072, SNAPPY_RECORD_BYTES_PE
 hipError_t launch_lz4_mixed_groups(const BatchArgs& a, hipStream_t stream, int32_t* mixedGroups, int32_t minBlocks);
 hipError_t launch_lz4_sequence_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
 hipError_t launch_snappy_element_sample(const BatchArgs& a, hipStream_t stream, int32_t* stats, int32_t minBlocks, int32_t shortLimit);
-// the two families as one table (block_decode.cpp), a row per family -- 0 LZ4, 1 Snappy: the block API's policy (achip_abi.cpp launch_block_decode) and
+// the two families as one table (block_decode.cpp), a row per family -- 0 LZ4, 1 Snappy: the block API's policy (abi_dispatch.cpp launch_block_decode) and
 // the containers' (launch_listed_decode) read the same row
 struct BlockCodec {
     hipError_t (*rings)(const BatchArgs& a, hipStream_t stream, int groupSize, int ringClass, const int32_t* mixedGroups);

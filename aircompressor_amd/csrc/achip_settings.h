@@ -25,7 +25,7 @@ struct KernelSettings {
     int snappyTierWorkgroups = 256 * 5;  // the persistent grid where the unit count is known on the device only (no option; tools/hostemu makes it small)
 };
 
-// Everything achip_ctx_set_option writes.  A mixed batch's helper contexts take a copy of their caller's (achip_abi.cpp: mix_lane).
+// Everything achip_ctx_set_option writes.  A mixed batch's helper contexts take a copy of their caller's (abi_dispatch.cpp: mix_lane).
 struct Settings {
     int lz4dGroup = 0;       // ring decoder, lanes per block: 0 = by the batch size (4 from 32 768 blocks on -- the headline's form --, 16 below, 64 up to 4 096: lz4_ring_group_for), else 1 .. 64
     int snappydGroup = 0;    // likewise (64 up to 2 048 blocks, 16 below 16 384, 4 above: snappy_ring_group_for)
@@ -49,7 +49,7 @@ struct Settings {
     int zstdStreamBlocks = 65536;  // 128 KiB blocks a pass of the pipeline's multi-block stages has room for (0: multi-block frames take the one-kernel decoder); ~20 GB of scratch, allocated when a batch first holds such frames (halved as often as it takes when the device cannot give that)
     int ringPad = 80;        // 64 bytes of far-match staging + 16: consecutive blocks start on different LDS banks
     int scratchPoison = -1;
-    int autoRemember = 1;    // decompress.auto_remember (achip_abi.cpp: auto_remembered)
+    int autoRemember = 1;    // decompress.auto_remember (abi_dispatch.cpp: auto_remembered)
     int maxSrcLenHint = 0;
     int snappyFan = 1;     // snappy.compress.fan: 1 = the sub-blocks of buffers beyond 64 KiB are work units of their own (default), 0 = a buffer is one wavefront's work
     int mixConcurrent = 1;   // mixed batches: 1 = the three codec families side by side, each on a stream (and scratch) of its own -- a bucket's tail is a few long

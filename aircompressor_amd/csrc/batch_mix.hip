@@ -49,7 +49,7 @@ hipError_t launch_mix_scatter(const int32_t* perm, int32_t n, const int32_t* gOu
     return hipGetLastError();
 }
 
-// A copy by a kernel (the host-pointer pipeline, achip_abi.cpp: option host.blit): dst / src may be pinned HOST memory -- hipHostMalloc'ed slots are
+// A copy by a kernel (the host-pointer pipeline, abi_host_batch.cpp: option host.blit): dst / src may be pinned HOST memory -- hipHostMalloc'ed slots are
 // mapped into the device's address space --, 16 bytes per lane, a KiB per wavefront and instruction.  Why not hipMemcpyAsync: the pipeline's uploads and
 // downloads, on two streams, did not overlap on the link (the times of the two directions ADDED: profiles/r06_notes.md); a copy engine one way and a kernel
 // the other do.  bytes need not be a multiple of 16; dst and src are 16-byte aligned (slot offsets are multiples of 256).

@@ -15,7 +15,7 @@ namespace achip {
 template <int GS, int IN_RING, int OUT_RING, int GPL, bool HANDOVER = false, int PHASED = 0>
 __global__ __launch_bounds__(256) void lz4_decompress_rings_kernel(BatchArgs a, const int32_t* mixedGroups)
 {
-    // auto mode (achip_abi.cpp): both LZ4 decoders are launched, the probe's count of mixed 16-block groups picks one
+    // auto mode (abi_dispatch.cpp): both LZ4 decoders are launched, the probe's count of mixed 16-block groups picks one
     if (mixedGroups != nullptr && lz4_pick(mixedGroups, batch_count(a)) != LZ4_PICK_RINGS) {
         return;
     }

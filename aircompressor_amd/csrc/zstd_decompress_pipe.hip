@@ -2154,7 +2154,7 @@ hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, v
 // ================================================================================================================================
 // ONE LONG STREAM, A STEP AT A TIME (what ZstdInputStream does over ZstdIncrementalFrameDecompressor.java:44-72,216-234).
 // The batched calls above want whole frames resident, input and output; a frame of gigabytes (ZstdOutputStream writes ONE frame however long
-// the stream) then needs gigabytes.  Here the host (achip_abi.cpp: achip_zstdstream_decompress_*) cuts a frame into STEPS of whole blocks and
+// the stream) then needs gigabytes.  Here the host (abi_zstd_stream.cpp: achip_zstdstream_decompress_*) cuts a frame into STEPS of whole blocks and
 // the multi-block stages run on a step as if it were a frame -- the host puts a six-byte frame header in front of the step's blocks and
 // marks its last block "last" -- with what a block may inherit from the blocks before it carried from step to step in a device-side record:
 //   tables     a ghost slot 0 in front of the step's block slots receives the carried Huffman table and the three FSE tables; blocks

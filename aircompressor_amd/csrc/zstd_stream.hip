@@ -301,7 +301,7 @@ hipError_t launch_zstd_stream_compress(const BatchArgs& a, hipStream_t stream, v
 }
 
 // ---- the same writer, a chunk per launch (achip_zstdstream_compress_begin / _feed / _finish: a stream of any length in the 4 MiB the Java stream
-// buffers).  The host (achip_abi.cpp) keeps ZstdOutputStream's buffer on the device -- write() appends, a full buffer is flushed (compressIfNecessary
+// buffers).  The host (abi_zstd_stream.cpp) keeps ZstdOutputStream's buffer on the device -- write() appends, a full buffer is flushed (compressIfNecessary
 // :122-131), close() writes what is left -- and launches one step per writeChunk (:154-221); what a CompressionContext carries from chunk to chunk
 // lives in this record between the launches (the match finder's tables stay where they are, in the stream's slab): the repeat offsets, the window's
 // base, the Huffman tables a treeless block may reuse, the running XXH64 of the input. ----

@@ -250,77 +250,65 @@ def main():
 
 def stream_cases():
     """launch_zstd_stream_step under the emulator: frames cut into steps of a few blocks, tables / repeat offsets / window / checksum carried from
-    step to step; this script plays the host's part (achip_abi.cpp: achip_zstdstream_decompress_feed) -- the walk over the block headers, the
-    stand-in frame header in front of a step, the history kept behind the output.  Damaged frames: the blocks in front of the damage are
-    delivered, the first damaged block is where the oracle's decoder fails too."""
-    import struct
+    step to step; this script plays the host's part (abi_zstd_stream.cpp: achip_zstdstream_decompress_feed) -- the stand-in frame header in front of a step, the
+    history kept behind the output -- over the product's own walk (achip_zstd_frame.h: read_frame_header, list_step).  Damaged frames: the blocks in front of
+    the damage are delivered, the first damaged block is where the oracle's decoder fails too; where the WALK stops, the oracle's decoder must fail as well."""
     emu.emu_zstd_stream_carry_bytes.restype = ctypes.c_int64
     cb = emu.emu_zstd_stream_carry_bytes()
 
-    def decode(frame, step_blocks, window_cap=None):
-        """returns (plaintext delivered, index of the first bad block or None)"""
+    def decode(frame, step_blocks):
+        """returns (plaintext delivered, None or where the stream stopped: the index of the first bad block, "checksum", or the WALK's verdict -- "header", "window",
+        "block type", "truncated")"""
         assert frame[:4] == b"\x28\xb5\x2f\xfd"
-        fhd = frame[4]
-        single = (fhd & 0x20) != 0
-        cs = fhd >> 6
-        pos = 5
-        window = None
-        if not single:
-            wd = frame[pos]; pos += 1
-            base = 1 << (10 + (wd >> 3)); window = base + (base // 8) * (wd & 7)
-        n = (1 if single else 0) if cs == 0 else (1 << cs)
-        content = int.from_bytes(frame[pos:pos + n], "little") + (256 if cs == 1 else 0) if n else None
-        pos += n
-        look = window if content is None else (content if window is None else min(window, content))
-        if window_cap:
-            look = min(look, window_cap)
-        has_checksum = (fhd & 4) != 0
+        buf = np.frombuffer(frame, dtype=np.uint8).copy()
+        head = np.zeros(7, dtype=np.int64)
+        emu.emu_zstd_read_frame_header(P(buf[4:]), ctypes.c_int64(len(buf) - 4), P(head))
+        state, _, _, header_size, has_checksum, look, beyond_java = (int(x) for x in head)
+        if state != 0:
+            return b"", "truncated" if state == 1 else "header"
+        if look < 0:
+            return b"", "window"
+        pos = 4 + header_size
         carry = np.zeros(cb, dtype=np.uint8)
         emu.emu_zstd_stream_carry_init(P(carry))
         W = max(look, 1 << 16)
-        S = step_blocks * 131072
+        room = step_blocks + 15  # (a RAW / RLE block of up to 16 parts needs a step with room for it: the product's 32 always have, steps of 1, 3 or 4 get a longer one)
+        S = room * 131072
         hist = np.full(W + S + 64, 0xEE, dtype=np.uint8)
         hist_len = 0
         out = bytearray()
         block_no = 0
+        listed = np.zeros(4 * room, dtype=np.int64)
+        info = np.zeros(4, dtype=np.int64)
         while True:
-            blocks = []
-            closing = False
-            at = pos
-            while len(blocks) < step_blocks:
-                hd = int.from_bytes(frame[at:at + 3], "little")
-                typ, size = (hd >> 1) & 3, hd >> 3
-                st = 1 if typ == 1 else size
-                blocks.append(frame[at:at + 3 + st])
-                at += 3 + st
-                if hd & 1:
-                    closing = True
-                    break
+            n = emu.emu_zstd_list_step(P(buf[pos:]), ctypes.c_int64(len(buf) - pos), has_checksum, beyond_java, step_blocks, P(listed), P(info))
+            if n == 0 and int(info[3]) == 0:  # (nothing listed, nothing broken: truncated -- or a block of more parts than a step of step_blocks has room for)
+                n = emu.emu_zstd_list_step(P(buf[pos:]), ctypes.c_int64(len(buf) - pos), has_checksum, beyond_java, room, P(listed), P(info))
+            at, closing, expected, broken = (int(x) for x in info)
+            if n == 0:
+                return bytes(out), ("truncated", "block type", "window")[broken]
             body = bytearray(b"\x28\xb5\x2f\xfd\x20\x00")
-            for i, b in enumerate(blocks):
-                b = bytearray(b)
-                b[0] = (b[0] & 0xFE) | (1 if i == len(blocks) - 1 else 0)
-                body += b
+            for i in range(n):
+                hd, data_pos, data_len, _ = (int(x) for x in listed[4 * i:4 * i + 4])
+                body += ((hd & ~1) | (1 if i == n - 1 else 0)).to_bytes(3, "little") + frame[pos + data_pos:pos + data_pos + data_len]
             src = np.frombuffer(bytes(body), dtype=np.uint8).copy()
-            expected = int.from_bytes(frame[at:at + 4], "little") if closing and has_checksum else 0
             result = np.zeros(3, dtype=np.int32)
             base = hist[W - hist_len:]
-            rc = emu.emu_zstd_stream_step(P(carry), P(src), len(src), len(blocks), P(base), hist_len, hist_len + S, 1 if closing else 0, 1 if has_checksum else 0,
-                                          ctypes.c_uint32(expected), P(result))
+            rc = emu.emu_zstd_stream_step(P(carry), P(src), len(src), n, P(base), hist_len, hist_len + S, closing, has_checksum, ctypes.c_uint32(expected), P(result))
             assert rc == 0, rc
             good, produced, verdict = int(result[0]), int(result[1]), int(result[2])
             out += hist[W:W + produced].tobytes()
             keep = min(look, hist_len + produced)
             hist[W - keep:W] = hist[W + produced - keep:W + produced].copy()
             hist_len = keep
-            if good < len(blocks):
+            if good < n:
                 return bytes(out), block_no + good
-            block_no += len(blocks)
+            block_no += n
             if closing:
                 if has_checksum and verdict != 1:
                     return bytes(out), "checksum"
                 return bytes(out), None
-            pos = at
+            pos += at
 
     bad = 0
     plains = common.multi_block_plains()
@@ -349,10 +337,7 @@ def stream_cases():
             for _ in range(4 if "--quick" not in sys.argv else 1):
                 g = bytearray(f)
                 g[int(rng.integers(12, len(g) - 4))] ^= 1 << int(rng.integers(0, 8))
-                try:
-                    got, where = decode(bytes(g), 4)
-                except Exception as e:  # (a damaged block header makes this script's own walk run off the frame)
-                    continue
+                got, where = decode(bytes(g), 4)  # (a damaged block header: the walk's own verdict, which the oracle failing must bear out)
                 cases += 1
                 try:
                     ref_plain = o.decompress("zstd", bytes(g), len(p) + 1024)

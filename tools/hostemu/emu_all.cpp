@@ -17,7 +17,7 @@ void* all_mb_get(void*, int64_t bytes)
 }
 }  // namespace
 
-// the product's Zstd decode as achip_abi.cpp launches it: pipeline (multi-block stages included), then the one-kernel decoder over the fallback list
+// the product's Zstd decode as abi_dispatch.cpp launches it: pipeline (multi-block stages included), then the one-kernel decoder over the fallback list
 extern "C" int emu_zstd_full(const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, uint8_t* dstBase, const int64_t* dstOff, const int32_t* dstCap,
                              int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n, int32_t variant, int32_t passBlocks, int32_t* counters)
 {

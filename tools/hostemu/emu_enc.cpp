@@ -38,7 +38,7 @@ extern "C" int emu_encode(int op, const uint8_t* srcBase, const int64_t* srcOff,
         return achip::launch_snappy_compress(a, nullptr, option & 15, scratch.data(), (option & 16) == 0, ks);  // (option bit 4: the sub-blocks in turn, as until round 5)
     }
     if (op == 5 || op == 14) {
-        if (op == 5) a.ringPad = option == 1 ? 1 : (option == 3 ? 3 : 0);  // (what achip_abi.cpp does: the one-kernel path reads the variant from the spare field)
+        if (op == 5) a.ringPad = option == 1 ? 1 : (option == 3 ? 3 : 0);  // (what abi_dispatch.cpp's launch_op does: the one-kernel path reads the variant from the spare field)
         scratch.assign((size_t)achip::zstd_compress_scratch_bytes(n), 0xCD);
         return op == 5 ? achip::launch_zstd_compress(a, nullptr, scratch.data(), (int64_t)scratch.size(), option) : achip::launch_zstd_stream_compress(a, nullptr, scratch.data(), option);
     }
@@ -59,7 +59,7 @@ extern "C" int emu_encode(int op, const uint8_t* srcBase, const int64_t* srcOff,
     return -1;
 }
 
-// The stream writer a chunk per launch (zstd_stream.hip: zstd_ostream_step_kernel), driven the way achip_abi.cpp's achip_zstdstream_compress_feed /
+// The stream writer a chunk per launch (zstd_stream.hip: zstd_ostream_step_kernel), driven the way abi_zstd_stream.cpp's achip_zstdstream_compress_feed /
 // _finish drive it: ZstdOutputStream's buffer of 4 MiB, a step per writeChunk, the buffer moved down behind a flush.  `piece`: bytes per write() call.
 extern "C" int64_t emu_zstd_ostream(const uint8_t* in, int64_t n, uint8_t* out, int64_t cap, int32_t piece)
 {

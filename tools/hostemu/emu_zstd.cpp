@@ -6,6 +6,7 @@
 thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
 extern "C" { long long achip_emu_counters[16]; }
 #include "../../aircompressor_amd/csrc/zstd_decompress_pipe.hip"
+#include "../../aircompressor_amd/csrc/achip_zstd_frame.h"
 #include <vector>
 namespace achip {
 namespace {
@@ -71,8 +72,29 @@ void* emu_mb_get(void*, int64_t bytes)
 }
 }  // namespace
 
-// a stream decoded a step at a time (launch_zstd_stream_step): the caller (check_zstd.py --stream) plays the host's part -- the walk over the
-// block headers, the stand-in frame header, the history
+// a stream decoded a step at a time (launch_zstd_stream_step): the caller (check_zstd.py --stream) plays the host's part -- the stand-in frame header, the
+// history -- with the product's own walk over frame header and block headers (achip_zstd_frame.h, as abi_zstd_stream.cpp calls it)
+// out: state detail offset headerSize hasChecksum lookBack windowBeyondJava (the look-back for a reader that keeps at most 128 MiB, as the product's does)
+extern "C" void emu_zstd_read_frame_header(const uint8_t* p, int64_t have, int64_t* out)
+{
+    const achip::zframe::FrameHeader h = achip::zframe::read_frame_header(p, have);
+    const achip::zframe::FrameWindow w = achip::zframe::frame_window(h, 128LL << 20);
+    const int64_t v[7] = {h.state, h.detail, h.offset, h.headerSize, h.hasChecksum, w.lookBack, w.windowBeyondJava};
+    memcpy(out, v, sizeof(v));
+}
+// blocks: header dataPos dataLen streamBytes per listed block; info: bytes closing expected broken; returns the number of blocks
+extern "C" int emu_zstd_list_step(const uint8_t* p, int64_t have, int32_t hasChecksum, int32_t windowBeyondJava, int32_t maxBlocks, int64_t* blocks, int64_t* info)
+{
+    const achip::zframe::Step s = achip::zframe::list_step(p, have, hasChecksum != 0, windowBeyondJava != 0, maxBlocks);
+    for (size_t i = 0; i < s.blocks.size(); i++) {
+        const achip::zframe::StepBlock& b = s.blocks[i];
+        const int64_t v[4] = {b.header, (int64_t)b.dataPos, b.dataLen, b.streamBytes};
+        memcpy(blocks + 4 * i, v, sizeof(v));
+    }
+    const int64_t v[4] = {s.bytes, s.closing, s.expected, s.broken};
+    memcpy(info, v, sizeof(v));
+    return (int)s.blocks.size();
+}
 extern "C" int64_t emu_zstd_stream_carry_bytes() { return achip::zstd_stream_carry_bytes(); }
 extern "C" void emu_zstd_stream_carry_init(void* carry) { achip::zstd_stream_carry_init(carry); }
 extern "C" int emu_zstd_stream_step(void* carry, const uint8_t* src, int32_t srcLen, int32_t blocks, uint8_t* out, int32_t startPos, int32_t outLimit, int32_t closing,
