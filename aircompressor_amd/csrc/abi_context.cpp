@@ -386,6 +386,12 @@ int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name)
         const int word = k == "zstd.decompress.multiblock_items" ? 40 : (k == "zstd.decompress.multiblock_blocks" ? 41 : 42);
         return read_scratch(ctx, 4 * word, &v, 1) ? v : -1;
     }
+    if (k == "zstd.decompress.long_items") {
+        // the last Zstd decode's last tile: items the sequence stage counted as long-sequence items (what the execute stage's per-item choice goes by)
+        if (ctx->lastZstddBlocks <= 0 || ctx->scratch.get() == nullptr || ctx->lastZstddVariant == 0) return -1;
+        int32_t v = 0;
+        return read_scratch(ctx, 4 * 18, &v, 1) ? v : -1;
+    }
     const std::string prefix = "zstd.decompress.fallback_";
     if (k.compare(0, prefix.size(), prefix) == 0) {
         // "items": all items handed to the one-kernel decoder; "stage1".."stage5": by the stage that handed them over

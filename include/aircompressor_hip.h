@@ -193,6 +193,9 @@ int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value);
  * "zstd.decompress.multiblock_items" / "_blocks" / "_fast_items": items of the last Zstd decode that hold one frame of several blocks
  *   (ZstdOutputStream's output; ZstdFrameCompressor's and libzstd's beyond 128 KiB), their blocks, and how many of them the pipeline's
  *   multi-block stages finished (the rest went to the one-kernel decoder); option "zstd.decompress.stream_blocks" sizes those stages;
+ * "zstd.decompress.long_items": items of the last Zstd decode's last tile that the pipeline's sequence stage counted as long-sequence
+ *   items (capacity >= 80 bytes per sequence): a tile of more than 16 384 items with at least 24 576 of them runs those on the ring executor,
+ *   everything else runs on the record executor (-1: the one-kernel decoder ran);
  * "lz4.decompress.mixed_groups": auto mode's count of mixed 16-block groups of the last LZ4 / Snappy decode (-1: no probe ran);
  * "decompress.choice": the decoder auto mode ran (0 LDS rings, 3 two passes; -1: no probe ran).  DESIGN.md 8b lists every option and
  *   statistic. */

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests import common, oracle_lib
+from tests import zstd_frame_cases as zc
 from tests.oracle_lib import OracleError
 
 pytestmark = pytest.mark.gpu
@@ -17,12 +18,17 @@ def gb():
     return GpuBatch(0)
 
 
-@pytest.fixture(scope="module", params=[1, 0], ids=["pipeline", "one-kernel"])
+@pytest.fixture(scope="module", params=[(1, None), (0, None), (1, 0)], ids=["pipeline", "one-kernel", "pipeline-rings"])
 def gbd(request):
-    """decoder under test: the five-stage pipeline (default) and the one-kernel decoder it falls back to"""
+    """decoder under test: the five-stage pipeline (default: batches of this module's sizes run its record executor), the one-kernel decoder it falls back to,
+    and the pipeline with every item on its ring executor (zstd.decompress.exec 0: what the default picks for long-sequence items of large batches)"""
     from tests.gpu_harness import GpuBatch
-    g = GpuBatch(0, options={"zstd.decompress.variant": request.param})
-    g.variant = request.param
+    variant, exec_mode = request.param
+    options = {"zstd.decompress.variant": variant}
+    if exec_mode is not None:
+        options["zstd.decompress.exec"] = exec_mode
+    g = GpuBatch(0, options=options)
+    g.variant = variant
     return g
 
 
@@ -346,6 +352,161 @@ def test_pipeline_takes_java_encoded_frames(gbd, o):
     assert status[1] == est and (est == 0 or err[1] == eoff)
     if gbd.variant == 1:
         assert gbd.codec.native.get_stat("zstd.decompress.fallback_items") <= 1
+
+
+# ---- the execute stage's two kernels: the case catalog of tests/zstd_frame_cases.py, and tiles large enough for the per-item choice ----
+DEFAULT_RING_PAD = 80  # (the library's default of decompress.ring_pad, restored by the test that changes it)
+
+
+@pytest.fixture(scope="module")
+def frame_cases(o):
+    """(cases, expected): the hand frames of the catalog and encoders' frames next to them (the oracle's and libzstd's, text and fragments data, 300 bytes to
+    128 KiB: Huffman literals from the arena, FSE tables); expected[pad][i] is the oracle's (status, offset, bytes) for case i at its capacity + pad"""
+    text = b"".join(d for _, d, _ in common.corpus_sample()[:3])
+    plains = zc.encoder_plains(text, common.synthetic_blocks(21, 1, 131072)[0])
+    cases = zc.catalog() + zc.encoder_cases(plains, [("oracle", lambda b: o.compress("zstd", b)), ("libzstd-3", lambda b: zstd_frames([b], 3)[0])])
+    expected = {pad: [_expect(o, c.frame, c.capacity(pad)) for c in cases] for pad in (0, 64)}
+    for pad in (0, 64):
+        for c, (est, _, eout) in zip(cases, expected[pad]):
+            assert (est != 0) == c.malformed and (c.malformed or eout == c.plain), c.name  # (the catalog's own verdict is the oracle's: also tests/test_zstd_frame_cases.py)
+    return cases, expected
+
+
+def _run_catalog(g, cases, expected, pad):
+    """the catalog through g at capacity + pad: status, offset and bytes as the oracle has them; exactly the malformed cases handed to the one-kernel decoder,
+    all of them by the execute stage (a valid frame that leaves the fast path tests nothing here)"""
+    outs, status, err = g.run(OP_ZSTD_DECOMPRESS, [c.frame for c in cases], [c.capacity(pad) for c in cases], unaligned=(pad == 0))
+    for i, (c, (est, eoff, eout)) in enumerate(zip(cases, expected[pad])):
+        assert status[i] == est, "%s: gpu status %d oracle %d (gpu offset %d, oracle %d)" % (c.name, status[i], est, err[i], eoff)
+        if est == 0:
+            assert len(outs[i]) == len(eout) and outs[i] == eout, c.name
+        else:
+            assert err[i] == eoff, "%s: gpu offset %d oracle %d" % (c.name, err[i], eoff)
+    stat = g.codec.native.get_stat
+    stages = [stat("zstd.decompress.fallback_stage%d" % k) for k in range(1, 7)]
+    n_bad = sum(1 for c in cases if c.malformed)
+    assert stat("zstd.decompress.fallback_items") == n_bad, stages
+    assert stat("zstd.decompress.fallback_stage4") == sum(1 for c in cases if c.stage == 4) == n_bad, stages
+
+
+@pytest.mark.parametrize("exec_mode", [0, 1], ids=["ring-executor", "record-executor"])
+def test_catalog_under_each_executor(o, frame_cases, exec_mode):
+    """zstd.decompress.exec 0 / 1: every item of the catalog on the ring executor (zstd_pipe_execute_kernel) / on the record executor, at exact capacities with
+    unaligned outputs and with 64 bytes of slack"""
+    from tests.gpu_harness import GpuBatch
+    cases, expected = frame_cases
+    g = GpuBatch(0, options={"zstd.decompress.variant": 1, "zstd.decompress.exec": exec_mode})
+    _run_catalog(g, cases, expected, 0)
+    _run_catalog(g, cases, expected, 64)
+
+
+def test_catalog_on_the_ring_executor_without_a_staging_area(o, frame_cases):
+    """decompress.ring_pad 0: the ring executor gets no LDS staging area for far matches (it has one from 64 bytes of pad on; the default is 80) and reads them
+    from its flushed output piece by piece -- the other branch of achip_rings.h copy_match"""
+    from tests.gpu_harness import GpuBatch
+    cases, expected = frame_cases
+    g = GpuBatch(0, options={"zstd.decompress.variant": 1, "zstd.decompress.exec": 0})
+    try:
+        g.set_option("decompress.ring_pad", 0)
+        _run_catalog(g, cases, expected, 0)
+        _run_catalog(g, cases, expected, 64)
+    finally:
+        g.set_option("decompress.ring_pad", DEFAULT_RING_PAD)
+
+
+LARGE_TILE = 32768
+
+
+@pytest.fixture(scope="module")
+def tile_pools(frame_cases):
+    """the catalog's small cases (at most 4 KiB of output, malformed ones and both checksum settings among them) as (frame, capacity, expected, counted as long),
+    apart by what the sequence stage counts them as: an item is counted as a long-sequence item when it HAS sequences and its capacity is at least 80 bytes a sequence"""
+    cases, expected = frame_cases
+    K = zc.kernel_constants()
+    assert LARGE_TILE > K["ALL_RECORDS_MAX_ITEMS"]  # (a tile of at most that many items runs the record executor whatever it holds)
+    pools = {True: [], False: []}
+    far = 0
+    for c, e in zip(cases, expected[0]):
+        if c.cap <= 4096:
+            pools[zc.counted_long(c.cap, c.nseq, K)].append((c.frame, c.cap, e, c.malformed))
+            far += "far=prefetch-lane>0" in c.tags and zc.counted_long(c.cap, c.nseq, K)
+    assert len(pools[True]) + len(pools[False]) <= 400 and min(len(pools[True]), len(pools[False])) >= 20
+    assert sum(1 for p in pools[True] if p[3]) >= 3 and sum(1 for p in pools[False] if p[3]) >= 3
+    assert far >= 2  # (long-sequence frames whose far matches the ring executor requests ahead, from lanes other than a group's first)
+    return pools, K
+
+
+def _large_tile(pools, n_long, extra=()):
+    """LARGE_TILE items, n_long of them from the long pool, spread evenly among the others item by item (every workgroup of either execute kernel holds both
+    kinds); extra: items that take the place of every 32nd one"""
+    items = []
+    taken = {True: 0, False: 0}
+    for i in range(LARGE_TILE):
+        long = (i + 1) * n_long // LARGE_TILE != i * n_long // LARGE_TILE
+        items.append(pools[long][taken[long] % len(pools[long])])
+        taken[long] += 1
+    for k, e in enumerate(extra):
+        items[32 * k + 5] = e
+    return items
+
+
+def _run_large_tile(g, items, K):
+    """runs the items; every one as the oracle has it, exactly the malformed ones handed to the one-kernel decoder; returns the tile's long-item count as the
+    library reports it, after comparing it with the count made here from the frames' sequence counts and capacities"""
+    outs, status, err = g.run(OP_ZSTD_DECOMPRESS, [it[0] for it in items], [it[1] for it in items], unaligned=True)
+    for i, (frame, cap, (est, eoff, eout), malformed) in enumerate(items):
+        assert status[i] == est, "item %d: gpu status %d oracle %d (gpu offset %d, oracle %d)" % (i, status[i], est, err[i], eoff)
+        if est == 0:
+            assert len(outs[i]) == len(eout) and outs[i] == eout, "item %d" % i
+        else:
+            assert err[i] == eoff, "item %d: gpu offset %d oracle %d" % (i, err[i], eoff)
+    stat = g.codec.native.get_stat
+    assert stat("zstd.decompress.fallback_items") == sum(1 for it in items if it[3]), [stat("zstd.decompress.fallback_stage%d" % k) for k in range(1, 7)]
+    want_long = sum(1 for frame, cap, _, _ in items if zc.counted_long(cap, zc.sequence_count(frame), K))
+    assert stat("zstd.decompress.long_items") == want_long
+    return want_long
+
+
+def test_large_tile_splits_its_items_between_the_executors(o, tile_pools):
+    """No option set: a tile of 32 768 items (the sequence stage in full 64-item workgroups) with 26 000 long-sequence items among 6 768 others runs the former on
+    the ring executor and the latter on the record executor; with 20 000 -- fewer than the rule asks for -- all on the record executor.  zstd.decompress.long_items
+    says which of the two happened."""
+    from tests.gpu_harness import GpuBatch
+    pools, K = tile_pools
+    g = GpuBatch(0)
+    n = _run_large_tile(g, _large_tile(pools, 26000), K)
+    assert n == 26000 >= K["RINGS_MIN_LONG_ITEMS"] and LARGE_TILE - n >= 4096
+    n = _run_large_tile(g, _large_tile(pools, 20000), K)
+    assert n == 20000 < K["RINGS_MIN_LONG_ITEMS"]
+
+
+@pytest.mark.parametrize("waves", [1, 2, 4])
+def test_large_tile_sequence_stage_wavefronts_per_workgroup(o, tile_pools, waves):
+    """zstd.decompress.seq_waves on a tile whose sequence-stage workgroups are full (64 items each: tiles of 16 384 items and more), both executors behind it"""
+    from tests.gpu_harness import GpuBatch
+    pools, K = tile_pools
+    g = GpuBatch(0)
+    try:
+        g.set_option("zstd.decompress.seq_waves", waves)
+        assert _run_large_tile(g, _large_tile(pools, 26000), K) >= K["RINGS_MIN_LONG_ITEMS"]
+    finally:
+        g.set_option("zstd.decompress.seq_waves", DEFAULT_SEQ_WAVES)
+
+
+def test_capacity_stands_in_for_size_in_a_large_tile(o, frame_cases, tile_pools):
+    """The per-item rule sees the capacity, not the output size: text frames (a sequence every 10 .. 15 bytes) handed over with 100 times the capacity they need
+    count as long-sequence items and, in a tile with enough of those, run on the ring executor -- plaintext and the exact length all the same"""
+    from tests.gpu_harness import GpuBatch
+    cases, expected = frame_cases
+    pools, K = tile_pools
+    text = [(c.frame, 100 * len(c.plain), (0, 0, c.plain), False) for c in cases if "-text-" in c.name and len(c.plain) <= 2500]
+    assert len(text) == 6
+    for frame, cap, _, _ in text:
+        n = zc.sequence_count(frame)
+        assert not zc.counted_long(cap // 100, n, K) and zc.counted_long(cap, n, K)
+    g = GpuBatch(0)
+    items = _large_tile(pools, 26000, extra=[text[k % len(text)] for k in range(LARGE_TILE // 32)])
+    assert _run_large_tile(g, items, K) >= K["RINGS_MIN_LONG_ITEMS"]
 
 
 # ---- encoder (level 3), rows a11-a14 -------------------------------------------------------------------------

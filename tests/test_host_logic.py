@@ -162,7 +162,9 @@ def test_zstd_pipeline_kernels_on_the_cpu():
     """The Zstd decode pipeline (parse / literals / sequences / execute / checksum and the multi-block stages: walk, per-block parse, tables
     fetched through links, repeat-offset sentinels, one window per frame) under tools/hostemu with quad-level rendezvous: frames of the
     oracle's encoder and of libzstd, single-block and multi-block, at two pass sizes, must decode to the plaintext on the fast path; damaged
-    multi-block frames must either leave the fast path or decode to exactly what the oracle's decoder returns."""
+    multi-block frames must either leave the fast path or decode to exactly what the oracle's decoder returns.  The case catalog of
+    tests/zstd_frame_cases.py (hand-built frames at the execute stage's edges, valid and malformed, and encoders' frames) runs under BOTH execute
+    stages: the ring executor (exec mode 0, with and without its staging area for far matches) and the record executor (mode 1)."""
     import shutil
     import sys
     import pytest
@@ -173,12 +175,13 @@ def test_zstd_pipeline_kernels_on_the_cpu():
     subprocess.run([clang, "-O1", "-std=c++17", "-fPIC", "-shared", "-I", emu_dir, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"),
                     "-o", os.path.join(emu_dir, "libemu_zstd.so"), os.path.join(emu_dir, "emu_zstd.cpp")], check=True)
     jobs = [subprocess.Popen([sys.executable, os.path.join(emu_dir, "check_zstd.py"), "--quick", "--part", part], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
-            for part in ("single", "multi", "damaged")]  # (side by side)
+            for part in ("single", "multi", "damaged", "catalog")]  # (side by side)
     outs = [j.communicate()[0] for j in jobs]
     assert all(j.returncode == 0 for j in jobs), "\n".join(outs)
     out = "\n".join(outs)
     lines = [l for l in out.splitlines() if "mismatches" in l]
-    assert len(lines) == 4 and all(" 0 mismatches" in l for l in lines), out
+    assert len(lines) == 5 and all(" 0 mismatches" in l for l in lines), out
+    assert out.count("catalog, ring executor") == 4 and out.count("catalog, record executor") == 2, out  # (two capacities each)
     assert "fast 18, fallback list []" in out and "fast 17, fallback list [17]" in out, out  # (the smallest passes: the frame of ~260 short blocks has no room)
 
 

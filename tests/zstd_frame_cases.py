@@ -1,0 +1,431 @@
+"""Hand-built Zstd frames that aim at the pipeline's execute stage (zstd_decompress_pipe.hip: the ring executor zstd_pipe_execute_kernel and the record
+executor zstd_pipe_execute2_kernel), shared by the emulator check (tools/hostemu/check_zstd.py --part catalog) and the GPU tests (tests/test_gpu_zstd.py).
+Imports only numpy (and the standard library).
+
+build_frame() writes a single-segment frame of one compressed block: raw literals, the three sequence tables in RLE mode, a bit stream of extra bits only.
+Its plaintext comes from executing the sequences in plain Python (RFC 8878 3.1.1.4 / 3.1.1.5) -- not from the oracle, not from any library; the CPU suite
+checks that the oracle agrees (tests/test_zstd_frame_cases.py).
+
+What the format allows such a frame: with RLE tables all sequences of a frame share their literal-length, match-length and offset CODE, so a frame's
+values vary within one code's range, and the first record must find its match inside its own literals (offset <= ll).  Two consequences:
+  * ll = 0 (code 0, no extra bits) makes every record of the frame ll = 0, and the first one has nothing to copy from: ll = 0, and the repeat-offset codes
+    with ll = 0, occur in hand frames only as frames that are malformed at the first record.  Valid ll = 0 records come with the encoders' frames.
+  * a match that starts before the output (of > output + ll) can only be built in the first or the second record: an offset code spans a factor of two, a
+    literal-length code at most a factor of two, so from the third record on output + ll exceeds every offset of the code the first record could use.  The
+    records 4 and 5 (the last lane of the ring executor's first step, the first of its second) fail through the executor's other two checks instead:
+    ll beyond the literals left, and a match that runs beyond the capacity."""
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# RFC 8878 3.1.1.3.2.1.1: code -> baseline, extra bits
+LL_BASE = list(range(16)) + [16, 18, 20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536]
+LL_BITS = [0] * 16 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
+ML_BASE = list(range(3, 35)) + [35, 37, 39, 41, 43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051, 4099, 8195, 16387, 32771, 65539]
+ML_BITS = [0] * 32 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
+MAX_BLOCK = 131072
+
+
+def _code(base, bits, v):
+    c = max(i for i in range(len(base)) if base[i] <= v)
+    assert v - base[c] < (1 << bits[c]), v
+    return c
+
+
+def ll_code(v):
+    return _code(LL_BASE, LL_BITS, v)
+
+
+def ml_code(v):
+    return _code(ML_BASE, ML_BITS, v)
+
+
+def of_value(off):
+    """the coded offset value of a sequence's third field: off > 0 is a real offset, -1 / -2 / -3 the repeat-offset values 1 / 2 / 3"""
+    return off + 3 if off > 0 else -off
+
+
+M64 = (1 << 64) - 1
+_P1, _P2, _P3, _P4, _P5 = 0x9E3779B185EBCA87, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0x85EBCA77C2B2AE63, 0x27D4EB2F165667C5
+
+
+def _rotl(x, r):
+    return ((x << r) | (x >> (64 - r))) & M64
+
+
+def xxh64(data, seed=0):
+    """XXH64 in plain Python (the frame's content checksum is its low 32 bits)"""
+    n = len(data)
+    rnd = lambda acc, w: (_rotl((acc + w * _P2) & M64, 31) * _P1) & M64
+    pos = 0
+    if n >= 32:
+        words = np.frombuffer(data[:n // 32 * 32], dtype="<u8").reshape(-1, 4).tolist()
+        v = [(seed + _P1 + _P2) & M64, (seed + _P2) & M64, seed, (seed - _P1) & M64]
+        for row in words:
+            v = [rnd(v[0], row[0]), rnd(v[1], row[1]), rnd(v[2], row[2]), rnd(v[3], row[3])]
+        h = (_rotl(v[0], 1) + _rotl(v[1], 7) + _rotl(v[2], 12) + _rotl(v[3], 18)) & M64
+        for x in v:
+            h = ((h ^ rnd(0, x)) * _P1 + _P4) & M64
+        pos = n // 32 * 32
+    else:
+        h = (seed + _P5) & M64
+    h = (h + n) & M64
+    while pos + 8 <= n:
+        h = (_rotl(h ^ rnd(0, int.from_bytes(data[pos:pos + 8], "little")), 27) * _P1 + _P4) & M64
+        pos += 8
+    if pos + 4 <= n:
+        h = (_rotl(h ^ (int.from_bytes(data[pos:pos + 4], "little") * _P1 & M64), 23) * _P2 + _P3) & M64
+        pos += 4
+    while pos < n:
+        h = (_rotl(h ^ (data[pos] * _P5 & M64), 11) * _P1) & M64
+        pos += 1
+    h = ((h ^ (h >> 33)) * _P2) & M64
+    h = ((h ^ (h >> 29)) * _P3) & M64
+    return h ^ (h >> 32)
+
+
+def execute(literals, sequences):
+    """the plaintext of a block: (bytes or None where a record is malformed, the resolved offsets, the record that failed or -1).  Repeat-offset history as in
+    RFC 8878 3.1.1.5, starting from 1, 4, 8."""
+    out = bytearray()
+    lp = 0
+    rep = [1, 4, 8]
+    offs = []
+    for k, (ll, ml, off) in enumerate(sequences):
+        if off < 0:
+            idx = -off - 1 + (1 if ll == 0 else 0)  # 0: the last offset; 1, 2: the ones before; 3: the last offset - 1
+            if idx == 0:
+                o = rep[0]
+            else:
+                o = rep[0] - 1 if idx == 3 else rep[idx]
+                o = o if o != 0 else 1
+                if idx != 1:
+                    rep[2] = rep[1]
+                rep[1] = rep[0]
+                rep[0] = o
+        else:
+            o = off
+            rep = [o, rep[0], rep[1]]
+        offs.append(o)
+        if lp + ll > len(literals):
+            return None, offs, k
+        out += literals[lp:lp + ll]
+        lp += ll
+        if o > len(out):
+            return None, offs, k
+        if o >= ml:
+            start = len(out) - o
+            out += out[start:start + ml]
+        else:
+            period = bytes(out[len(out) - o:])
+            out += (period * (ml // o + 1))[:ml]
+    out += literals[lp:]
+    return bytes(out), offs, -1
+
+
+def build_frame(literals, sequences, *, checksum=False, last_literals=None, content_size=None):
+    """(frame, plaintext).  sequences: [(ll, ml, off)], off > 0 a real offset, -1 / -2 / -3 the repeat-offset values; all of them must share their three
+    codes.  last_literals: how many of `literals` the sequences leave over (checked; None: not checked -- a frame that is malformed on purpose).
+    content_size: the frame header's field where it is not the plaintext's length (malformed frames: what the lengths add up to).  The plaintext is
+    None where executing the sequences fails."""
+    literals = bytes(literals)
+    plain, _, _ = execute(literals, sequences)
+    if last_literals is not None:
+        assert len(literals) - sum(s[0] for s in sequences) == last_literals
+    if content_size is None:
+        content_size = len(plain) if plain is not None else sum(s[0] + s[1] for s in sequences) + max(0, len(literals) - sum(s[0] for s in sequences))
+    n = len(literals)
+    if n < 32:
+        block = bytes([n << 3])
+    elif n < 4096:
+        block = ((n << 4) | 4).to_bytes(2, "little")
+    else:
+        block = ((n << 4) | 12).to_bytes(3, "little")
+    block += literals
+    ns = len(sequences)
+    if ns == 0:
+        block += b"\x00"
+    else:
+        assert ns < 0x7F00
+        block += bytes([ns]) if ns < 128 else bytes([128 + (ns >> 8), ns & 255])
+        cl, cm, co = ll_code(sequences[0][0]), ml_code(sequences[0][1]), of_value(sequences[0][2]).bit_length() - 1
+        block += bytes([0x54, cl, co, cm])
+        acc = nbits = 0
+        for ll, ml, off in reversed(sequences):  # written last-first: LL, ML, OF bits, so that the reader meets OF, ML, LL
+            v = of_value(off)
+            assert ll_code(ll) == cl and ml_code(ml) == cm and v.bit_length() - 1 == co, "a frame's sequences share their codes"
+            for value, width in ((ll - LL_BASE[cl], LL_BITS[cl]), (ml - ML_BASE[cm], ML_BITS[cm]), (v - (1 << co), co)):
+                acc |= value << nbits
+                nbits += width
+        acc |= 1 << nbits
+        block += acc.to_bytes((nbits + 8) // 8, "little")
+    assert 3 <= len(block) <= MAX_BLOCK
+    if content_size < 256:
+        head = bytes([0x20 | (4 if checksum else 0), content_size])
+    elif content_size < 65536 + 256:
+        head = bytes([0x60 | (4 if checksum else 0)]) + (content_size - 256).to_bytes(2, "little")
+    else:
+        head = bytes([0xA0 | (4 if checksum else 0)]) + content_size.to_bytes(4, "little")
+    frame = b"\x28\xb5\x2f\xfd" + head + ((len(block) << 3) | 5).to_bytes(3, "little") + block
+    if checksum:
+        frame += (xxh64(plain if plain is not None else b"") & 0xFFFFFFFF).to_bytes(4, "little")
+    return frame, plain
+
+
+def sequence_count(frame):
+    """the sequence count of a single-segment or windowed frame's first block, read from its literals and sequences headers (None: not one compressed block)"""
+    fhd = frame[4]
+    pos = 5 + (0 if fhd & 0x20 else 1) + ((1 if fhd & 0x20 else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6)) + (0 if fhd & 3 == 0 else 1 << ((fhd & 3) - 1))
+    h = int.from_bytes(frame[pos:pos + 3], "little")
+    if (h >> 1) & 3 != 2 or not h & 1:
+        return None
+    pos += 3
+    b0 = frame[pos]
+    kind, form = b0 & 3, (b0 >> 2) & 3
+    if kind < 2:
+        nbytes = 1 if form in (0, 2) else (2 if form == 1 else 3)
+        size = int.from_bytes(frame[pos:pos + nbytes], "little") >> (3 if nbytes == 1 else 4)
+        pos += nbytes + (size if kind == 0 else 1)
+    else:
+        nbytes = 3 if form < 2 else (4 if form == 2 else 5)
+        hh = int.from_bytes(frame[pos:pos + 5], "little")
+        comp = (hh >> 14) & 0x3FF if nbytes == 3 else ((hh >> 18) & 0x3FFF if nbytes == 4 else (hh >> 22) & 0x3FFFF)
+        pos += nbytes + comp
+    n = frame[pos]
+    if n == 255:
+        return int.from_bytes(frame[pos + 1:pos + 3], "little") + 0x7F00
+    return n if n < 128 else ((n - 128) << 8) + frame[pos + 1]
+
+
+def kernel_constants():
+    """the execute stage's geometry, read from the kernel sources: the ring executor's instantiation and what achip_rings.h derives from it, the record
+    executor's window, and the rule that picks between the two"""
+    csrc = os.path.join(ROOT, "aircompressor_amd", "csrc")
+    pipe = open(os.path.join(csrc, "zstd_decompress_pipe.hip")).read()
+    rings = open(os.path.join(csrc, "achip_rings.h")).read()
+    sx2 = open(os.path.join(csrc, "achip_seqexec2.h")).read()
+    m = re.search(r"constexpr int GS = (\d+), IN_RING = (\d+), OUT_RING = (\d+);", pipe)
+    env = {"GS": int(m.group(1)), "IN_RING": int(m.group(2)), "OUT_RING": int(m.group(3)), "GPL": 1}
+    for name in ("CHUNK", "LDS_REACH"):
+        expr = re.search(r"static constexpr int %s = ([A-Z_0-9 *+\-]+);" % name, rings).group(1)
+        env[name] = int(eval(expr, {"__builtins__": {}}, dict(env)))
+    env["WIN"] = int(re.search(r"constexpr int WIN_DEFAULT = (\d+);", sx2).group(1))
+    env["LONG_BYTES_PER_SEQ"] = int(re.search(r"bool long_sequences\(int32_t capacity, int32_t nSeq\) \{ return \(int64_t\)capacity >= (\d+)LL \*", pipe).group(1))
+    env["RINGS_MIN_LONG_ITEMS"] = int(re.search(r"constexpr int32_t RINGS_MIN_LONG_ITEMS = (\d+);", pipe).group(1))
+    env["ALL_RECORDS_MAX_ITEMS"] = int(re.search(r"constexpr int32_t ZSTD_EXEC_ALL_RECORDS_MAX_ITEMS = (\d+);", pipe).group(1))
+    return env
+
+
+class Case:
+    """one catalog entry: a frame with the capacity it is decoded at.  malformed: the decoder must refuse it (at the execute stage: `stage` is 4); plain: the
+    expected bytes of a valid one; nseq: its sequence count; tags: the edges it covers, from the generator's own records"""
+
+    def __init__(self, name, frame, plain, cap, nseq, malformed=False, stage=None, tags=(), checksum=False, slack=True):
+        self.name, self.frame, self.plain, self.cap, self.nseq = name, frame, plain, cap, nseq
+        self.malformed, self.stage, self.tags, self.checksum = malformed, stage, set(tags), checksum
+        self.slack = slack and not malformed  # (a case that is malformed by its capacity keeps that capacity in the runs that add slack)
+
+    def capacity(self, pad):
+        return self.cap + (pad if self.slack else 0)
+
+
+def is_long(cap, nseq, K):
+    """the execute stage's rule for an item (zp::long_sequences): the capacity stands in for the output size"""
+    return cap >= K["LONG_BYTES_PER_SEQ"] * max(nseq, 1)
+
+
+def counted_long(cap, nseq, K):
+    """... and what the sequence stage adds to the tile's count of such items: only an item that has sequences passes through it"""
+    return nseq > 0 and is_long(cap, nseq, K)
+
+
+# the edge values the catalog must hold (the self-check counts them from the cases' tags)
+SEQ_COUNTS = (0, 1, 3, 4, 5, 8, 9, 127, 128, 129, 3000)
+LIT_LENGTHS = (0, 1, 15, 16, 17, 127, 128, 129, 300)
+LAST_LITERALS = (0, 1, 129, 5000)
+MATCH_LENGTHS = (3, 4, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1000, 65539)
+FAR_OFFSETS = (60000, 120000)
+
+
+def offsets_wanted(K):
+    R, W = K["LDS_REACH"], K["WIN"]
+    return (1, 2, 3, 4, 7, 8, 15, 16, 17, R - 1, R, R + 1, R + 16, W - 1, W, W + 1) + FAR_OFFSETS
+
+
+_catalog = None
+
+
+def catalog():
+    """the hand frames: [Case], built once"""
+    global _catalog
+    if _catalog is not None:
+        return _catalog
+    K = kernel_constants()
+    GS, CHUNK, R, W = K["GS"], K["CHUNK"], K["LDS_REACH"], K["WIN"]
+    rng = np.random.default_rng(20240)
+    cases = []
+    want_of = set(offsets_wanted(K))
+
+    def tags_of(seqs, offs, last):
+        t = {"nseq=%d" % len(seqs), "last=%d" % last, "count-form=%d" % (0 if not seqs else (1 if len(seqs) < 128 else 2))}
+        out = 0
+        for i0 in range(0, len(seqs), GS):  # the ring executor's step: what is flushed when it requests its far matches (an output that starts on a 16-byte boundary)
+            flushed = out // CHUNK * CHUNK
+            for lane, ((ll, ml, off), o) in enumerate(zip(seqs[i0:i0 + GS], offs[i0:i0 + GS])):
+                t.add("ll=%d" % ll)
+                t.add("ml=%d" % ml)
+                if o in want_of or off < 0:
+                    t.add("of=%d" % o if off > 0 else "rep=%d,ll%s0" % (-off, ">" if ll > 0 else "="))
+                start = out + ll - o
+                if o > R:
+                    if o >= 16 and start >= 0 and start + 16 <= flushed:
+                        t.add("far=prefetch")
+                        if lane > 0:
+                            t.add("far=prefetch-lane>0")  # (the 16 bytes reach the group from another lane than its first)
+                        if ml < 16:
+                            t.add("far=short")
+                    else:
+                        t.add("far=near-source")
+                if o < ml:
+                    t.add("overlap")
+                out += ll + ml
+        return t
+
+    def add(name, seqs, last=0, checksum=None, cap=None, malformed=False, lit_cut=0, extra_tags=()):
+        checksum = len(cases) % 2 == 1 if checksum is None else checksum
+        nlit = sum(s[0] for s in seqs) + last - lit_cut
+        literals = rng.integers(0, 256, nlit, dtype=np.uint8).tobytes()
+        frame, plain = build_frame(literals, seqs, checksum=checksum, last_literals=None if lit_cut else last)
+        _, offs, failed = execute(literals, seqs)
+        assert (plain is None) == (failed >= 0)
+        full = len(plain) if plain is not None else sum(s[0] + s[1] for s in seqs) + last
+        cap = full if cap is None else cap
+        bad = plain is None or cap < full
+        assert bad == malformed, name
+        t = tags_of(seqs, offs, last) if not bad else set()
+        cases.append(Case(name, frame, None if bad else plain, cap, len(seqs), malformed=bad, stage=4 if bad else None, tags=t | set(extra_tags), checksum=checksum, slack=not bad))
+        return cases[-1]
+
+    def mixed(n, lls, mls, ofs):
+        """n sequences that cycle through the given values (each list within one code); an offset that does not fit yet gives way to the largest that does"""
+        seqs = []
+        out = 0
+        for i in range(n):
+            ll = max(lls) if i == 0 else lls[i % len(lls)]
+            ml = mls[(i // 2) % len(mls)] if i else mls[0]
+            fit = [o for o in ofs if o <= out + ll]
+            assert fit, (lls, ofs)
+            pick = ofs[(i * 5 // 3) % len(ofs)]
+            seqs.append((ll, ml, pick if pick in fit and i else max(fit)))
+            out += ll + ml
+        return seqs
+
+    # the smallest instance: one raw literal, one sequence (ll 1, ml 3, offset 1) -> AAAA
+    frame, plain = build_frame(b"A", [(1, 3, 1)], checksum=False, last_literals=0)
+    assert frame == bytes.fromhex("28b52ffd20044500000841015401020004") and plain == b"AAAA"
+    cases.append(Case("smallest", frame, plain, 4, 1, tags={"nseq=1", "ll=1", "ml=3", "of=1", "last=0", "overlap", "count-form=1"}))
+
+    # sequence counts: the ring executor takes GS records a step and requests the next GS; both forms of the count
+    for n in SEQ_COUNTS:
+        add("count-%d" % n, [(5, 4, 1 + (i * 7) % 4 if i else 4) for i in range(n)], last=7 if n == 0 else n % 3)
+    # last literals
+    for last in LAST_LITERALS:
+        add("last-%d" % last, mixed(5, [20, 21], [9], [13, 17, 20]), last=last, checksum=last in (0, 5000))
+    # literal-length groups x match-length groups x offset groups; every list lies within one code
+    ll_groups = {"1": [1], "15": [15], "16": [17, 16], "25": [127, 64, 100], "26": [129, 128, 200], "27": [300, 256, 511], "31": [W + 4, W, W + 900]}
+    of_groups = {"tiny": [1, 2, 3, 4], "8": [7, 8, 5, 12], "16": [15, 16, 17, 13, 28], "reach": [R - 1, R, R + 1, R + 16, 125, 252],
+                 "window": [W - 1, W, W + 1, 2 * W - 4]}
+    ml_groups = [[3], [4], [15], [16], [17], [63, 64, 65, 59, 66], [255, 256, 257, 131, 258], [1000, 515, 1026], [65539]]
+    pairs = [("1", "tiny"), ("15", "tiny"), ("15", "8"), ("15", "16"), ("16", "16"), ("16", "8"), ("25", "reach"), ("25", "tiny"), ("26", "reach"), ("27", "reach"),
+             ("27", "16"), ("31", "window"), ("31", "reach")]
+    for mls in ml_groups:
+        for lg, og in pairs:
+            ofs = of_groups[og] if lg != "1" else [1]
+            n = 1 if mls[0] == 65539 else 9
+            if mls[0] == 65539 and lg == "31":
+                continue  # (one of these is enough: 64 KiB of output a frame)
+            add("ll%s-ml%d-of-%s" % (lg, mls[0], og), mixed(n, ll_groups[lg], mls, ofs), last=(len(cases) * 37) % 131)
+    # far offsets in a block near 128 KiB, with long and with short matches.  (Their literal-length codes allow four records at the most: all of them in the ring
+    # executor's first step, which begins with nothing flushed -- they reach their sources through copy_match's far path, not through the prefetch.)
+    add("far-60000", [(60100, 900, 60000), (32768, 600, 60001), (32800, 1000, 59990)], last=300)
+    add("far-60000-short", [(60100, 15, 60000), (32768, 15, 60001), (32800, 15, 59990)], last=5000)
+    add("far-120000", [(120100, 5000, 120000)], last=5000)
+    add("far-120000-short", [(120100, 11, 120000)], last=10000)
+    # ... and the source close behind the write position: the far offset's first 16 bytes are not flushed yet when the step begins
+    add("far-near-source", [(127, 200, 125)] + [(64 + 5 * i, 131 + i, R + 1 + (i % 4) * 5) for i in range(1, 12)], last=1)
+    add("far-near-source-short", [(127, 3 + 8, 125)] + [(64 + 5 * i, 3 + 8, R + 1 + (i % 4) * 5) for i in range(1, 12)], last=0)
+    # ... and prefetches in a frame small enough for the large tiles' pool: the second and third record of a step find their sources flushed
+    add("far-prefetch-small", [(511, 40, 509)] + [(256 + i, 40, 1020 - 7 * i if i > 1 else 800) for i in range(1, 12)], last=5)
+    add("far-prefetch-small-short", [(511, 12, 509)] + [(256 + i, 12, 1000 - i if i > 2 else 780) for i in range(1, 13)], last=0)
+    # repeat-offset codes with ll > 0: value 1 is the last offset (1 at a frame's start), 2 and 3 the ones before it (4 and 8)
+    add("rep-1", [(9, 5, -1)] * 6, last=2)
+    add("rep-2-3", [(9, 5, -2), (9, 5, -3), (9, 5, -3), (9, 5, -2), (9, 5, -2), (9, 5, -3), (9, 5, -3)], last=2)
+
+    # ---- malformed at the execute stage (every stage before it content) ----
+    bad0 = len(cases)
+    # a match that starts before the output, in the first and in the second record (see the module's text for the fourth and the fifth)
+    add("bad-match@1", [(8, 4, 9), (8, 4, 5)], last=3, malformed=True, extra_tags={"bad-match@1"})
+    add("bad-match@2", [(255, 3, 253), (128, 3, 508), (128, 3, 253)], last=3, malformed=True, extra_tags={"bad-match@2"})
+    # ll = 0: all records of the frame, so the first one fails; also with each repeat-offset value
+    add("bad-ll0", [(0, 4, 1), (0, 4, 1)], last=9, malformed=True, extra_tags={"ll=0", "bad-match@1"})
+    for v in (1, 2, 3):
+        add("bad-rep%d-ll0" % v, [(0, 4, -v), (0, 4, -v)], last=9, malformed=True, extra_tags={"rep=%d,ll=0" % v, "bad-match@1"})
+    for k in (1, 2, 4, 5):
+        seqs = mixed(7, [20, 21], [9], [13, 17, 20])
+        # ll beyond the literals left: the literals end one byte short of record k's
+        add("bad-ll@%d" % k, seqs, malformed=True, lit_cut=sum(s[0] for s in seqs[k - 1:]) - seqs[k - 1][0] + 1, extra_tags={"bad-ll@%d" % k})
+        # output beyond the capacity by one byte in record k's match
+        add("bad-cap-match@%d" % k, seqs, last=4, malformed=True, cap=sum(s[0] + s[1] for s in seqs[:k]) - 1, extra_tags={"bad-cap-match@%d" % k})
+    for k in (4, 5):  # ... the same with sequences long enough for the per-item rule to hand the frame to the ring executor in a large tile
+        seqs = mixed(7, [127, 64, 100], [63, 64], [R + 1, 125])
+        add("bad-ll-long@%d" % k, seqs, malformed=True, lit_cut=sum(s[0] for s in seqs[k - 1:]) - seqs[k - 1][0] + 1, extra_tags={"bad-ll@%d" % k})
+        add("bad-cap-match-long@%d" % k, seqs, last=4, malformed=True, cap=sum(s[0] + s[1] for s in seqs[:k]) - 1, extra_tags={"bad-cap-match@%d" % k})
+    seqs = mixed(6, [127, 64, 100], [63, 64], [R + 1, 125])
+    full = sum(s[0] + s[1] for s in seqs)
+    add("bad-cap-match-last", seqs, last=0, malformed=True, cap=full - 1, extra_tags={"bad-cap-match-last"})
+    add("bad-cap-last-literals-1", seqs, last=129, malformed=True, cap=full + 128, extra_tags={"bad-cap-last"})
+    add("bad-cap-last-literals-all", seqs, last=129, malformed=True, cap=full, extra_tags={"bad-cap-last"})
+    add("bad-cap-one-short", seqs, last=1, malformed=True, cap=full, extra_tags={"bad-cap-one-short"})
+    add("bad-cap-one-short-no-sequences", [], last=40, malformed=True, cap=39, extra_tags={"bad-cap-one-short"})
+    add("bad-cap-one-short-checksum", mixed(9, [5], [4], [1, 2, 3, 4]), last=1, checksum=True, malformed=True, cap=9 * 9, extra_tags={"bad-cap-one-short"})
+    assert all(c.malformed for c in cases[bad0:]) and not any(c.malformed for c in cases[:bad0])
+    _catalog = cases
+    return cases
+
+
+MALFORMED_KINDS = ("bad-match@1", "bad-match@2", "bad-ll@1", "bad-ll@2", "bad-ll@4", "bad-ll@5", "bad-cap-match@1", "bad-cap-match@2", "bad-cap-match@4",
+                   "bad-cap-match@5", "bad-cap-match-last", "bad-cap-last", "bad-cap-one-short", "ll=0", "rep=1,ll=0", "rep=2,ll=0", "rep=3,ll=0")
+
+
+def required_tags(K):
+    """every edge the catalog promises, as tags of its VALID cases (ll = 0 and the repeat-offset codes with ll = 0: of its malformed ones)"""
+    t = ["nseq=%d" % n for n in SEQ_COUNTS] + ["count-form=1", "count-form=2"]
+    t += ["ll=%d" % v for v in LIT_LENGTHS if v] + ["last=%d" % v for v in LAST_LITERALS] + ["ml=%d" % v for v in MATCH_LENGTHS]
+    t += ["of=%d" % v for v in offsets_wanted(K)] + ["far=prefetch", "far=prefetch-lane>0", "far=near-source", "far=short", "overlap"]
+    t += ["rep=%d,ll>0" % v for v in (1, 2, 3)]
+    return t
+
+
+def encoder_plains(text, fragments):
+    """the plaintexts of the encoders' frames (they bring Huffman literals from the arena, FSE tables, ll = 0 and repeat offsets): pieces of 300 bytes to
+    128 KiB of `text` and of `fragments` (bytes of at least 128 KiB each: the callers take them from tests/common.py)"""
+    out = []
+    for kind, data in (("text", text), ("fragments", fragments)):
+        for n, at in ((300, 0), (1000, 5000), (2500, 777), (4096, 20000), (33333, 1234), (131072, 0)):
+            out.append(("%s-%d" % (kind, n), data[at:at + n]))
+    return out
+
+
+def encoder_cases(plains, encoders):
+    """[Case] of encoders' frames: plains as encoder_plains() gives them, encoders [(name, bytes -> frame)]"""
+    cases = []
+    for ename, enc in encoders:
+        for pname, p in plains:
+            f = bytes(enc(p))
+            n = sequence_count(f)
+            assert n is not None, (ename, pname)
+            cases.append(Case("%s-%s" % (ename, pname), f, p, len(p), n, tags={"encoder"}, checksum=bool(f[4] & 4)))
+    return cases

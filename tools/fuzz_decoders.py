@@ -21,7 +21,8 @@ def run(n_cases, seed, codecs=("lz4", "snappy"), big=False):
     HADOOP = {"lz4hadoop": "lz4", "snappyhadoop": "snappy"}
     VARIANTS = {"lz4": [1, 13, 7, 71], "snappy": [1, 13, 7, 71],  # (71: variant 7 with the lane-per-block parser -- batches of this size take the wavefront-per-block one;
                                                                 # 13: the ring decoders' latency class -- a wavefront and 128 KiB of LDS history per block -- for every batch size)
-                 "zstd": [1, 0], "lz4frame": [None], "snappyframed": [None], "lz4hadoop": [3, 1, 2, 0], "snappyhadoop": [3, 1, 2, 0]}  # (hadoop.decompress.variant)
+                                                                # zstd 10: the pipeline (variant 1) with every item on its ring executor -- zstd.decompress.exec 0; batches of this size otherwise take the record executor)
+                 "zstd": [1, 0, 10], "lz4frame": [None], "snappyframed": [None], "lz4hadoop": [3, 1, 2, 0], "snappyhadoop": [3, 1, 2, 0]}  # (hadoop.decompress.variant)
 
 
     def expect(codec, data, cap):
@@ -77,7 +78,9 @@ def run(n_cases, seed, codecs=("lz4", "snappy"), big=False):
             if variant is not None and codec in HADOOP:
                 gb.set_option("hadoop.decompress.variant", variant)
             elif variant is not None:
-                gb.set_option("%s.decompress.variant" % codec, 7 if variant == 71 else (1 if variant == 13 else variant))
+                gb.set_option("%s.decompress.variant" % codec, 7 if variant == 71 else (1 if variant in (13, 10) else variant))
+                if codec == "zstd":
+                    gb.set_option("zstd.decompress.exec", 0 if variant == 10 else 2)
                 gb.set_option("decompress.latency_max_blocks", 65536 if variant == 13 else 0)
                 if codec in ("lz4", "snappy"):
                     gb.set_option("%s.decompress.parse" % codec, 1 if variant == 71 else 0)
@@ -94,6 +97,8 @@ def run(n_cases, seed, codecs=("lz4", "snappy"), big=False):
             print("%s variant %s: %d cases (%d malformed), %d mismatches" % (codec, variant, len(cases), n_err, wrong), flush=True)
         if codec in ("lz4", "snappy"):
             gb.set_option("%s.decompress.parse" % codec, 0)
+        if codec == "zstd":
+            gb.set_option("zstd.decompress.exec", 2)
         if codec in HADOOP:
             gb.set_option("hadoop.decompress.variant", 3)
         gb.set_option("decompress.latency_max_blocks", 256)

@@ -208,16 +208,72 @@ def fuzz(n_cases, seed):
     return bad
 
 
+def catalog_cases(quick):
+    """the case catalog of tests/zstd_frame_cases.py: the hand frames, and the encoders' frames next to them"""
+    from tests import zstd_frame_cases as zc
+    text = b"".join(d for _, d, _ in common.corpus_sample()[:3])
+    encs = [("oracle", lambda p: o.compress("zstd", p))] + ([("libzstd-3", lambda p: libzstd(p, 3))] if HAVE_LIBZSTD else [])
+    cases = zc.catalog() + zc.encoder_cases(zc.encoder_plains(text, common.synthetic_blocks(21, 1, 131072)[0]), encs)
+    if quick:  # (the frames beyond 40 KB: only the far offsets' -- nothing else in them that a smaller frame does not have)
+        cases = [c for c in cases if c.cap <= 40000 or c.name.startswith("far-")]
+    return cases
+
+
+def catalog(expect_fast):
+    """--part catalog: the execute stage's case catalog under BOTH executors -- exec_mode low bits 0: the ring executor (zstd_pipe_execute_kernel), without a
+    staging area for far matches and (bit 8) with the product's; 1: the record executor -- at exact capacities and with slack.  A valid frame must come back as the
+    oracle's plaintext from the fast path; a malformed one (all of them are malformed at the execute stage) must be on the fallback list, counted at stage 4."""
+    cases = catalog_cases("--quick" in sys.argv)
+    bad = 0
+    for mode, what in ((0, "ring executor, no staging area"), (0 | (1 << 8), "ring executor, far matches staged"), (1, "record executor")):
+        for pad in (0, 64):
+            caps = [c.capacity(pad) for c in cases]
+            outs, status, fb = run([c.frame for c in cases], caps, exec_mode=mode)
+            wrong = 0
+            for i, c in enumerate(cases):
+                try:
+                    want = o.decompress("zstd", c.frame, caps[i])
+                except oracle_lib.OracleError:
+                    want = None
+                if (want is None) != c.malformed or (want is not None and want != c.plain):
+                    wrong += 1
+                    print("MISMATCH catalog %s: the oracle %s" % (c.name, "refuses" if want is None else "decodes %d bytes" % len(want)))
+                elif want is None:
+                    if i not in fb:
+                        wrong += 1
+                        print("MISMATCH %s, pad %d, %s: malformed, but not on the fallback list (status %d)" % (what, pad, c.name, status[i]))
+                elif i in fb or status[i] != 0 or outs[i] != want:
+                    wrong += 1
+                    first = -1
+                    if outs[i] is not None:
+                        m = min(len(outs[i]), len(want))
+                        d = np.nonzero(np.frombuffer(outs[i][:m], dtype=np.uint8) != np.frombuffer(want[:m], dtype=np.uint8))[0]
+                        first = int(d[0]) if len(d) else m
+                    print("MISMATCH %s, pad %d, %s: %s, status %d, %s bytes of %d, first difference at %d" % (
+                        what, pad, c.name, "on the fallback list" if i in fb else "fast path", status[i], None if outs[i] is None else len(outs[i]), len(want), first))
+            stages = [int(x) for x in run.counters[33:39]]
+            n_bad = sum(1 for c in cases if c.malformed)
+            if stages != [0, 0, 0, n_bad, 0, 0]:
+                wrong += 1
+                print("MISMATCH %s, pad %d: fallback list by stage %s, expected %d at stage 4 only" % (what, pad, stages, n_bad))
+            print("catalog, %s, pad %d: %d frames (%d malformed), fallback list by stage %s, %d wrong" % (what, pad, len(cases), n_bad, stages, wrong), flush=True)
+            bad += wrong
+    print("zstd execute-stage catalog under both executors: %d mismatches" % bad)
+    return bad
+
+
 def main():
     if "--fuzz" in sys.argv:
         k = sys.argv.index("--fuzz")
         sys.exit(1 if fuzz(int(sys.argv[k + 1]), int(sys.argv[k + 2]) if len(sys.argv) > k + 2 else 1) else 0)
     expect_fast = "--expect-fast" in sys.argv
-    part = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else "all"  # single | multi | damaged | all
+    part = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else "all"  # single | multi | damaged | catalog | all
     if part == "multi":
         sys.exit(1 if multi_block(expect_fast) else 0)
     if part == "damaged":
         sys.exit(1 if mutations(expect_fast) else 0)
+    if part == "catalog":
+        sys.exit(1 if catalog(expect_fast) else 0)
     plains = [d for _, d in common.HAND_CASES if len(d) > 0] + [d[:131072] for _, d, _ in common.corpus_sample()[:8]] + common.synthetic_blocks(5, 6)
     plains = [p for p in plains if len(p) <= 131072]
     bad = 0; slow = 0; total = 0
@@ -244,6 +300,7 @@ def main():
     if part == "all":
         bad += multi_block(expect_fast)
         bad += mutations(expect_fast)
+        bad += catalog(expect_fast)
     if bad or (expect_fast and slow):
         sys.exit(1)
 

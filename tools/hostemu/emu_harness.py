@@ -85,7 +85,8 @@ class EmuAllBatch(EmuBatch):
         self.codec.native.get_stat = self.get_stat
 
     def get_stat(self, name):
-        words = {"zstd.decompress.fallback_items": 0, "zstd.decompress.multiblock_items": 40, "zstd.decompress.multiblock_blocks": 41, "zstd.decompress.multiblock_fast_items": 42}
+        words = {"zstd.decompress.fallback_items": 0, "zstd.decompress.multiblock_items": 40, "zstd.decompress.multiblock_blocks": 41, "zstd.decompress.multiblock_fast_items": 42,
+                 "zstd.decompress.long_items": 18}
         if name in words:
             return int(self.counters[words[name]])
         if name.startswith("zstd.decompress.fallback_stage"):

@@ -2,6 +2,8 @@
 // the multi-block stages) under the fiber emulator.  The sequence stage gives an item to a quad of lanes: its DPP broadcasts and LDS
 // hand-overs are quad-level rendezvous here (hip/hip_runtime.h).  The one-kernel decoder that takes the pipeline's fallback list moves
 // bytes between lanes in hardware order and is NOT emulated: items on the fallback list are reported to the caller instead.
+// The ring executor (zstd_pipe_execute_kernel: four lanes an item over achip_rings.h) needs the rings' group rendezvous, as tools/hostemu/emu.cpp has them.
+#define HOSTEMU_RINGS_LOCKSTEP 1  // achip_rings.h: the lanes of a group meet where the device's lockstep makes them meet
 #include "hip/hip_runtime.h"
 thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
 extern "C" { long long achip_emu_counters[16]; }
@@ -112,7 +114,8 @@ extern "C" int emu_zstd_pipe(const uint8_t* srcBase, const int64_t* srcOff, cons
                              int32_t* counters, int64_t mbMaxBytes)
 {
     g_mbMaxBytes = mbMaxBytes;
-    achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, 16};
+    // (execMode bit 8: the product's default decompress.ring_pad of 80 -- the ring executor then stages far matches in LDS; otherwise 16: no staging area)
+    achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, (execMode >> 8) & 1 ? 80 : 16};
     static std::vector<uint8_t> scratch;
     const int64_t bytes = achip::zstd_decompress_pipe_scratch_bytes(n, tile);
     scratch.assign((size_t)bytes, 0xCD);
