@@ -27,8 +27,11 @@
 #pragma once
 #include "lz4_compress_body.h"
 
-#if defined(ACHIP_HOST_STATS)  // (tools/hostemu, a counting build: which way the replay's sequences go -- tools/hostemu/lz4_paths.py)
-extern "C" long long g_zc_stats[32];
+#if defined(ACHIP_HOST_STATS)  // (tools/hostemu, a counting build: which way the replay's sequences go -- tools/hostemu/enc_paths.py, tests/test_encoder_edge_cases.py)
+// 20 sequences of the replay, 21 vector path, 22 more than 4 bytes match backwards, 23 candidate inside the window, 24 no usable facts, 25 mode-2 matches, 26 windows,
+// 27 zero-literal hits, 28 / 29 scalar count from registers (okA && okB) / from memory, 30 / 34 the memory catch-up takes a second trip (window / mode 2),
+// 31 / 32 the block ends at a probe beyond matchFindLimit / behind a match, 33 a match ends beyond its window, 35 mode 2 runs off the end
+extern "C" long long g_zc_stats[64];
 #define MWC(k) do { if (lane == 0) g_zc_stats[k]++; } while (0)
 #else
 #define MWC(k)
@@ -197,6 +200,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                     wave_sync();  // (the accesses of this wavefront to its table, in order; it may share its workgroup with others: lz4_compress_tiers_kernel)
                     if (winner < 0) {
                         if (firstInvalid < 64) {
+                            MWC(35);
                             break;  // the search ran off the end: last literals from anchor
                         }
                         k0 += 64;
@@ -216,6 +220,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                         if (run < 64) {
                             break;
                         }
+                        if (room > 0) MWC(34);
                     }
                     const int32_t literalLength = input - anchor;
                     const int32_t tokenPos = output;
@@ -335,6 +340,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                     }
                     const int w = __builtin_ctzll(first);
                     if (((im >> w) & 1ull) != 0) {  // the probe at lane w would step beyond matchFindLimit: the block ends in literals
+                        MWC(31);
                         M |= sbits(p0, w);
                         blockDone = true;
                         break;
@@ -363,6 +369,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                     MWC(20);
                     if (jl >= 0) MWC(23);
                     if (!quick) MWC(24);
+                    if (zeroLit) MWC(27);
                     if (quick) {
                         const int32_t vIn0 = vec(input), vCand0 = vec(cand);
                         const uint32_t vF = vec(factsW);
@@ -395,6 +402,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                             vAnchor = vInput + vMl + MIN_MATCH;
                             input = uni(vAnchor);
                             if (input > matchFindLimit) {  // :152-155
+                                MWC(32);
                                 blockDone = true;
                                 break;
                             }
@@ -404,6 +412,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                                 r = rr;
                                 continue;
                             }
+                            MWC(33);
                             break;  // the match ends beyond the window: the next one starts at input - 2
                         }
                     }
@@ -491,6 +500,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                                 if (run < 64) {
                                     break;
                                 }
+                                if (room2 > 0) MWC(30);
                             }
                             back = input - i2;
                         }
@@ -521,6 +531,8 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                         // (a catch-up that went to memory may have moved both positions out of what the registers hold)
                         const bool okA = la >= 0 && la < 64 && a0 + 8 <= inLen;
                         const bool okB = jl >= 0 ? (lb >= 0 && lb < 64 && b0 + 8 <= inLen) : (winFast && back <= shiftW + 4);
+                        if (okA && okB) MWC(28);
+                        if (!(okA && okB)) MWC(29);
                         if (okA && okB) {
                             const uint64_t a8 = rl64(x, la);
                             const uint64_t b8 = jl >= 0 ? rl64(x, lb) : ext64(rLoW, rHiW, shiftW + 4 - back);
@@ -542,6 +554,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                     vAnchor = vec(anchor);
                     vOutput = vec(output);
                     if (input > matchFindLimit) {  // :152-155
+                        MWC(32);
                         blockDone = true;
                         break;
                     }
@@ -551,6 +564,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                         r = rr;
                         continue;
                     }
+                    MWC(33);
                     break;  // the match ends beyond the window: the next one starts at input - 2
                 }
                 anchor = uni(vAnchor);

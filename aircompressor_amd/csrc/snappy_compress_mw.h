@@ -9,6 +9,18 @@
 #pragma once
 #include "snappy_compress_body.h"
 
+#if defined(ACHIP_HOST_STATS)  // (tools/hostemu, a counting build: which way the replay's copies go -- tools/hostemu/enc_paths.py, tests/test_encoder_edge_cases.py)
+// 40 copies of the replay, 41 candidate inside the window, 42 re-probe hits, 43 copies split into pieces of 64 / 60, 44 / 45 the last piece a copy with a 1-byte /
+// 2-byte offset, 46 mode-2 copies, 47 windows, 48 / 49 the search runs off the end in a window / in mode 2, 50 vector path, 51 a copy ends beyond its window,
+// 52 / 53 scalar count from registers / from memory
+extern "C" long long g_zc_stats[64];
+#define SNWC(k) do { if (lane == 0) g_zc_stats[k]++; } while (0)
+#define SNWC_COPY(offset, matched) do { int32_t m_ = (matched); if (m_ > 64) SNWC(43); while (m_ >= 68) m_ -= 64; if (m_ > 64) m_ -= 60; \
+                                        if (m_ < 12 && (offset) < 2048) SNWC(44); else SNWC(45); } while (0)
+#else
+#define SNWC(k)
+#define SNWC_COPY(offset, matched)
+#endif
 namespace achip {
 
 namespace snmw {
@@ -140,6 +152,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                         wave_mem_order();
                         if (winner < 0) {
                             if (firstInvalid < 64) {
+                                SNWC(49);
                                 break;  // the search ran off the end: what is left is a literal (:160-162)
                             }
                             k0 += 64;
@@ -152,6 +165,8 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                         group_copy<64>(out + output, in + nextEmit, literalLength, lane);
                         output += literalLength;
                         const int32_t matched = 4 + wave_count(in, input + 4, candidate + 4, blockLimit, lane);
+                        SNWC(46);
+                        SNWC_COPY(input - candidate, matched);
                         output = snappy_emit_copy(out, output, input - candidate, matched, lane);
                         input += matched;
                         nextEmit = input;
@@ -164,6 +179,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
 
                     // ---- a window: 64 consecutive positions from `base`.  After a copy: lane 0 = input - 1 (inserted, never probed), lane 1 =
                     // input (the re-probe), the search from lane 2; at the start of a block: lane 0 = position 0 (neither), the search from lane 1 ----
+                    SNWC(47);
                     const int32_t base = mode == 0 ? 0 : input - 1;
                     const int32_t pos = base + lane;
                     const bool canLoad = pos + 8 <= blockLimit;
@@ -260,6 +276,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             }
                             const int w = __builtin_ctzll(first);
                             if (((im >> w) & 1ull) != 0) {  // the loop condition of :141 fails at lane w: the block ends in a literal
+                                SNWC(48);
                                 M |= probes & sbits(c, w);
                                 blockDone = true;
                                 break;
@@ -271,6 +288,9 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                         }
                         // ---- a copy starts at lane wl against `cand` ----
                         input = base + wl;
+                        SNWC(40);
+                        if (jl >= 0) SNWC(41);
+                        if (viaReprobe) SNWC(42);
                         uint32_t factsW = 0;
                         if (jl < 0) {
                             factsW = rl32(facts, wl);
@@ -296,6 +316,8 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             if (__ballot(vFwd == 8 && vLimitLen > 8) != 0) {  // (uniform) the registers' 8 bytes all match: memory has the rest
                                 vMatched = 12 + vec(wave_count(in, vIn + 12, vCand + 12, blockLimit, lane));
                             }
+                            SNWC(50);
+                            SNWC_COPY(vIn - vCand, vMatched);
                             vOutput = snappy_emit_copy(out, vOutput, vIn - vCand, vMatched, lane);
                             vNextEmit = vIn + vMatched;
                             input = uni(vNextEmit);
@@ -309,6 +331,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                                 r = rr;
                                 continue;
                             }
+                            SNWC(51);
                             break;  // the copy ends beyond the window: the next one starts at input - 1
                         }
                         // ---- every other copy: scalar code, as before round 6 ----
@@ -329,6 +352,8 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             const int la = a0 - base, lb = b0 - base;
                             const bool okA = la < 64 && a0 + 8 <= blockLimit;
                             const bool okB = jl >= 0 ? (lb < 64 && b0 + 8 <= blockLimit) : rl32((uint32_t)fast, wl) != 0;
+                            if (okA && okB) SNWC(52);
+                            if (!(okA && okB)) SNWC(53);
                             if (okA && okB) {
                                 const uint64_t a8 = rl64(x, la);
                                 const uint64_t b8 = jl >= 0 ? rl64(x, lb) : rl64(after8, wl);
@@ -344,6 +369,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                                 matched = 4 + wave_count(in, a0, b0, blockLimit, lane);
                             }
                         }
+                        SNWC_COPY(input - cand, matched);
                         output = snappy_emit_copy(out, output, input - cand, matched, lane);
                         input += matched;
                         nextEmit = input;
@@ -359,6 +385,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             r = rr;
                             continue;
                         }
+                        SNWC(51);
                         break;  // the copy ends beyond the window: the next one starts at input - 1
                     }
                     nextEmit = uni(vNextEmit);

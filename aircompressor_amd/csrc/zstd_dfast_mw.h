@@ -24,7 +24,7 @@
 #pragma once
 
 #ifdef ACHIP_HOST_STATS  // (CPU emulator only: how often each part of the replay runs -- tools/hostemu/zc_stats.py)
-extern "C" long long g_zc_stats[32];
+extern "C" long long g_zc_stats[64];
 // (out of line and not instrumented: under the emulator's access-granular lockstep every traced access is an order point of ALL lanes)
 static __attribute__((noinline, no_sanitize("coverage"))) void zc_stat_add(int i, long long n) { g_zc_stats[i] += n; }
 #define ZC_STAT(i, n) \

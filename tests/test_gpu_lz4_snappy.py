@@ -62,6 +62,8 @@ def test_compress_is_bit_exact_with_oracle(gb, o, codec, variant):
     assert all(s == 0 for s in status), status
     for i, (b, c) in enumerate(zip(blocks, outs)):
         assert c == o.compress(codec, b), "block %d (len %d)" % (i, len(b))
+    packed, status, _ = gb.run(CODECS[codec]["c"], blocks, caps, unaligned=True)  # (sources and slots back to back: no block starts 16-byte aligned)
+    assert all(s == 0 for s in status) and packed == outs
     # committed hashes of the oracle's streams for the corpus sample (tests/golden/corpus_sample.json)
     n_hand = len(common.HAND_CASES)
     for k, (_, _, e) in enumerate(common.corpus_sample()):

@@ -3,7 +3,8 @@ order point -- the lockstep of a wavefront at the granularity of memory operatio
 parse on all 64 lanes and updates its tables in place).  Output, status and length against the oracle's restatement of the Java encoders:
 byte-identical or a mismatch.
 
-  check_enc.py [--quick] [--part block|zstd|stream|containers]     the encoders' parity cases at sizes the emulator finishes in minutes
+  check_enc.py [--quick] [--part block|zstd|stream|containers|snappyfan|edges]   the encoders' parity cases at sizes the emulator finishes in minutes
+                                                                   (edges: the constructed inputs of tests/encoder_edge_cases.py, every LZ4 / Snappy variant)
   check_enc.py --chunked N                                         one ZstdOutputStream of N bytes (N >= 4 MiB: the chunked writer with its
                                                                    window slides, behind zstd.stream.chunked = 1 in the product)"""
 import ctypes, os, sys, time
@@ -156,6 +157,26 @@ def part_snappyfan():
     return bad
 
 
+def part_edges():
+    """the catalog of constructed inputs (tests/encoder_edge_cases.py: every entry of at most 20 000 bytes; a mismatch names its case) through every variant"""
+    from tests import encoder_edge_cases
+    bad = 0
+    for codec, op, variants in (("lz4", 1, (4, 4 | 16, 4 | 48, 1, 0)), ("snappy", 3, (4, 2, 1, 0))):
+        entries = encoder_edge_cases.emulator_cases(codec)
+        blocks = [d for _, d, _ in entries]
+        caps = [o.max_compressed_length(codec, len(b)) for b in blocks]
+        want = [o.compress(codec, b) for b in blocks]
+        for v in variants:
+            t = time.time()
+            outs, status, _ = EncBatch(v).run(op, blocks, caps, unaligned=True)
+            wrong = [e[0] for e, c, s, w in zip(entries, outs, status, want) if s != 0 or c != w]
+            for name in wrong:
+                print("  MISMATCH %s compress, variant %d: %s" % (codec, v, name))
+            bad += len(wrong)
+            print("%-64s %4d items %8d bytes  %d mismatches  (%.0f s)" % ("%s compress, variant %d, catalog of edges" % (codec, v), len(blocks), sum(len(b) for b in blocks), len(wrong), time.time() - t), flush=True)
+    return bad
+
+
 def chunked(n):
     src = b"".join(common.multi_block_plains())
     while len(src) < n:
@@ -201,7 +222,7 @@ def main():
         sys.exit(1 if ostream(sizes) else 0)
     if "--chunked" in sys.argv:
         sys.exit(1 if chunked(int(sys.argv[sys.argv.index("--chunked") + 1])) else 0)
-    parts = {"block": part_block, "zstd": part_zstd, "stream": part_stream, "containers": part_containers, "snappyfan": part_snappyfan}
+    parts = {"block": part_block, "zstd": part_zstd, "stream": part_stream, "containers": part_containers, "snappyfan": part_snappyfan, "edges": part_edges}
     only = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else None
     bad = 0
     for name, fn in parts.items():
