@@ -224,6 +224,39 @@ class HipBatchCodec:
         self.pack_outputs(r["slots"], r["dst_off"], r["out_len"], r["status"], n, align, r["packed"], r["total_bytes"], r["packed_off"], r["packed_len"], total, **raw)
         return r
 
+    def window_decompress(self, op, flags, src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, err_off, n_blocks, consumed, stop, need):
+        """achip_window_decompress_batch: item i is a WINDOW of an x-snappy-framed or Hadoop stream (op: OP_SNAPPYFRAMED_ / OP_LZ4HADOOP_ / OP_SNAPPYHADOOP_DECOMPRESS)
+        that begins at a unit boundary; flags[i] (int32) = native.WINDOW_FIRST | native.WINDOW_LAST.  The call takes the leading whole units that fit dst_cap[i]:
+        consumed[i] (int64) bytes of input, out_len[i] bytes of plaintext; stop[i] (int32, native.STOP_*) says why it took no more and need[i] (int64) what the next
+        unit wants.  The caller keeps the stream position; nothing is kept between calls.  Asynchronous on the context stream; all arguments device-accessible."""
+        r = self.lib.achip_window_decompress_batch(self.native.ctx, int(op), _ptr(flags), _ptr(src), _ptr(src_off), _ptr(src_len), _ptr(dst), _ptr(dst_off), _ptr(dst_cap),
+                                                   _ptr(out_len), _ptr(status), _ptr(err_off), int(n_blocks), _ptr(consumed), _ptr(stop), _ptr(need))
+        if r < 0:
+            native.raise_for_status(r)
+
+    def window_compress(self, op, flags, src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, err_off, n_blocks, consumed, stop, need):
+        """achip_window_compress_batch: the writers' side of `window_decompress` (op: the three container compress ops).  consumed[i] = the whole blocks of window i
+        whose worst case fits dst_cap[i] -- with WINDOW_LAST the partial tail too; the outputs of a stream's windows, one behind the other, are the one-shot
+        writer's stream.  Asynchronous on the context stream; all arguments device-accessible."""
+        r = self.lib.achip_window_compress_batch(self.native.ctx, int(op), _ptr(flags), _ptr(src), _ptr(src_off), _ptr(src_len), _ptr(dst), _ptr(dst_off), _ptr(dst_cap),
+                                                 _ptr(out_len), _ptr(status), _ptr(err_off), int(n_blocks), _ptr(consumed), _ptr(stop), _ptr(need))
+        if r < 0:
+            native.raise_for_status(r)
+
+    def window_host(self, op, flags, src, dst_cap, compress=False):
+        """achip_window_decompress / achip_window_compress: ONE window in host memory (`src`: bytes-like), staged through the context's pinned buffer; synchronous.
+        -> (consumed, output bytes, stop, need, status, err_off)"""
+        src = np.frombuffer(bytes(src), dtype=np.uint8)
+        dst = np.empty(max(int(dst_cap), 1), dtype=np.uint8)
+        consumed, produced, need, err = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        stop = ctypes.c_int32()
+        fn = self.lib.achip_window_compress if compress else self.lib.achip_window_decompress
+        r = fn(self.native.ctx, int(op), int(flags), src.ctypes.data if len(src) else None, len(src), dst.ctypes.data, int(dst_cap), ctypes.byref(consumed),
+               ctypes.byref(produced), ctypes.byref(stop), ctypes.byref(need), ctypes.byref(err))
+        if r < 0 and stop.value != native.STOP_FAILED:
+            native.raise_for_status(r)  # (the call itself failed: arguments, the device)
+        return consumed.value, dst[:produced.value].tobytes(), stop.value, need.value, r, err.value
+
     def run_host_mixed(self, ops, src, src_off, src_len, dst, dst_off, dst_cap):
         """Host numpy arrays in/out through achip_mixed_batch_host: one op per item."""
         n = len(src_off)

@@ -6,7 +6,8 @@
 
 using namespace achip::host;
 
-namespace {
+namespace achip {
+namespace host ACHIP_HIDDEN {
 
 // pinned + device staging for bytes that arrive in host memory (grown on demand, at least 1 MiB)
 int32_t ensure_stage(achip_ctx* ctx, int64_t bytes)
@@ -26,7 +27,8 @@ int32_t ensure_stage(achip_ctx* ctx, int64_t bytes)
     return 0;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace achip
 
 // The body of every hash batch: its checks (countName: what the count is called in its error text), then its launch -- a macro, so that a failed launch is
 // reported by the call's own text.

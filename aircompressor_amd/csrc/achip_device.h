@@ -41,6 +41,14 @@ struct BatchArgs {
     int32_t countLo = 0, countHi = 0x7FFFFFFF;
 };
 
+// What a window call (achip_window_*: a batch whose items are pieces of streams that begin at unit boundaries) has beside a batch's arrays
+struct WindowArgs {
+    const int32_t* __restrict__ flags;  // per window: ACHIP_WINDOW_FIRST | ACHIP_WINDOW_LAST
+    int64_t* __restrict__ consumed;     // bytes of the window taken: whole units only
+    int32_t* __restrict__ stop;         // ACHIP_STOP_*
+    int64_t* __restrict__ need;         // NEED_INPUT: window bytes the next unit wants (0: unknown); NEED_ROOM: the room it wants
+};
+
 __device__ __forceinline__ int32_t batch_count(const BatchArgs& a) { return a.nBlocksDev != nullptr ? *a.nBlocksDev : a.nBlocks; }
 
 __host__ __device__ __forceinline__ constexpr int32_t mk_status(int cls, int detail) { return -(cls + 16 * detail); }

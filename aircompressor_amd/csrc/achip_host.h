@@ -1,6 +1,6 @@
 // achip_host.h -- what the host units of libaircompressor_hip.so share (private to csrc/, not installed): the context, the owners of device resources, the
 // error helpers, and the few functions one unit calls in another.  The units: abi_context.cpp (context, statuses, sizes), abi_dispatch.cpp (scratch policy, the
-// device-resident batch entry points), abi_hash.cpp, abi_host_batch.cpp (the host-pointer pipeline), abi_zstd_stream.cpp (the incremental Zstd reader and writer).
+// device-resident batch entry points), abi_hash.cpp, abi_host_batch.cpp (the host-pointer pipeline), abi_window.cpp (windows over the chunked containers), abi_zstd_stream.cpp (the incremental Zstd reader and writer).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -175,6 +175,8 @@ int32_t ensure_scratch(achip_ctx* ctx, int64_t bytes);            // frees what 
 int32_t grow_scratch_keeping_old(achip_ctx* ctx, int64_t bytes);  // allocates first, frees the old scratch only when that worked
 void* zstd_mb_scratch(void* user, int64_t bytes);                 // the context's second, lazily grown buffer (ZstdMbProvider::get, AuxScratch)
 int32_t launch_op(int32_t op, achip_ctx* ctx, const BatchArgs& args);
+// abi_hash.cpp
+int32_t ensure_stage(achip_ctx* ctx, int64_t bytes);  // the context's hostStage / devStage pair holds at least this much (the stream is idle when it had to grow)
 
 }  // namespace host
 }  // namespace achip

@@ -109,6 +109,16 @@ hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void
 int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize);
 hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize);
 int64_t hadoop_compress_scratch_bytes(int32_t nStreams);
+// ... and their window forms (WindowArgs, achip_device.h): an item is a piece of a stream that begins at a unit boundary; `w` says per item what was taken and why the call stopped
+hipError_t launch_snappyframed_window_decompress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
+int64_t snappyframed_window_decompress_scratch_bytes(int32_t nStreams);
+hipError_t launch_snappyframed_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch);
+int64_t snappyframed_window_compress_scratch_bytes(int32_t nStreams);
+hipError_t launch_hadoop_window_decompress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux,
+                                           const KernelSettings& ks);
+int64_t hadoop_window_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize);
+hipError_t launch_hadoop_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize);
+int64_t hadoop_window_compress_scratch_bytes(int32_t nStreams);
 
 // ---- decoded sizes and the output planner (decoded_size.hip) ----
 // A batch to be sized: item i reads srcBase[srcOff[i] .. + srcLen[i]) and reports outSize[i], status[i], errOffset[i]

@@ -38,6 +38,7 @@
 #include "snappy_compress_mw.h"
 #include "achip_launch.h"
 #include "achip_lists.h"
+#include "achip_window.h"
 
 namespace achip {
 
@@ -348,6 +349,207 @@ __global__ __launch_bounds__(64) void hadoop_serial_decompress_kernel(BatchArgs 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// the general reader over a WINDOW (achip_window_decompress_batch): the same Java loops, a unit at a time.  At every unit boundary the reader is a fresh
+// one over what is left of the window and of the destination, so whatever it reports is what the one-shot reader reports there; the end of the input in
+// front of a whole unit is a stop, not an error.
+struct WindowEnd {
+    int32_t consumed, produced, stop;
+    int64_t need;
+    int32_t status;
+    int64_t eo;
+};
+
+__device__ __forceinline__ bool is_truncation(int32_t st)
+{
+    return st == mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_HDP_TRUNCATED_INT) || st == mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_HDP_EOF_BLOCK_DATA);
+}
+
+// A block that does not fit what the destination has left: is it whole?  The reader's loop over its chunks without delivering a byte -- an LZ4 chunk is
+// decoded into the stream's own buffer (what it produces is known no other way), a Snappy chunk announces it.  0: whole (a chunk the reader would refuse
+// ends the unit too); STREAM_EOF or a truncation status: the window ends inside it.
+template <bool SNAPPY>
+__device__ int32_t skip_unit(Reader& r)
+{
+    for (;;) {
+        const int32_t clen = next_chunk(r);
+        if (clen < 0) {
+            return clen == STREAM_EOF || is_truncation(clen) ? clen : 0;
+        }
+        int32_t w;
+        if (SNAPPY) {
+            int32_t beo = 0;
+            w = snappy_announced(r.chunk, clen, beo);
+            if (w <= 0 || w > r.blockLen) {
+                return 0;
+            }
+        }
+        else {
+            w = lz4_decode(r, r.chunk, clen, r.internal, r.internalLen);
+            if (w < 0) {
+                return 0;
+            }
+        }
+        r.chunkLen = w;
+        r.chunkOff = w;
+        if (r.blockLen == r.chunkOff) {
+            return 0;
+        }
+    }
+}
+
+template <bool SNAPPY>
+__device__ void window_item(const uint8_t* in, int32_t inLen, uint8_t* out, int32_t outCap, bool last, uint8_t* internal, int32_t internalMax, int32_t bufferSize, uint8_t* lds,
+                            int lane, int32_t base, int32_t done, WindowEnd& e)
+{
+    Reader r;
+    r.internal = internal;
+    r.internalMax = internalMax;
+    r.lds = lds;
+    r.lane = lane;
+    r.snappy = SNAPPY;
+    e.need = 0;
+    e.status = 0;
+    e.eo = 0;
+    for (;;) {
+        // a unit boundary: a fresh reader over what is left of the window
+        auto fresh = [&]() {
+            r.in = in + base;
+            r.n = inLen - base;
+            r.pos = 0;
+            r.blockLen = 0;
+            r.chunkOff = 0;
+            r.chunkLen = 0;
+            r.internalLen = SNAPPY ? 0 : bufferSize + 8;
+            r.chunk = r.in;
+            r.eo = 0;
+        };
+        fresh();
+        e.consumed = base;
+        e.produced = done;
+        if (r.n == 0) {
+            e.stop = ACHIP_STOP_END;
+            return;
+        }
+        const int32_t room = outCap - done;
+        const int32_t u = r.n >= 4 ? rd_be(r.in) : 0;
+        if (r.n >= 4 && u == 0) {
+            base += 4;  // a zero length word
+            continue;
+        }
+        const bool fits = u <= room;
+        if (!fits) {
+            const int32_t whole = skip_unit<SNAPPY>(r);
+            if (whole == 0) {
+                e.stop = ACHIP_STOP_NEED_ROOM;
+                e.need = u;
+                return;
+            }
+            if (!last) {
+                e.stop = ACHIP_STOP_NEED_INPUT;
+                e.need = whole == mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_HDP_EOF_BLOCK_DATA) ? (int64_t)r.pos + rd_be(r.in + r.pos - 4) : 0;
+                return;
+            }
+            fresh();  // the stream ends inside this block: the reader decides, as in the one-shot call
+        }
+        int32_t result = 0, got = 0;
+        bool closed = false;  // HadoopCodecDecompressor's one more read() behind its loop has been made
+        for (;;) {
+            if (got >= room) {  // (the loop ends here)
+                const int32_t b = SNAPPY ? snappy_read(r, nullptr, 0, true) : lz4_read(r, nullptr, 0, true);
+                if (b >= 0) {
+                    r.eo = r.pos;
+                    result = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_HDP_NOT_CONSUMED);
+                }
+                else {
+                    result = b;
+                }
+                closed = true;
+                break;
+            }
+            const int32_t size = SNAPPY ? snappy_read(r, out + done + got, room - got, false) : lz4_read(r, out + done + got, room - got, false);
+            if (size < 0) {
+                result = size;
+                break;
+            }
+            got += size;
+            if (r.blockLen == r.chunkOff && r.chunkOff >= r.chunkLen) {
+                result = 0;  // the block is complete
+                break;
+            }
+        }
+        if (result == 0) {
+            done += got;
+            base += r.pos;
+            continue;
+        }
+        bool ended = false;
+        if (result == STREAM_EOF && last) {  // the reader's stream ends here: the one more read() decides, as in the one-shot call
+            ended = true;
+            if (!closed) {
+                const int32_t b = SNAPPY ? snappy_read(r, nullptr, 0, true) : lz4_read(r, nullptr, 0, true);
+                if (b >= 0) {
+                    r.eo = r.pos;
+                    result = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_HDP_NOT_CONSUMED);
+                }
+                else {
+                    result = b;
+                }
+            }
+            if (result == STREAM_EOF) {
+                e.consumed = inLen;
+                e.produced = done + got;
+                e.stop = ACHIP_STOP_END;
+                return;
+            }
+        }
+        if (!ended && (result == STREAM_EOF || (is_truncation(result) && !last))) {
+            e.stop = ACHIP_STOP_NEED_INPUT;
+            e.need = result == mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_HDP_EOF_BLOCK_DATA) ? (int64_t)r.pos + rd_be(r.in + r.pos - 4) : 0;
+            return;
+        }
+        if (!fits && result == mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_HDP_NOT_CONSUMED)) {
+            e.stop = ACHIP_STOP_NEED_ROOM;
+            e.need = u;
+            return;
+        }
+        e.stop = ACHIP_STOP_FAILED;
+        e.status = result;
+        e.eo = (int64_t)base + r.eo;
+        return;
+    }
+}
+
+template <bool SNAPPY>
+__global__ __launch_bounds__(64) void hadoop_serial_window_kernel(BatchArgs a, WindowArgs w, uint8_t* internals, int32_t internalMax, int32_t bufferSize, int32_t* nextItem,
+                                                                  const int32_t* only, const int32_t* startPos, const int32_t* startOut)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[IN_RING + OUT_RING];
+    __shared__ int32_t item;
+    const int lane = threadIdx.x;
+    uint8_t* internal = internals + (size_t)blockIdx.x * (size_t)internalMax;
+    for (;;) {
+        __syncthreads();
+        if (lane == 0) {
+            item = atomicAdd(nextItem, 1);
+        }
+        __syncthreads();
+        const int32_t s = item;
+        if (s >= a.nBlocks) {
+            return;
+        }
+        if (only[s] == 0) {
+            continue;  // finished by the chunk-parallel path
+        }
+        WindowEnd e;
+        window_item<SNAPPY>(a.srcBase + a.srcOff[s], a.srcLen[s], a.dstBase + a.dstOff[s], a.dstCap[s], (w.flags[s] & ACHIP_WINDOW_LAST) != 0, internal, internalMax, bufferSize, lds,
+                            lane, startPos[s], startOut[s], e);
+        if (lane == 0) {
+            win::report(a, w, s, e.consumed, e.produced, e.stop, e.need, e.status, e.eo);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // the chunk-parallel reader
 struct ChunkList : lists::ChunkBatch {  // per chunk: a batch for the block decoders (counters [16..]: probe statistics of the decoders' choice, [32] serial cursor) ...
     int32_t* cExpect;   // ... and the block length it has to produce
@@ -368,10 +570,22 @@ struct ChunkList : lists::ChunkBatch {  // per chunk: a batch for the block deco
     }
 };
 
+// A window's walk (achip_window_decompress_batch): where it stopped and why, and what it may list.
+struct WindowWalk {
+    bool last;           // ACHIP_WINDOW_LAST: an incomplete tail is the reader's truncation error, not a stop
+    int32_t maxChunks;   // the list has room for this many
+    int32_t* cUnit;      // per listed chunk: where its unit begins in the window
+    int32_t pos;         // out: the end of the units walked
+    int32_t stop;        // out: ACHIP_STOP_END / _NEED_INPUT / _NEED_ROOM (the list is full: need 0), or win::STOP_SERIAL
+    int64_t need;
+};
+
 // The Java loops over one stream without the chunk bodies; returns false when the stream is not of the simple shape (the serial kernel
 // then decodes it).  FILL = false: count the chunks; true: write their descriptors.
-template <bool SNAPPY, bool FILL>
-__device__ bool walk_stream(const BatchArgs& a, const ChunkList& L, int32_t stream, int32_t first, int32_t& countOut, int32_t& outOut)
+// WINDOW: the stream is a window.  The walk stops in front of the first unit that is not whole, does not fit or is not of the simple shape, says which in
+// `w` and returns true: the units in front of it are listed.
+template <bool SNAPPY, bool FILL, bool WINDOW = false>
+__device__ bool walk_stream(const BatchArgs& a, const ChunkList& L, int32_t stream, int32_t first, int32_t& countOut, int32_t& outOut, WindowWalk* w = nullptr)
 {
     const uint8_t* __restrict__ in = a.srcBase + a.srcOff[stream];
     const int32_t inLen = a.srcLen[stream];
@@ -379,28 +593,34 @@ __device__ bool walk_stream(const BatchArgs& a, const ChunkList& L, int32_t stre
     int32_t pos = 0, o = 0, n = 0;
     countOut = 0;
     outOut = 0;
+#define WALK_STOP(at, why, want)   \
+    {                              \
+        if (WINDOW) {              \
+            w->pos = (at);         \
+            w->stop = (why);       \
+            w->need = (want);      \
+            countOut = n;          \
+            outOut = o;            \
+        }                          \
+        return WINDOW;             \
+    }
     while (pos < inLen) {
-        if (inLen - pos < 4) {
-            return false;
-        }
+        const int32_t unit = pos;
+        if (WINDOW && n >= w->maxChunks) WALK_STOP(unit, ACHIP_STOP_NEED_ROOM, 0);
+        if (inLen - pos < 4) WALK_STOP(unit, w->last ? win::STOP_SERIAL : ACHIP_STOP_NEED_INPUT, 0);
         const int32_t u = rd_be(in + pos);
         pos += 4;
         if (u == 0) {
             continue;  // `while (uncompressedBlockLength == 0)`
         }
-        if (u < 0 || inLen - pos < 4) {
-            return false;
-        }
+        if (u < 0 || inLen - pos < 4) WALK_STOP(unit, u < 0 || w->last ? win::STOP_SERIAL : ACHIP_STOP_NEED_INPUT, 0);
         const int32_t clen = rd_be(in + pos);
         pos += 4;
-        if (clen < 0 || clen > inLen - pos || u > outCap - o) {
-            return false;
-        }
+        if (WINDOW && clen >= 0 && clen > inLen - pos && !w->last) WALK_STOP(unit, ACHIP_STOP_NEED_INPUT, (int64_t)clen + 8);
+        if (clen < 0 || clen > inLen - pos || u > outCap - o) WALK_STOP(unit, win::STOP_SERIAL, 0);
         if (SNAPPY) {
             int32_t beo = 0;
-            if (snappy_announced(in + pos, clen, beo) != u) {
-                return false;
-            }
+            if (snappy_announced(in + pos, clen, beo) != u) WALK_STOP(unit, win::STOP_SERIAL, 0);
         }
         if (FILL) {
             const int32_t c = first + n;
@@ -409,10 +629,19 @@ __device__ bool walk_stream(const BatchArgs& a, const ChunkList& L, int32_t stre
             L.cDstOff[c] = a.dstOff[stream] + o;
             L.cDstCap[c] = outCap - o;  // (what the Java reader hands its block decoder: the rest of the caller's buffer)
             L.cExpect[c] = u;
+            if (WINDOW) {
+                w->cUnit[c] = unit;
+            }
         }
         n++;
         o += u;
         pos += clen;
+    }
+#undef WALK_STOP
+    if (WINDOW) {
+        w->pos = pos;
+        w->stop = ACHIP_STOP_END;
+        w->need = 0;
     }
     countOut = n;
     outOut = o;
@@ -469,6 +698,99 @@ __global__ __launch_bounds__(64) void hadoop_fold_kernel(BatchArgs a, ChunkList 
     }
 }
 
+// ---- the window forms of walk and fold (achip_window_decompress_batch) ----
+struct WindowList : ChunkList {
+    int32_t* cUnit;   // per chunk: where its unit begins in its window
+    int32_t* sPos;    // per window: where the walk stopped; after the fold: where the serial kernel starts ...
+    int32_t* sStart;  // ... and with how many bytes delivered
+    int32_t* sStop;
+    int64_t* sNeed;
+    void carve(lists::Carver& k, int64_t nStreams)
+    {
+        ChunkList::carve(k, nStreams);
+        sNeed = k.take<int64_t>(nStreams);
+        sPos = k.take<int32_t>(nStreams);
+        sStart = k.take<int32_t>(nStreams);
+        sStop = k.take<int32_t>(nStreams);
+        cUnit = k.take<int32_t>(CAPACITY);
+    }
+};
+
+// a lane per window: the leading units of the writer's shape that are whole and fit go on the list -- as many as the list has room for
+template <bool SNAPPY>
+__global__ __launch_bounds__(64) void hadoop_window_walk_kernel(BatchArgs a, WindowList L, WindowArgs w)
+{
+    const int32_t stream = blockIdx.x * 64 + threadIdx.x;
+    if (stream >= a.nBlocks) {
+        return;
+    }
+    L.sFirst[stream] = 0;
+    L.sCount[stream] = 0;
+    L.sOut[stream] = 0;
+    L.sPos[stream] = 0;
+    L.sNeed[stream] = 0;
+    if (a.srcLen[stream] < 0 || a.dstCap[stream] < 0) {
+        L.sStop[stream] = ACHIP_STOP_FAILED;
+        L.sSerial[stream] = 0;
+        return;
+    }
+    WindowWalk ww;
+    ww.last = (w.flags[stream] & ACHIP_WINDOW_LAST) != 0;
+    ww.maxChunks = 0x7FFFFFFF;
+    ww.cUnit = L.cUnit;
+    int32_t n = 0, out = 0;
+    walk_stream<SNAPPY, false, true>(a, L, stream, 0, n, out, &ww);
+    const int32_t first = n > 0 ? atomicAdd(L.counters, n) : 0;
+    if ((int64_t)first + n > CAPACITY) {  // the list takes what fits; with no room at all the serial kernel makes the progress
+        ww.maxChunks = first < CAPACITY ? CAPACITY - first : 0;
+        walk_stream<SNAPPY, false, true>(a, L, stream, 0, n, out, &ww);
+        if (n == 0) {
+            ww.stop = win::STOP_SERIAL;
+        }
+    }
+    if (n > 0) {
+        walk_stream<SNAPPY, true, true>(a, L, stream, first, n, out, &ww);
+    }
+    L.sFirst[stream] = first;
+    L.sCount[stream] = n;
+    L.sOut[stream] = out;
+    L.sPos[stream] = ww.pos;
+    L.sStop[stream] = ww.stop;
+    L.sNeed[stream] = ww.need;
+    L.sSerial[stream] = 0;
+}
+
+// a lane per window: the prefix of its listed chunks that decoded to their blocks' lengths is delivered; behind it the walk's stop stands, or the serial
+// kernel goes on (sSerial, from sPos / sStart)
+__global__ __launch_bounds__(64) void hadoop_window_fold_kernel(BatchArgs a, WindowList L, WindowArgs w)
+{
+    const int32_t stream = blockIdx.x * 64 + threadIdx.x;
+    if (stream >= a.nBlocks) {
+        return;
+    }
+    if (L.sStop[stream] == ACHIP_STOP_FAILED) {
+        win::report(a, w, stream, 0, 0, ACHIP_STOP_FAILED, 0, mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT), 0);
+        return;
+    }
+    const int32_t first = L.sFirst[stream], n = L.sCount[stream];
+    int32_t pos = L.sPos[stream], out = L.sOut[stream], stop = L.sStop[stream];
+    for (int32_t k = 0; k < n; k++) {
+        if (L.cStatus[first + k] != 0 || L.cOutLen[first + k] != L.cExpect[first + k]) {
+            pos = L.cUnit[first + k];
+            out = (int32_t)(L.cDstOff[first + k] - a.dstOff[stream]);
+            stop = win::STOP_SERIAL;  // the Java loops decide what this chunk means
+            break;
+        }
+    }
+    if (stop == win::STOP_SERIAL) {
+        L.sSerial[stream] = 1;
+        L.sPos[stream] = pos;
+        L.sStart[stream] = out;
+        return;
+    }
+    win::report(a, w, stream, pos, out, stop, L.sNeed[stream], 0, 0);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // the writer
 using BlockList = lists::WriterList;  // (bSize: a chunk's compressed bytes, or the block encoder's status)
@@ -502,6 +824,54 @@ __global__ __launch_bounds__(64) void hadoop_plan_kernel(BatchArgs a, BlockList 
         st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_UNSUPPORTED);
     }
     L.sStatus[stream] = st;
+}
+
+// The window form of the plan (achip_window_compress_batch): the full blocks the window holds and the destination has worst-case room for are taken, the
+// partial tail only under ACHIP_WINDOW_LAST; taken[] is what the encode and compact kernels see as the input's length.
+template <bool SNAPPY>
+__global__ __launch_bounds__(64) void hadoop_window_plan_kernel(BatchArgs a, BlockList L, int32_t bufferSize, WindowArgs w, int32_t* taken)
+{
+    const int32_t stream = blockIdx.x * 64 + threadIdx.x;
+    if (stream >= a.nBlocks) {
+        return;
+    }
+    const int32_t inLen = a.srcLen[stream], cap = a.dstCap[stream];
+    const int32_t chunk = input_max_size(SNAPPY, bufferSize);
+    int32_t st = 0, stop = ACHIP_STOP_END;
+    int64_t blocks = 0, consumed = 0, need = 0;
+    if (inLen < 0 || cap < 0 || chunk <= 0) {
+        st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT);
+    }
+    else {
+        const int64_t worst = 8 + block_bound(SNAPPY, chunk);
+        const int64_t full = inLen / chunk, rest = inLen % chunk;
+        blocks = full < cap / worst ? full : cap / worst;
+        consumed = blocks * chunk;
+        if (blocks < full) {
+            stop = ACHIP_STOP_NEED_ROOM;
+            need = worst;
+        }
+        else if (rest > 0 && (w.flags[stream] & ACHIP_WINDOW_LAST) == 0) {
+            stop = ACHIP_STOP_NEED_INPUT;
+            need = chunk;
+        }
+        else if (rest > 0 && cap - blocks * worst < 8 + block_bound(SNAPPY, rest)) {
+            stop = ACHIP_STOP_NEED_ROOM;
+            need = 8 + block_bound(SNAPPY, rest);
+        }
+        else if (rest > 0) {
+            blocks++;
+            consumed += rest;
+        }
+    }
+    if (!lists::plan_entries(L, stream, st == 0 ? (int32_t)blocks : 0)) {  // (more than a million chunks in one call)
+        st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_UNSUPPORTED);
+    }
+    L.sStatus[stream] = st;
+    taken[stream] = st == 0 ? (int32_t)consumed : 0;
+    w.consumed[stream] = st == 0 ? consumed : 0;
+    w.stop[stream] = st == 0 ? stop : ACHIP_STOP_FAILED;
+    w.need[stream] = st == 0 ? need : 0;
 }
 
 // LZ4: a wavefront per workgroup around its table in LDS.  Snappy (round 3): the two tiers of the block encoder (snappy_compress.hip) -- a 32 KB
@@ -667,6 +1037,52 @@ hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void
     return hipGetLastError();
 }
 
+// ---- windows (achip_window_decompress_batch / _compress_batch) ----
+static uint8_t* carve_hadoop_window_reader(lists::Carver& k, hdp::WindowList& L, int64_t nStreams, int32_t bufferSize)
+{
+    L.carve(k, nStreams);
+    return k.take<uint8_t>((nStreams < HDP_SERIAL_WAVES ? nStreams : HDP_SERIAL_WAVES) * hdp_internal_bytes(bufferSize));
+}
+
+int64_t hadoop_window_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize)
+{
+    lists::Carver k(nullptr);
+    hdp::WindowList L;
+    carve_hadoop_window_reader(k, L, nStreams < 1 ? 1 : nStreams, bufferSize);
+    return k.used();
+}
+
+// walk -> seal -> the listed chunks through the block decoders (as the one-shot reader's variants 1 .. 3) -> fold -> the wavefront-per-stream kernel for the
+// windows the fold could not finish
+hipError_t launch_hadoop_window_decompress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant,
+                                           const AuxScratch* aux, const KernelSettings& ks)
+{
+    if (a.nBlocks <= 0) {
+        return hipSuccess;
+    }
+    lists::Carver k(scratch);
+    hdp::WindowList L;
+    uint8_t* internals = carve_hadoop_window_reader(k, L, a.nBlocks, bufferSize);
+    int32_t* counters = L.counters;
+    hipError_t e = hipMemsetAsync(counters, 0, 4096, stream);
+    if (e != hipSuccess) return e;
+    const int64_t internalMax = hdp_internal_bytes(bufferSize);
+    const unsigned serialGrid = (unsigned)(a.nBlocks < HDP_SERIAL_WAVES ? a.nBlocks : HDP_SERIAL_WAVES);
+    const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
+    if (snappy) hipLaunchKernelGGL(hdp::hadoop_window_walk_kernel<true>, dim3(perStream), dim3(64), 0, stream, a, L, w);
+    else hipLaunchKernelGGL(hdp::hadoop_window_walk_kernel<false>, dim3(perStream), dim3(64), 0, stream, a, L, w);
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, counters, lists::CAPACITY);
+    const bool sync = (variant == 2 || variant == 3) && aux != nullptr && aux->get != nullptr;
+    const ListedWant want{sync, variant == 3, true, ((int64_t)(bufferSize > 65536 ? bufferSize : 65536) + 65535) / 65536, -1};
+    bool decoded = false;
+    e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), snappy ? 1 : 0, stream, counters, counters + 16, aux, ks, want, &decoded);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hdp::hadoop_window_fold_kernel, dim3(perStream), dim3(64), 0, stream, a, L, w);
+    if (snappy) hipLaunchKernelGGL(hdp::hadoop_serial_window_kernel<true>, dim3(serialGrid), dim3(64), 0, stream, a, w, internals, (int32_t)internalMax, bufferSize, counters + 32, (const int32_t*)L.sSerial, (const int32_t*)L.sPos, (const int32_t*)L.sStart);
+    else hipLaunchKernelGGL(hdp::hadoop_serial_window_kernel<false>, dim3(serialGrid), dim3(64), 0, stream, a, w, internals, (int32_t)internalMax, bufferSize, counters + 32, (const int32_t*)L.sSerial, (const int32_t*)L.sPos, (const int32_t*)L.sStart);
+    return hipGetLastError();
+}
+
 namespace {
 constexpr int HADOOP_SNAPPY_WORKGROUPS = 256 * 5;  // five 32 KB LDS tables per CU, four wavefronts around each
 constexpr int64_t HADOOP_SNAPPY_SLAB_WORDS = (int64_t)HADOOP_SNAPPY_WORKGROUPS * 3 * snc::MAX_HASH_TABLE_SIZE;
@@ -711,6 +1127,48 @@ hipError_t launch_hadoop_compress(const BatchArgs& a, hipStream_t stream, void* 
         hipLaunchKernelGGL(hdp::hadoop_encode_kernel<false>, dim3(encodeGrid), dim3(64), 0, stream, a, L, bufferSize, slabs);
         hipLaunchKernelGGL(hdp::hadoop_compact_kernel<false>, dim3(compactGrid), dim3(64), 0, stream, a, L, bufferSize);
     }
+    return hipGetLastError();
+}
+
+int64_t hadoop_window_compress_scratch_bytes(int32_t nStreams)
+{
+    lists::Carver k(nullptr);
+    hdp::BlockList L;
+    carve_hadoop_writer(k, L, nStreams < 1 ? 1 : nStreams);
+    k.take<int32_t>(nStreams < 1 ? 1 : nStreams);
+    return k.used();
+}
+
+// the window plan, then the one-shot writer's encode and compact kernels over what the plan took
+hipError_t launch_hadoop_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize)
+{
+    if (a.nBlocks <= 0) {
+        return hipSuccess;
+    }
+    lists::Carver k(scratch);
+    hdp::BlockList L;
+    uint16_t* const slabs = carve_hadoop_writer(k, L, a.nBlocks);
+    int32_t* const taken = k.take<int32_t>(a.nBlocks);
+    hipError_t e = hipMemsetAsync(L.counters, 0, 4096, stream);
+    if (e != hipSuccess) return e;
+    BatchArgs t = a;
+    t.srcLen = taken;
+    const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
+    const unsigned encodeGrid = snappy ? HADOOP_SNAPPY_WORKGROUPS : 256 * 10;
+    const unsigned compactGrid = (unsigned)a.nBlocks;
+    if (snappy) {
+        hipLaunchKernelGGL(hdp::hadoop_window_plan_kernel<true>, dim3(perStream), dim3(64), 0, stream, a, L, bufferSize, w, taken);
+        hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, lists::CAPACITY);
+        hipLaunchKernelGGL(hdp::hadoop_encode_kernel<true>, dim3(encodeGrid), dim3(256), 0, stream, t, L, bufferSize, slabs);
+        hipLaunchKernelGGL(hdp::hadoop_compact_kernel<true>, dim3(compactGrid), dim3(64), 0, stream, t, L, bufferSize);
+    }
+    else {
+        hipLaunchKernelGGL(hdp::hadoop_window_plan_kernel<false>, dim3(perStream), dim3(64), 0, stream, a, L, bufferSize, w, taken);
+        hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, lists::CAPACITY);
+        hipLaunchKernelGGL(hdp::hadoop_encode_kernel<false>, dim3(encodeGrid), dim3(64), 0, stream, t, L, bufferSize, slabs);
+        hipLaunchKernelGGL(hdp::hadoop_compact_kernel<false>, dim3(compactGrid), dim3(64), 0, stream, t, L, bufferSize);
+    }
+    hipLaunchKernelGGL(win::writer_verdict_kernel, dim3(perStream), dim3(64), 0, stream, a, w);
     return hipGetLastError();
 }
 

@@ -11,6 +11,9 @@ LIBRARY_PATH = os.path.join(_HERE, "libaircompressor_hip.so")
 
 CLASS_MALFORMED, CLASS_OUTPUT_TOO_SMALL, CLASS_INVALID_ARGUMENT, CLASS_DEVICE = 1, 2, 3, 4
 DETAIL_LZ4_EMPTY_OUTPUT = 7
+# achip_window_*: a window's flags and why a call stopped (include/aircompressor_hip.h)
+WINDOW_FIRST, WINDOW_LAST = 1, 2
+STOP_END, STOP_NEED_INPUT, STOP_NEED_ROOM, STOP_FAILED = 0, 1, 2, 3
 
 _i32, _i64, _vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 _BATCH = [_vp] * 10 + [_i32]
@@ -113,6 +116,10 @@ SIGNATURES = {
     "achip_plan_outputs": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "achip_compress_bound_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32]),
     "achip_pack_outputs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "achip_window_decompress_batch": (_i32, [_vp, _i32, _vp] + _BATCH[1:] + [_vp, _vp, _vp]),
+    "achip_window_compress_batch": (_i32, [_vp, _i32, _vp] + _BATCH[1:] + [_vp, _vp, _vp]),
+    "achip_window_decompress": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32] + [ctypes.POINTER(_i64)] * 2 + [ctypes.POINTER(_i32)] + [ctypes.POINTER(_i64)] * 2),
+    "achip_window_compress": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32] + [ctypes.POINTER(_i64)] * 2 + [ctypes.POINTER(_i32)] + [ctypes.POINTER(_i64)] * 2),
     "achip_multi_batch_host": (_i32, [_vp, _i32, _i32, _vp] + _BATCH[1:] + [_vp]),
     "achip_partition_blocks": (_i32, [_vp, _i32, _i32, _vp]),
 }

@@ -526,6 +526,57 @@ int32_t achip_zstdstream_compress_feed(achip_ctx* ctx, void* state, const void* 
 int32_t achip_zstdstream_compress_finish(achip_ctx* ctx, void* state, void* dst, int64_t dstCap, int64_t* produced);
 int32_t achip_zstdstream_compress_end(achip_ctx* ctx, void* state);
 
+/* ---- Windows over the chunked containers (SURVEY L4 streams): x-snappy-framed, Hadoop LZ4 and Hadoop Snappy streams of any length in bounded memory ----
+ * What SnappyFramedInputStream / SnappyFramedOutputStream, Lz4HadoopInputStream / Lz4HadoopOutputStream and SnappyHadoopInputStream /
+ * SnappyHadoopOutputStream (and the HadoopStreams factories that hand them out) do a read() / write() at a time.  These formats' chunks are independent, so the
+ * incremental form needs no state: the CALLER keeps the stream position, the library keeps nothing between calls, and many streams' windows run side by side in
+ * one call, chunk-parallel on the device.
+ * A WINDOW is a piece of one stream that begins at a unit boundary.  A UNIT is what the format's reader reads as one step -- x-snappy-framed: one chunk of any
+ * type (the 10-byte stream identifier and skippable chunks included); Hadoop: one zero length word, or one block: [BE plaintext length] and every
+ * [BE compressed length][codec block] chunk the reader reads for it.  A unit is WHOLE when all the bytes its reader would read for it are in the window.
+ * codecOp: ACHIP_OP_SNAPPYFRAMED_ / LZ4HADOOP_ / SNAPPYHADOOP_ DECOMPRESS for the decompress calls, the three _COMPRESS ops for the compress calls; anything else is
+ * INVALID_ARGUMENT, decided before the context is touched.  Batch calls: every array (flags too) device-accessible, asynchronous on the ctx stream, scratch from the
+ * context, nBlocks == 0 launches nothing; the Hadoop ops use the context's "hadoop.buffer_size".
+ * DECODE, window W with room dstCap: the call takes k leading whole units.  consumed = their bytes; outLen and the destination are what the op's one-shot reader
+ * yields for those bytes with the same dstCap (a window without FIRST: for those bytes behind a stream identifier).  If the first unit is whole, fits and decodes,
+ * k >= 1; units of the writer's shape (Hadoop: one chunk per block that produces the declared length; x-snappy-framed: any well-formed chunk) are ALL taken in one
+ * call as far as they are whole, fit and decode -- listed by a walk, decoded side by side, the prefix found by a fold; units of any other shape are taken by a
+ * wavefront per window, at least one per call.  stop says why the call took no more:
+ *   END         consumed == srcLen.
+ *   NEED_INPUT  the next unit is not whole and LAST is not set -- whatever the partial bytes look like.  need = the window bytes that unit wants, counted from its
+ *               start, as far as its headers tell; 0 if they do not.  (A Hadoop end-of-stream marker -- a length word of -1; for LZ4 any negative chunk length --
+ *               leaves its unit not whole: the one-shot reader reads once more behind the end it announces, so its verdict waits for LAST.)
+ *   NEED_ROOM   the next unit is whole and its declared plaintext (the Hadoop block length, the Snappy preamble of a compressed chunk, length - 4 of a raw chunk)
+ *               exceeds dstCap - outLen: need = that length.  Takes the place of ACHIP_D_SNF_OUTPUT_TOO_SMALL / ACHIP_D_HDP_NOT_CONSUMED, which stay what they are in
+ *               the one-shot calls.  need == 0: the call's chunk list (2^20 entries for all its windows together) was full -- call again with what is left.
+ *   FAILED      status != 0: status, its detail and errOffset - consumed are what the one-shot reader reports for W[consumed:] with room dstCap - outLen; under LAST an
+ *               incomplete tail is among them (the one-shot reader's truncation errors).  Everything in front of the damage has been delivered: consumed and outLen
+ *               describe it (the feed contract of achip_zstdstream_decompress_feed).  x-snappy-framed checksums are verified as in the one-shot reader.
+ * ENCODE: consumed = the largest multiple of the writer's block size (x-snappy-framed: 64 KiB; Hadoop: bufferSize minus the codec's overhead, as the one-shot
+ * writer cuts) that the window holds and whose worst-case output fits dstCap; with LAST the partial tail block too.  The bytes written are the one-shot writer's for
+ * W[:consumed] -- the x-snappy-framed stream identifier only under FIRST, which a caller sets until the stream's first byte is out -- so the windows' outputs, one
+ * behind the other, are the one-shot writer's stream however the stream was cut.  NEED_INPUT: a partial block is left (need = the block size); NEED_ROOM: a block is
+ * left for want of room (need = its worst case: the codec's bound and the two Hadoop length words, or the chunk's 8 bytes of header and CRC and the block; plus the
+ * stream identifier's 10 bytes where not even they fit); FAILED only for argument faults (a negative length: INVALID_ARGUMENT). */
+#define ACHIP_WINDOW_FIRST 1   /* the window starts the stream (x-snappy-framed: the stream identifier is required / written) */
+#define ACHIP_WINDOW_LAST  2   /* the stream ends with this window */
+#define ACHIP_STOP_END        0  /* the whole window was taken */
+#define ACHIP_STOP_NEED_INPUT 1  /* the next unit is not whole (decode) / a partial block is left (encode) */
+#define ACHIP_STOP_NEED_ROOM  2  /* the next unit is whole but does not fit what dst has left */
+#define ACHIP_STOP_FAILED     3  /* status != 0 */
+int32_t achip_window_decompress_batch(achip_ctx* ctx, int32_t codecOp, const int32_t* flags, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, void* dstBase,
+                                      const int64_t* dstOff, const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t nBlocks,
+                                      int64_t* consumed, int32_t* stop, int64_t* need);
+int32_t achip_window_compress_batch(achip_ctx* ctx, int32_t codecOp, const int32_t* flags, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, void* dstBase,
+                                    const int64_t* dstOff, const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t nBlocks,
+                                    int64_t* consumed, int32_t* stop, int64_t* need);
+/* one HOST window, staged through the context's pinned buffer, synchronous; returns the window's status (0, or negative with *stop == ACHIP_STOP_FAILED) or a launch /
+ * argument failure; every out pointer is required */
+int32_t achip_window_decompress(achip_ctx* ctx, int32_t codecOp, int32_t flags, const void* src, int32_t srcLen, void* dst, int32_t dstCap,
+                                int64_t* consumed, int64_t* produced, int32_t* stop, int64_t* need, int64_t* errOffset);
+int32_t achip_window_compress(achip_ctx* ctx, int32_t codecOp, int32_t flags, const void* src, int32_t srcLen, void* dst, int32_t dstCap,
+                              int64_t* consumed, int64_t* produced, int32_t* stop, int64_t* need, int64_t* errOffset);
+
 /* Balanced contiguous partition of a batch over nParts GPUs: fills
  * starts[0..nParts] with block indices so that each part's sum of weight[i] is
  * as equal as a contiguous split allows.  Pure host arithmetic. */

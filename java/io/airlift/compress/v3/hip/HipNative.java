@@ -62,6 +62,13 @@ public final class HipNative
     public static final int OP_LZ4HADOOP_COMPRESS = 11;      // achip_lz4hadoop_compress
     public static final int OP_SNAPPYHADOOP_DECOMPRESS = 12; // achip_snappyhadoop_decompress
     public static final int OP_SNAPPYHADOOP_COMPRESS = 13;   // achip_snappyhadoop_compress
+    // achip_window_*: a window's flags and why a call stopped
+    public static final int WINDOW_FIRST = 1;
+    public static final int WINDOW_LAST = 2;
+    public static final int STOP_END = 0;
+    public static final int STOP_NEED_INPUT = 1;
+    public static final int STOP_NEED_ROOM = 2;
+    public static final int STOP_FAILED = 3;
     public static final int OP_ZSTDSTREAM_COMPRESS = 14;     // achip_zstdstream_compress (SURVEY 8f row 3: what a ZstdOutputStream puts on its sink)
 
     private record MethodHandles(
@@ -290,6 +297,16 @@ public final class HipNative
             MethodHandle eventElapsedMs,
             @NativeSignature(name = "achip_partition_blocks", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, MemorySegment.class})
             MethodHandle partitionBlocks,
+            // windows over the chunked containers: (ctx, codecOp, flags*, the batch arrays, nBlocks, consumed*, stop*, need*) and the single host window
+            // (ctx, codecOp, flags, src, srcLen, dst, dstCap, consumed*, produced*, stop*, need*, errOffset*)
+            @NativeSignature(name = "achip_window_decompress_batch", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle windowDecompressBatch,
+            @NativeSignature(name = "achip_window_compress_batch", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle windowCompressBatch,
+            @NativeSignature(name = "achip_window_decompress", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, MemorySegment.class, int.class, MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle windowDecompress,
+            @NativeSignature(name = "achip_window_compress", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, MemorySegment.class, int.class, MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle windowCompress,
             // sizing a device-resident batch: (ctx, codecOp, srcBase, srcOff*, srcLen*, outSize*, status*, errOffset*, nBlocks) and the planner
             // (ctx, outSize*, status*, nBlocks, align, dstOff*, dstCap*, total*)
             @NativeSignature(name = "achip_decoded_size_batch", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
@@ -1044,6 +1061,56 @@ public final class HipNative
             if (result < 0) {
                 throw toException(result, 0);
             }
+        }
+
+        /**
+         * achip_window_decompress_batch / achip_window_compress_batch: item i is a WINDOW of an x-snappy-framed or Hadoop stream -- a piece that begins at a unit
+         * boundary -- with {@code flags[i]} = {@link #WINDOW_FIRST} | {@link #WINDOW_LAST}.  The call takes the leading whole units that fit: {@code consumed[i]}
+         * (long) bytes of input, {@code outLen[i]} bytes of output; {@code stop[i]} ({@code STOP_*}) says why it took no more, {@code need[i]} (long) what the next
+         * unit wants.  What {@code SnappyFramedInputStream}, {@code Lz4HadoopInputStream}, {@code SnappyHadoopInputStream} and their output twins do a call at a
+         * time, for many streams side by side; the caller keeps the stream positions.  Asynchronous on this context's stream; all segments device-accessible.
+         */
+        public void windowBatch(boolean compress, int op, MemorySegment flags, MemorySegment srcBase, MemorySegment srcOff, MemorySegment srcLen, MemorySegment dstBase,
+                MemorySegment dstOff, MemorySegment dstCap, MemorySegment outLen, MemorySegment status, MemorySegment errOffset, int blocks, MemorySegment consumed,
+                MemorySegment stop, MemorySegment need)
+        {
+            int result;
+            try {
+                MethodHandle call = compress ? HANDLES.windowCompressBatch() : HANDLES.windowDecompressBatch();
+                result = (int) call.invokeExact(handle(), op, flags, srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, blocks, consumed, stop, need);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /**
+         * achip_window_decompress / achip_window_compress: ONE window in host memory, staged through this context's pinned buffer; synchronous.
+         * {@code result}: five longs -- consumed, produced, stop, need, error offset.  Returns the window's status: 0, or negative with stop == {@link #STOP_FAILED}
+         * (everything in front of the damage has been delivered); a failure of the call itself is thrown.
+         */
+        public int window(boolean compress, int op, int flags, MemorySegment src, int srcLength, MemorySegment dst, int dstCapacity, MemorySegment result)
+        {
+            int status;
+            try {
+                MethodHandle call = compress ? HANDLES.windowCompress() : HANDLES.windowDecompress();
+                status = (int) call.invokeExact(handle(), op, flags, src, srcLength, dst, dstCapacity, result, result.asSlice(8), result.asSlice(16), result.asSlice(24),
+                        result.asSlice(32));
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            if (status < 0 && result.get(java.lang.foreign.ValueLayout.JAVA_INT, 16) != STOP_FAILED) {
+                throwIfError(status, 0);
+            }
+            return status;
         }
 
         /**
