@@ -120,7 +120,9 @@ def test_lane_private_decoder_kernels_on_the_cpu():
     in a different order from pass to pass): the ring decoders with one lane per block and -- the product's default, the headline's kernel --
     with FOUR lanes per block (the lanes of a group meet at the emulator-only lockstep points of achip_rings.h), the lane-per-block decoders
     with an LDS window, and the cooperative two-pass decoders (parse to records + a wavefront per block; also with an arena so small that blocks
-    fall back) -- plaintext, status, error offset and guard bands against the oracle, on the cases of the GPU parity suite, without a GPU."""
+    fall back) -- plaintext, status, error offset and guard bands against the oracle, on the cases of the GPU parity suite, without a GPU.  And
+    every ring instantiation the product launches (16 and 64 lanes per block and the latency class among them) on the catalog of constructed
+    streams built for its own ring sizes (check_v3.py --part edges)."""
     import shutil
     import sys
     import pytest
@@ -149,8 +151,16 @@ def test_lane_private_decoder_kernels_on_the_cpu():
         "lz4frame": start("check_lz4frame.py"),
         # the x-snappy-framed reader's variant 2 (walk, chunks through the two-pass Snappy decoder, CRC-32C verification, fold)
         "snappyframed": start("check_snappyframed.py"),
+        # the catalog of constructed streams (tests/decoder_edge_cases.py: one edge of one ring instantiation per stream, valid and malformed) through every
+        # ring instantiation of the launch tables -- 1 .. 64 lanes per block, both ring classes, the latency class: the non-unified copy paths of 8 lanes and
+        # more run on the CPU here and nowhere else -- and through the two-pass decoders, at four (source, destination) misalignments: a line per op and pair
+        "edges-rings": start("check_v3.py", "--part", "edges", "--ops", "16,17,12,13,44,54,46,56,49,59"),
+        "edges-two-pass": start("check_v3.py", "--part", "edges", "--ops", "24,25,26,27,34,35,36,37"),
+        "edges-64-lanes": start("check_v3.py", "--part", "edges", "--ops", "48,58,2641,3641"),
+        "edges-other-widths": start("check_v3.py", "--part", "edges", "--ops", "2020,2021,2041,2042,2080,2081,2161,2320,2321,3020,3021,3041,3042,3080,3081,3161,3320,3321"),
     }
-    expected = {"rings-1-lane": 4, "two-pass-lz4": 4, "two-pass-snappy": 4, "rings-4-lanes": 2, "records": 1, "hadoop": 6, "lz4frame": 2, "snappyframed": 1}
+    expected = {"rings-1-lane": 4, "two-pass-lz4": 4, "two-pass-snappy": 4, "rings-4-lanes": 2, "records": 1, "hadoop": 6, "lz4frame": 2, "snappyframed": 1,
+                "edges-rings": 40, "edges-two-pass": 32, "edges-64-lanes": 16, "edges-other-widths": 72}
     for name, job in jobs.items():
         out = job.communicate()[0]
         assert job.returncode == 0, (name, out)

@@ -7,7 +7,9 @@ from tests import common, oracle_lib
 from tests.gpu_harness import GpuBatch
 from tests.oracle_lib import OracleError
 
-def run(n_cases, seed, codecs=("lz4", "snappy"), big=False):
+def run(n_cases, seed, codecs=("lz4", "snappy"), big=False, edge_seeds=False):
+    """edge_seeds: the constructed streams of tests/decoder_edge_cases.py join the seed streams of lz4 and snappy (the command line asks for them; a caller that
+    does not draws the cases it always drew)"""
     rng = np.random.default_rng(seed)
     o = oracle_lib.load()
     gb = GpuBatch(0)
@@ -44,6 +46,15 @@ def run(n_cases, seed, codecs=("lz4", "snappy"), big=False):
                     c, n = common.snappy_random_stream(rng, target)
                     comp.append(c)
                     caps.append(n)
+        if edge_seeds and codec in ("lz4", "snappy"):
+            # the constructed streams of tests/decoder_edge_cases.py for the ring instantiation a batch of this size takes (lz4_ring_group_for /
+            # snappy_ring_group_for; compact rings): mutation starts from streams that stand on that instantiation's edges
+            from tests import decoder_edge_cases
+            small, large = (4096, 32768) if codec == "lz4" else (2048, 16384)
+            lanes = 64 if n_cases <= small else (16 if n_cases < large else 4)
+            for c in decoder_edge_cases.cases(codec, (lanes, 0)):
+                comp.append(c.stream)
+                caps.append(len(c.plain))
         if codec == "zstd":  # third-party frames as well (no checksum, other header forms, treeless / repeat modes never from the Java encoder)
             try:
                 import pyarrow as pa
@@ -108,4 +119,4 @@ def run(n_cases, seed, codecs=("lz4", "snappy"), big=False):
 
 if __name__ == "__main__":
     sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 6000, int(sys.argv[2]) if len(sys.argv) > 2 else 1,
-                      tuple(sys.argv[3].split(",")) if len(sys.argv) > 3 else ("lz4", "snappy"), big=len(sys.argv) > 4) else 0)
+                      tuple(sys.argv[3].split(",")) if len(sys.argv) > 3 else ("lz4", "snappy"), big=len(sys.argv) > 4, edge_seeds=True) else 0)

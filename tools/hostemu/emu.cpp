@@ -79,6 +79,13 @@ extern "C" int emu_batch(int op, const uint8_t* srcBase, const int64_t* srcOff, 
         a.ringPad = 80;
         return op == 49 ? achip::launch_lz4_decompress_rings(a, nullptr, 4, 3, nullptr) : achip::launch_snappy_decompress_rings(a, nullptr, 4, 3, nullptr);
     }
+    // any lane width and ring class of the launch tables, with the product's ring padding: 2000 + 10 * lanes + ring class for LZ4, 3000 + the same for
+    // Snappy (check_v3.py --part edges runs the configurations that have no op of their own above through these)
+    if (op >= 2000 && op < 4000) {
+        a.ringPad = 80;
+        const int gs = (op % 1000) / 10, ringClass = op % 10;
+        return op < 3000 ? achip::launch_lz4_decompress_rings(a, nullptr, gs, ringClass, nullptr) : achip::launch_snappy_decompress_rings(a, nullptr, gs, ringClass, nullptr);
+    }
     return -1;
 }
 
