@@ -15,8 +15,8 @@
 //                     assumed -- is walked by the lane itself.
 //   planner           reduce, scan of the partial sums by one workgroup, scan: three launches, no workgroup waits for another.
 #include "achip_waveparse.h"
-#include "achip_xxhash.h"
-#include "zstd_dec_common.h"
+#include "lz4_frame_head.h"
+#include "zstd_default_tables.h"
 #include "achip_launch.h"
 #include "achip_lists.h"
 #include "achip_plan.h"
@@ -237,6 +237,10 @@ __global__ __launch_bounds__(64) void snappy_size_kernel(SizeArgs s)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Zstd: a wavefront per item, everything wave-uniform (zstd_decompress.hip's walk without its output)
+// The walk below is zstd_decompress.hip's (zstd_decompress_item and what it calls, without the output), stated here again, not shared: a change there belongs here
+// too.  On a walk shared with the decoder (one template over frames, blocks and sections, a sink per caller) this kernel sized 65 536 text frames in 212.19 ms
+// against 205.60, the old code's three runs within 0.49 (profiles/zstd_grammar_ab.txt).  R3 of tests/decoded_size_cases.py holds the two together: a fault
+// reported here is the fault the decoder reports.
 namespace ds {
 using namespace zd;
 
@@ -524,38 +528,6 @@ __device__ int64_t zstd_size_item(Ctx& c, TableShared& sh, const FseTable* dflt)
 }
 }  // namespace ds
 
-// the three predefined tables, once per launch (zstd_default_tables_kernel's work, for this unit's scratch)
-__global__ __launch_bounds__(64) void zstd_size_tables_kernel(zd::FseTable* dflt)
-{
-    using namespace zd;
-    __shared__ TableShared sh;
-    Ctx c;
-    c.in = nullptr;
-    c.inLen = 0;
-    c.out = nullptr;
-    c.outCap = 0;
-    c.lit = nullptr;
-    c.R = nullptr;
-    c.lane = threadIdx.x;
-    c.detail = 0;
-    c.errOff = 0;
-    const int16_t* norms[3] = {LL_DEFAULT_NORM, OF_DEFAULT_NORM, ML_DEFAULT_NORM};
-    const int32_t maxSym[3] = {35, 28, 52};
-    const int32_t logs[3] = {6, 5, 6};
-    for (int k = 0; k < 3; k++) {
-        __syncthreads();
-        for (int i = c.lane; i <= maxSym[k]; i += 64) {
-            sh.norm[i] = norms[k][i];
-        }
-        __syncthreads();
-        fse_build(c, sh, sh.fse[k], maxSym[k], logs[k], 0);
-        __syncthreads();
-        for (int i = c.lane; i < 512; i += 64) {
-            dflt[k].e[i] = sh.fse[k].e[i];
-        }
-    }
-}
-
 __global__ __launch_bounds__(64) void zstd_size_kernel(SizeArgs s, const zd::FseTable* __restrict__ dflt)
 {
     __shared__ zd::TableShared sh;
@@ -659,13 +631,6 @@ struct NoSizer {  // (the Snappy containers: the preamble is read in the loop)
 
 // ---- LZ4 frames: Lz4FrameCompression.decompress / decompressFrame / skipFrame, M/lz4/Lz4FrameCompression.java:145-343, without the blocks' bodies.  A frame that
 // announces its content size decodes to that or fails (:318); any other frame is the sum of its blocks: a stored block's length, a compressed block's walk.
-namespace lz4f {
-constexpr uint32_t MAGIC = 0x184D2204u, SKIPPABLE_MAGIC = 0x184D2A50u, SKIPPABLE_MASK = 0xFFFFFFF0u;
-constexpr int FLG_BLOCK_INDEPENDENCE = 1 << 5, FLG_BLOCK_CHECKSUM = 1 << 4, FLG_CONTENT_SIZE = 1 << 3, FLG_CONTENT_CHECKSUM = 1 << 2, FLG_DICTIONARY_ID = 1;
-constexpr int FLG_RESERVED_MASK = 0x02, BD_RESERVED_MASK = 0x8F;
-constexpr int HEADER_SIZE = 7;
-constexpr uint32_t UNCOMPRESSED_FLAG = 0x80000000u;
-}  // namespace lz4f
 
 template <class Z>
 __device__ int32_t lz4frame_size_item(const uint8_t* __restrict__ srcBase, int64_t srcOff, int32_t inLen, Z& z, int64_t& total, int64_t& eo)
@@ -689,27 +654,14 @@ __device__ int32_t lz4frame_size_item(const uint8_t* __restrict__ srcBase, int64
         }
         if (magic != MAGIC) DS_FAIL(ACHIP_D_LZ4F_BAD_MAGIC, pos);
         // decompressFrame :184-322
-        const int64_t dstart = pos + 4;
-        if (dstart + 2 > inLen) DS_FAIL(ACHIP_D_LZ4F_TRUNC_HEADER, dstart);
-        const int flg = in[dstart], bd = in[dstart + 1];
-        const int version = (flg >> 6) & 3;
-        if (version != 1) DS_FAIL(version == 0 ? ACHIP_D_LZ4F_VERSION_0 : (version == 2 ? ACHIP_D_LZ4F_VERSION_2 : ACHIP_D_LZ4F_VERSION_3), dstart);
-        if ((flg & FLG_RESERVED_MASK) != 0 || (bd & BD_RESERVED_MASK) != 0) DS_FAIL(ACHIP_D_LZ4F_RESERVED_BITS, dstart);
-        const bool blockChecksum = (flg & FLG_BLOCK_CHECKSUM) != 0, contentSize = (flg & FLG_CONTENT_SIZE) != 0, contentChecksum = (flg & FLG_CONTENT_CHECKSUM) != 0;
-        if ((flg & FLG_BLOCK_INDEPENDENCE) == 0) DS_FAIL(ACHIP_D_LZ4F_LINKED_BLOCKS, dstart);
-        if ((flg & FLG_DICTIONARY_ID) != 0) DS_FAIL(ACHIP_D_LZ4F_DICTIONARY, dstart);
-        const int sizeId = (bd >> 4) & 7;
-        if (sizeId < 4) DS_FAIL(ACHIP_D_LZ4F_BLOCK_MAX_SIZE, dstart + 1);
-        const int64_t blockMax = 1 << (8 + 2 * sizeId);
-        int64_t p = dstart + 2;
-        if (p + (contentSize ? 8 : 0) + 1 > inLen) DS_FAIL(ACHIP_D_LZ4F_TRUNC_HEADER, p);
-        int64_t expectedSize = -1;
-        if (contentSize) {
-            expectedSize = (int64_t)ld8(in + p);
-            p += 8;
+        FrameHeader h;
+        const int32_t hst = read_frame_header(in, inLen, (int32_t)pos, h, eo);
+        if (hst != 0) {
+            return hst;
         }
-        if (in[p] != (int)((xxh32_short(in + dstart, (int32_t)(p - dstart)) >> 8) & 0xFF)) DS_FAIL(ACHIP_D_LZ4F_HEADER_CHECKSUM, p);
-        p++;
+        const int64_t blockMax = h.blockMax, expectedSize = h.expectedSize;
+        const bool blockChecksum = h.blockChecksum, contentSize = h.contentSize, contentChecksum = h.contentChecksum;
+        int64_t p = h.firstBlock;
         int64_t o = 0;
         for (;;) {
             if (p + 4 > inLen) DS_FAIL(ACHIP_D_LZ4F_MISSING_BLOCK_SIZE, p);
@@ -1054,7 +1006,7 @@ hipError_t launch_decoded_size(int32_t op, const SizeArgs& s, hipStream_t stream
         case ACHIP_OP_SNAPPY_DECOMPRESS: hipLaunchKernelGGL(snappy_size_kernel, perLane, wg, 0, stream, s); return hipGetLastError();
         case ACHIP_OP_ZSTD_DECOMPRESS: {
             zd::FseTable* dflt = (zd::FseTable*)((uint8_t*)scratch + ZSTD_TABLES_AT);
-            hipLaunchKernelGGL(zstd_size_tables_kernel, dim3(1), wg, 0, stream, dflt);
+            hipLaunchKernelGGL(zstd_default_tables_kernel, dim3(1), wg, 0, stream, dflt);
             // a wavefront and 17 KiB of tables per item: the workgroups a chip holds at once, the items dealt round
             hipLaunchKernelGGL(zstd_size_kernel, dim3((unsigned)(s.nBlocks < 2048 ? s.nBlocks : 2048)), wg, 0, stream, s, (const zd::FseTable*)dflt);
             return hipGetLastError();

@@ -8,18 +8,13 @@
 // copies for stored blocks, XXH32 (achip_xxhash.h) for the header / block / content checksums.  Throughput comes from
 // many frames per batch; a 4 MiB block is one wavefront's work.
 #include "lz4_decode_body.h"
-#include "achip_xxhash.h"
+#include "lz4_frame_head.h"
 #include "achip_launch.h"
 #include "achip_lists.h"
 
 namespace achip {
 
 namespace lz4f {
-constexpr uint32_t MAGIC = 0x184D2204u, SKIPPABLE_MAGIC = 0x184D2A50u, SKIPPABLE_MASK = 0xFFFFFFF0u;
-constexpr int FLG_BLOCK_INDEPENDENCE = 1 << 5, FLG_BLOCK_CHECKSUM = 1 << 4, FLG_CONTENT_SIZE = 1 << 3, FLG_CONTENT_CHECKSUM = 1 << 2, FLG_DICTIONARY_ID = 1;
-constexpr int FLG_RESERVED_MASK = 0x02, BD_RESERVED_MASK = 0x8F;
-constexpr int HEADER_SIZE = 7;
-constexpr uint32_t UNCOMPRESSED_FLAG = 0x80000000u;
 constexpr int IN_RING = 2048, OUT_RING = 4096;
 using FR = Rings<64, IN_RING, OUT_RING, 1>;
 
@@ -32,31 +27,16 @@ using FR = Rings<64, IN_RING, OUT_RING, 1>;
 // decompressFrame :184-322 ; wave-uniform.  Returns 0 or the status; pos / op advance.
 __device__ int32_t decompress_frame(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* lds, int lane, int32_t& pos, int32_t& op, int64_t& eo)
 {
-    const int32_t frameStart = pos;
     const int32_t outStart = op;
-    const int32_t dstart = frameStart + 4;
-    if (dstart + 2 > inLen) LZ4F_FAIL(ACHIP_D_LZ4F_TRUNC_HEADER, dstart);
-    const int flg = in[dstart], bd = in[dstart + 1];
-    const int version = (flg >> 6) & 3;
-    if (version != 1) LZ4F_FAIL(version == 0 ? ACHIP_D_LZ4F_VERSION_0 : (version == 2 ? ACHIP_D_LZ4F_VERSION_2 : ACHIP_D_LZ4F_VERSION_3), dstart);
-    if ((flg & FLG_RESERVED_MASK) != 0 || (bd & BD_RESERVED_MASK) != 0) LZ4F_FAIL(ACHIP_D_LZ4F_RESERVED_BITS, dstart);
-    const bool blockChecksum = (flg & FLG_BLOCK_CHECKSUM) != 0, contentSize = (flg & FLG_CONTENT_SIZE) != 0, contentChecksum = (flg & FLG_CONTENT_CHECKSUM) != 0;
-    if ((flg & FLG_BLOCK_INDEPENDENCE) == 0) LZ4F_FAIL(ACHIP_D_LZ4F_LINKED_BLOCKS, dstart);
-    if ((flg & FLG_DICTIONARY_ID) != 0) LZ4F_FAIL(ACHIP_D_LZ4F_DICTIONARY, dstart);
-    const int sizeId = (bd >> 4) & 7;
-    if (sizeId < 4) LZ4F_FAIL(ACHIP_D_LZ4F_BLOCK_MAX_SIZE, dstart + 1);
-    const int32_t blockMax = 1 << (8 + 2 * sizeId);  // 64 KiB, 256 KiB, 1 MiB, 4 MiB (Lz4FrameFormat.java:58-67)
-    int32_t p = dstart + 2;
-    if ((int64_t)p + (contentSize ? 8 : 0) + 1 > inLen) LZ4F_FAIL(ACHIP_D_LZ4F_TRUNC_HEADER, p);
-    int64_t expectedSize = -1;
-    if (contentSize) {
-        expectedSize = (int64_t)ld8(in + p);
-        p += 8;
+    FrameHeader h;
+    const int32_t hst = read_frame_header(in, inLen, pos, h, eo);
+    if (hst != 0) {
+        return hst;
     }
-    const int expectedHc = in[p];
-    const int actualHc = (int)((xxh32_short(in + dstart, p - dstart) >> 8) & 0xFF);
-    if (expectedHc != actualHc) LZ4F_FAIL(ACHIP_D_LZ4F_HEADER_CHECKSUM, p);
-    p++;
+    const int32_t blockMax = h.blockMax;
+    const bool blockChecksum = h.blockChecksum, contentSize = h.contentSize, contentChecksum = h.contentChecksum;
+    const int64_t expectedSize = h.expectedSize;
+    int32_t p = h.firstBlock;
 
     int32_t o = outStart;
     for (;;) {

@@ -1,6 +1,7 @@
 // zstd_dec_common.h -- pieces of the Zstd decoder shared by zstd_decompress.hip (one wavefront per item, any
 // input) and zstd_decompress_pipe.hip (five-stage pipeline for single-block frames): format constants, the
-// backward bit reader, FSE table reading / building, Huffman table reading.  Reference lines are cited per function.
+// readers of the four headers' fields, the backward bit reader, FSE table reading / building, Huffman table reading.
+// Reference lines are cited per function.
 #pragma once
 #include "achip_rings.h"
 
@@ -92,6 +93,114 @@ __device__ __forceinline__ uint64_t rd_le(const Ctx& c, int32_t pos, int n)
     if (!(cond)) ZFAIL(c, d, off)
 
 __device__ __forceinline__ int32_t highest_bit(uint32_t v) { return 31 - __builtin_clz(v); }
+
+// ---- the frame and block grammar (RFC 8878 3.1.1): what stands in each header, stated once -- for the pipeline's parse stage and multi-block walk
+// (zstd_decompress_pipe.hip).  Fields only: no verdicts, no state.  Each caller keeps its own checks in its own order; rd_le reads bytes outside the input
+// as 0, so a reader may run before them.  (The one-kernel decoder and the size query keep their inline statements of the same fields -- on the readers and a
+// shared walk both measured slower, profiles/zstd_grammar_ab.txt -- so a change here belongs into zstd_decompress.hip and decoded_size.hip too.) ----
+constexpr uint32_t FRAME_MAGIC = 0xFD2FB528u, FRAME_MAGIC_V07 = 0xFD2FB527u;
+
+// at a frame's first byte: readFrameHeader, ZstdFrameDecompressor.java:860-940
+struct FrameHead {
+    uint32_t magic;
+    bool singleSegment, hasChecksum;
+    int32_t dictDesc, csDesc;
+    int32_t headerSize;  // from the descriptor byte on (the magic is not counted)
+    int32_t windowSize;  // -1: single segment
+};
+__device__ __forceinline__ FrameHead read_frame_head(const Ctx& c, int32_t at)
+{
+    FrameHead h;
+    h.magic = (uint32_t)rd_le(c, at, 4);
+    const int32_t fhd = (int32_t)rd_le(c, at + 4, 1);
+    h.singleSegment = (fhd & 0x20) != 0;
+    h.hasChecksum = (fhd & 4) != 0;
+    h.dictDesc = fhd & 3;
+    h.csDesc = fhd >> 6;
+    h.headerSize = 1 + (h.singleSegment ? 0 : 1) + (h.dictDesc == 0 ? 0 : (1 << (h.dictDesc - 1))) + (h.csDesc == 0 ? (h.singleSegment ? 1 : 0) : (1 << h.csDesc));
+    h.windowSize = -1;
+    if (!h.singleSegment) {
+        const int32_t wd = (int32_t)rd_le(c, at + 5, 1);
+        const uint32_t base = 1u << ((10 + (wd >> 3)) & 31);
+        h.windowSize = (int32_t)(base + (uint32_t)(((int32_t)base / 8) * (wd & 7)));
+    }
+    return h;
+}
+
+// :150-170
+struct BlockHead {
+    bool last;
+    int32_t type;  // 0 raw, 1 RLE, 2 compressed, 3 reserved
+    int32_t size;
+};
+__device__ __forceinline__ BlockHead read_block_head(const Ctx& c, int32_t at)
+{
+    const int32_t header = (int32_t)rd_le(c, at, 3);
+    BlockHead b;
+    b.last = (header & 1) != 0;
+    b.type = (header >> 1) & 3;
+    b.size = (header >> 3) & 0x1FFFFF;
+    return b;
+}
+
+// the literals section's header, :708-858: four block types, three or four size formats each
+struct LitHead {
+    int32_t type;         // 0 raw, 1 RLE, 2 compressed, 3 treeless (the Huffman table of an earlier section)
+    int32_t sizeFormat;
+    int32_t headerBytes;
+    int32_t regenerated;
+    int32_t compressed;   // 0 for raw / RLE
+    bool singleStream;
+    // the whole section: header, then the literals themselves / the one byte to repeat / the table and the streams
+    __device__ __forceinline__ int32_t section_bytes() const { return headerBytes + (type == 0 ? regenerated : (type == 1 ? 1 : compressed)); }
+};
+__device__ __forceinline__ LitHead read_lit_head(const Ctx& c, int32_t at)
+{
+    const uint64_t h = rd_le(c, at, 5);
+    LitHead l;
+    l.type = (int32_t)(h & 3);
+    l.sizeFormat = (int32_t)((h >> 2) & 3);
+    if (l.type < 2) {
+        l.headerBytes = l.sizeFormat == 1 ? 2 : (l.sizeFormat == 3 ? 3 : 1);
+        l.regenerated = l.headerBytes == 1 ? (int32_t)((h >> 3) & 0x1F) : (int32_t)((h >> 4) & (l.headerBytes == 2 ? 0xFFF : 0xFFFFF));
+        l.compressed = 0;
+        l.singleStream = false;
+    }
+    else {
+        const int bits = l.sizeFormat < 2 ? 10 : (l.sizeFormat == 2 ? 14 : 18);
+        l.headerBytes = l.sizeFormat < 2 ? 3 : (l.sizeFormat == 2 ? 4 : 5);
+        l.regenerated = (int32_t)((h >> 4) & ((1u << bits) - 1u));
+        l.compressed = (int32_t)((h >> (4 + bits)) & ((1u << bits) - 1u));
+        l.singleStream = l.sizeFormat == 0;
+    }
+    return l;
+}
+
+// the sequences section's header, :312-349: the count in one byte, in two, or in the 255 form; behind it the byte that names the three tables' modes
+// (0 predefined, 1 RLE, 2 described, 3 repeat).  A first byte of 0 ends the section (`none`): there is no mode byte, and mode[] means nothing.  (A count
+// of 0 in two bytes does not: the Java code reads the modes and the tables, then decodes no sequence.)
+struct SeqHead {
+    bool none;
+    int32_t count;
+    int32_t countBytes;
+    int32_t modesPos;
+    int32_t mode[3];  // literal lengths, offsets, match lengths
+};
+__device__ __forceinline__ SeqHead read_seq_head(const Ctx& c, int32_t at)
+{
+    const uint32_t h = (uint32_t)rd_le(c, at, 4);
+    const int32_t b0 = (int32_t)(h & 0xFF);
+    SeqHead s;
+    s.none = b0 == 0;
+    s.countBytes = b0 == 255 ? 3 : (b0 > 127 ? 2 : 1);
+    s.count = b0 == 255 ? (int32_t)((h >> 8) & 0xFFFF) + 0x7F00 : (b0 > 127 ? ((b0 - 128) << 8) + (int32_t)((h >> 8) & 0xFF) : b0);
+    s.modesPos = at + s.countBytes;
+    const int32_t modes = (int32_t)((h >> (8 * s.countBytes)) & 0xFF);
+    s.mode[0] = modes >> 6;
+    s.mode[1] = (modes >> 4) & 3;
+    s.mode[2] = (modes >> 2) & 3;
+    return s;
+}
 
 // ---- BitInputStream.java ----
 struct Bits {
@@ -646,5 +755,22 @@ __device__ __forceinline__ int32_t huf_decode_stream(const Ctx& c, const uint16_
 
 // wave copy with byte-exact bounds (src, dst do not overlap)
 __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, int32_t n, int lane) { group_copy<64>(dst, src, n, lane); }
+
+// a Ctx that reads `in` and writes nothing (walks, table builds)
+__device__ __forceinline__ Ctx reader_ctx(const uint8_t* in, int32_t inLen, int lane)
+{
+    Ctx c;
+    c.in = in;
+    c.inLen = inLen;
+    c.out = nullptr;
+    c.outCap = 0;
+    c.lit = nullptr;
+    c.R = nullptr;
+    c.lane = lane;
+    c.detail = 0;
+    c.errOff = 0;
+    return c;
+}
 }  // namespace zd
+
 }  // namespace achip

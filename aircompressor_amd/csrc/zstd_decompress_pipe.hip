@@ -184,37 +184,22 @@ __device__ int32_t parse_item(Ctx& c, TableShared& sh, const Pipe& p, int32_t sl
     if (inputLimit < 4 + 1 + 3 + 3) {
         return 0;
     }
-    int32_t input = 0;
-    if ((uint32_t)rd_le(c, input, 4) != 0xFD2FB528u) {
+    const FrameHead h = read_frame_head(c, 0);
+    if (h.magic != FRAME_MAGIC || h.dictDesc != 0 || h.headerSize > inputLimit - 4) {
         return 0;
     }
-    input += 4;
-    const int32_t headerAddress = input;
-    const int32_t fhd = (int32_t)rd_le(c, input++, 1);
-    const bool singleSegment = (fhd & 0x20) != 0;
-    const int32_t dictDesc = fhd & 3;
-    const int32_t csDesc = fhd >> 6;
-    const int32_t headerSize = 1 + (singleSegment ? 0 : 1) + (dictDesc == 0 ? 0 : (1 << (dictDesc - 1))) + (csDesc == 0 ? (singleSegment ? 1 : 0) : (1 << csDesc));
-    if (dictDesc != 0 || headerSize > inputLimit - headerAddress) {
+    if (!h.singleSegment && (h.windowSize > MAX_WINDOW_SIZE || h.windowSize < 0)) {
         return 0;
     }
-    if (!singleSegment) {
-        const int32_t wd = (int32_t)rd_le(c, input++, 1);
-        const uint32_t base = 1u << ((10 + (wd >> 3)) & 31);
-        const int32_t windowSize = (int32_t)(base + (uint32_t)(((int32_t)base / 8) * (wd & 7)));
-        if (windowSize > MAX_WINDOW_SIZE || windowSize < 0) {
-            return 0;
-        }
-    }
-    input = headerAddress + headerSize;
-    d.hasChecksum = (fhd & 4) != 0 ? 1 : 0;
+    int32_t input = 4 + h.headerSize;
+    d.hasChecksum = h.hasChecksum ? 1 : 0;
     if (input + 3 > inputLimit) {
         return 0;
     }
-    const int32_t header = (int32_t)rd_le(c, input, 3);
+    const BlockHead bh = read_block_head(c, input);
     input += 3;
-    const int32_t blockSize = (header >> 3) & 0x1FFFFF;
-    if ((header & 1) == 0 || ((header >> 1) & 3) != 2) {
+    const int32_t blockSize = bh.size;
+    if (!bh.last || bh.type != 2) {
         return p.mbList != nullptr ? 2 : 0;  // more than one block, or a raw / RLE block: the multi-block stages' walk looks at it
     }
     if (blockSize > MAX_BLOCK_SIZE || blockSize < 3) {
@@ -235,28 +220,16 @@ __device__ bool parse_block(Ctx& c, TableShared& sh, const Pipe& p, int32_t slot
     const int32_t blockLimit = input + blockSize;
 
     // literals section header (decode*Literals, ZstdFrameDecompressor.java:708-858)
-    const int32_t b0 = (int32_t)rd_le(c, input, 1);
-    const int32_t literalsBlockType = b0 & 3;
-    const int32_t type = (b0 >> 2) & 3;
+    const LitHead lh = read_lit_head(c, input);
+    const int32_t literalsBlockType = lh.type;
     d.hufLog = 0;
     d.nStreams = 0;
     if (literalsBlockType == 0 || literalsBlockType == 1) {
-        int32_t size;
-        if (type == 0 || type == 2) {
-            size = b0 >> 3;
-            input += 1;
+        if (literalsBlockType == 1 && lh.sizeFormat == 3 && blockSize < 4) {
+            return false;
         }
-        else if (type == 1) {
-            size = (int32_t)rd_le(c, input, 2) >> 4;
-            input += 2;
-        }
-        else {
-            if (literalsBlockType == 1 && blockSize < 4) {
-                return false;
-            }
-            size = (int32_t)(rd_le(c, input, 3) & 0xFFFFFF) >> 4;
-            input += 3;
-        }
+        const int32_t size = lh.regenerated;
+        input += lh.headerBytes;
         if (size > MAX_BLOCK_SIZE) {
             return false;
         }
@@ -281,27 +254,8 @@ __device__ bool parse_block(Ctx& c, TableShared& sh, const Pipe& p, int32_t slot
         if ((literalsBlockType == 3 && !hufBefore) || blockSize < 5) {
             return false;  // (nothing to reuse: "Dictionary is corrupted" :292)
         }
-        int32_t compressedSize, uncompressedSize, headerBytes;
-        bool singleStream = false;
-        if (type == 0 || type == 1) {
-            singleStream = type == 0;
-            const uint32_t h = (uint32_t)rd_le(c, input, 4);
-            headerBytes = 3;
-            uncompressedSize = (int32_t)((h >> 4) & 0x3FF);
-            compressedSize = (int32_t)((h >> 14) & 0x3FF);
-        }
-        else if (type == 2) {
-            const uint32_t h = (uint32_t)rd_le(c, input, 4);
-            headerBytes = 4;
-            uncompressedSize = (int32_t)((h >> 4) & 0x3FFF);
-            compressedSize = (int32_t)((h >> 18) & 0x3FFF);
-        }
-        else {
-            const uint64_t h = rd_le(c, input, 5);
-            headerBytes = 5;
-            uncompressedSize = (int32_t)((h >> 4) & 0x3FFFF);
-            compressedSize = (int32_t)((h >> 22) & 0x3FFFF);
-        }
+        const int32_t compressedSize = lh.compressed, uncompressedSize = lh.regenerated, headerBytes = lh.headerBytes;
+        const bool singleStream = lh.singleStream;
         if (uncompressedSize > MAX_BLOCK_SIZE || headerBytes + compressedSize > blockSize) {
             return false;
         }
@@ -377,27 +331,16 @@ __device__ bool parse_block(Ctx& c, TableShared& sh, const Pipe& p, int32_t slot
     if (blockLimit - input < 1) {
         return false;
     }
-    int32_t sequenceCount = (int32_t)rd_le(c, input++, 1);
+    const SeqHead sq = read_seq_head(c, input);
+    const int32_t sequenceCount = sq.count;
+    input += 1;
     d.log[0] = d.log[1] = d.log[2] = 0;
     d.seqBase = 0;
-    if (sequenceCount != 0) {
-        if (sequenceCount == 255) {
-            if (input + 2 > blockLimit) {
-                return false;
-            }
-            sequenceCount = (int32_t)rd_le(c, input, 2) + 0x7F00;
-            input += 2;
-        }
-        else if (sequenceCount > 127) {
-            if (input >= blockLimit) {
-                return false;
-            }
-            sequenceCount = ((sequenceCount - 128) << 8) + (int32_t)rd_le(c, input++, 1);
-        }
-        if (input + 4 > blockLimit) {
+    if (!sq.none) {
+        if (sq.modesPos + 4 > blockLimit) {  // (the count's bytes, the mode byte and the bit stream's first three)
             return false;
         }
-        const int32_t modes = (int32_t)rd_le(c, input++, 1);
+        input = sq.modesPos + 1;
         const int32_t maxSym[3] = {35, 28, 52};
         const int32_t maxLog[3] = {9, 8, 9};
         const int32_t dfltLog[3] = {6, 5, 6};
@@ -409,7 +352,7 @@ __device__ bool parse_block(Ctx& c, TableShared& sh, const Pipe& p, int32_t slot
         uint16_t* g = p.fse + (size_t)slot * FSE_SLOT;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const int32_t mode = (modes >> (6 - 2 * k)) & 3;
+            const int32_t mode = sq.mode[k];
             int32_t tableLog = 0;
             if (mode == 3) {
                 if (((fseBefore >> k) & 1) == 0) {
@@ -1507,20 +1450,17 @@ __device__ MbWalk mb_walk(const Ctx& c, MbBlock* blocks, int32_t firstSlot, int3
     w.seqs = 0;
     w.ok = false;
     const int64_t inputLimit = c.inLen;
-    const int32_t fhd = (int32_t)rd_le(c, 4, 1);
-    const bool singleSegment = (fhd & 0x20) != 0;
-    const int32_t csDesc = fhd >> 6;
-    int64_t input = 4 + 1 + (singleSegment ? 0 : 1) + (csDesc == 0 ? (singleSegment ? 1 : 0) : (1 << csDesc));  // (no dictionary id: K1)
-    w.hasChecksum = (fhd & 4) != 0 ? 1 : 0;
+    const FrameHead fh = read_frame_head(c, 0);
+    int64_t input = 4 + fh.headerSize;  // (no dictionary id: K1)
+    w.hasChecksum = fh.hasChecksum ? 1 : 0;
     int32_t lastHuf = -1, lastLL = -1, lastOF = -1, lastML = -1;
     for (;;) {
         if (input + 3 > inputLimit || w.n >= maxBlocks) {
             return w;
         }
-        const int32_t header = (int32_t)rd_le(c, (int32_t)input, 3);
+        const BlockHead bh = read_block_head(c, (int32_t)input);
         input += 3;
-        const int32_t type = (header >> 1) & 3;
-        const int32_t size = (header >> 3) & 0x1FFFFF;
+        const int32_t type = bh.type, size = bh.size;
         int64_t adv = size;
         if (type == 1) {
             adv = 1;
@@ -1559,38 +1499,24 @@ __device__ MbWalk mb_walk(const Ctx& c, MbBlock* blocks, int32_t firstSlot, int3
                 // the literals section's header gives its sizes (:708-858), behind it the sequences section's header gives the count and
                 // names the table modes (:328-349); the parse stage checks every field again
                 const int32_t bs = (int32_t)input, bl = (int32_t)input + size;
-                const int32_t b0 = (int32_t)rd_le(c, bs, 1);
-                const int32_t lbt = b0 & 3, sf = (b0 >> 2) & 3;
-                int32_t section, regenerated;
-                if (lbt < 2) {
-                    const int32_t hdr = sf == 1 ? 2 : (sf == 3 ? 3 : 1);
-                    regenerated = sf == 1 ? (int32_t)rd_le(c, bs, 2) >> 4 : (sf == 3 ? (int32_t)(rd_le(c, bs, 3) & 0xFFFFFF) >> 4 : b0 >> 3);
-                    section = hdr + (lbt == 0 ? regenerated : 1);
-                }
-                else {
-                    const int32_t hdr = sf < 2 ? 3 : (sf == 2 ? 4 : 5);
-                    const uint64_t h = rd_le(c, bs, 5);
-                    const int32_t csize = sf < 2 ? (int32_t)((h >> 14) & 0x3FF) : (sf == 2 ? (int32_t)((h >> 18) & 0x3FFF) : (int32_t)((h >> 22) & 0x3FFFF));
-                    regenerated = sf < 2 ? (int32_t)((h >> 4) & 0x3FF) : (sf == 2 ? (int32_t)((h >> 4) & 0x3FFF) : (int32_t)((h >> 4) & 0x3FFFF));
-                    section = hdr + csize;
-                    if (lbt == 2) {
+                const LitHead lh = read_lit_head(c, bs);
+                if (lh.type >= 2) {
+                    if (lh.type == 2) {
                         lastHuf = slot;
                     }
                     b.hufSlot = lastHuf;
                 }
-                if (lbt != 0 && regenerated <= MAX_BLOCK_SIZE) {
-                    w.litUnits += (uint32_t)(regenerated + 64 + 63) >> 6;  // (parse_block's request)
+                if (lh.type != 0 && lh.regenerated <= MAX_BLOCK_SIZE) {
+                    w.litUnits += (uint32_t)(lh.regenerated + 64 + 63) >> 6;  // (parse_block's request)
                 }
-                const int32_t seqPos = bs + section;
+                const int32_t seqPos = bs + lh.section_bytes();
                 if (seqPos < bl) {
-                    const int32_t cnt = (int32_t)rd_le(c, seqPos, 1);
-                    const int32_t modesPos = seqPos + 1 + (cnt == 255 ? 2 : (cnt > 127 ? 1 : 0));
-                    if (cnt != 0 && modesPos < bl) {
-                        w.seqs += cnt == 255 ? (uint32_t)rd_le(c, seqPos + 1, 2) + 0x7F00u : (cnt > 127 ? (uint32_t)(((cnt - 128) << 8) + (int32_t)rd_le(c, seqPos + 1, 1)) : (uint32_t)cnt);
-                        const int32_t modes = (int32_t)rd_le(c, modesPos, 1);
-                        lastLL = ((modes >> 6) & 3) != 3 ? slot : lastLL;
-                        lastOF = ((modes >> 4) & 3) != 3 ? slot : lastOF;
-                        lastML = ((modes >> 2) & 3) != 3 ? slot : lastML;
+                    const SeqHead sq = read_seq_head(c, seqPos);
+                    if (!sq.none && sq.modesPos < bl) {
+                        w.seqs += (uint32_t)sq.count;
+                        lastLL = sq.mode[0] != 3 ? slot : lastLL;
+                        lastOF = sq.mode[1] != 3 ? slot : lastOF;
+                        lastML = sq.mode[2] != 3 ? slot : lastML;
                         b.fseSlot[0] = lastLL;
                         b.fseSlot[1] = lastOF;
                         b.fseSlot[2] = lastML;
@@ -1603,7 +1529,7 @@ __device__ MbWalk mb_walk(const Ctx& c, MbBlock* blocks, int32_t firstSlot, int3
         }
         w.n++;
         input += adv;
-        if ((header & 1) != 0) {
+        if (bh.last) {
             break;
         }
     }
@@ -1620,17 +1546,7 @@ __device__ MbWalk mb_walk(const Ctx& c, MbBlock* blocks, int32_t firstSlot, int3
 
 __device__ __forceinline__ Ctx mb_source(const BatchArgs& a, int32_t item, int lane)
 {
-    Ctx c;
-    c.in = a.srcBase + a.srcOff[item];
-    c.inLen = a.srcLen[item];
-    c.out = nullptr;
-    c.outCap = 0;
-    c.lit = nullptr;
-    c.R = nullptr;
-    c.lane = lane;
-    c.detail = 0;
-    c.errOff = 0;
-    return c;
+    return reader_ctx(a.srcBase + a.srcOff[item], a.srcLen[item], lane);
 }
 
 __device__ __forceinline__ bool mb_in_pass(const Pipe& p, const MbItem& it, int32_t j) { return it.state == 1 && j >= p.itemFirst && j < p.itemEnd; }

@@ -1,6 +1,6 @@
 """achip_decoded_size_batch and achip_plan_outputs on the GPU, the oracle as the checker (tests/decoded_size_cases.py has the inputs and the rules R1 / R2):
 clean items of all seven ops are sized exactly; size -> plan -> decode reaches the plaintext at exact offsets with nothing but the total read back; seeded
-damaged items fall under R1, R2 or "a reported fault is no false alarm"; the planner alone against numpy; HipBatchCodec.decompress_unsized."""
+damaged items fall under R1, R2 or R3 "a reported fault is the reader's fault"; the planner alone against numpy; HipBatchCodec.decompress_unsized."""
 import numpy as np
 import pytest
 
@@ -123,19 +123,21 @@ EXPECTED_CATEGORIES = {
 
 @pytest.mark.parametrize("name", OP_NAMES)
 def test_damaged_items_obey_r1_and_r2(o, g, name):
+    """... and R3: a fault sizing reports is the fault the op's reader reports, status and offset (tests/decoded_size_cases.py)"""
     op = cases.OPS[name]
     items = cases.damaged_items(o, name, 100 + op, 400)
     data = [d for _, d, _ in items]
-    size, status, _, _ = size_on_gpu(g, op, data)
-    seen = {"exact": 0, "r2": 0, "fault": 0}
+    size, status, err, _ = size_on_gpu(g, op, data)
+    seen = {"exact": 0, "r2": 0, "fault": 0, "payload": 0}
     wrong = []
-    for (kind, d, room), z, s in zip(items, size, status):
-        category, what = cases.judge(o, name, d, room, int(z), int(s))
+    for (kind, d, room), z, s, e in zip(items, size, status, err):
+        category, what = cases.judge(o, name, d, room, int(z), int(s), int(e))
         seen[category] += 1
         if what:
             wrong.append((kind, len(d), what))
     print("%s: %s" % (name, seen))
     assert not wrong, wrong[:8]
+    assert cases.payload_share_wrong(name, seen) is None, seen
     assert {c for c, k in seen.items() if k > 0} >= EXPECTED_CATEGORIES[name], seen
     if name == "lz4":  # the same items often enough for the lane-per-block shape: the two shapes agree item by item
         reps = 16384 // len(data) + 2

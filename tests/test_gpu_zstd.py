@@ -414,6 +414,38 @@ def test_catalog_on_the_ring_executor_without_a_staging_area(o, frame_cases):
         g.set_option("decompress.ring_pad", DEFAULT_RING_PAD)
 
 
+def header_form_items(o):
+    """(frames, plaintexts): the catalog's valid frames and the encoder's frames of zc.form_plains() -- between them every literals header and every form of the
+    sequence count the format has (tests/test_zstd_frame_cases.py counts them)"""
+    cases = [c for c in zc.catalog() if not c.malformed]
+    forms = zc.form_plains()
+    return [c.frame for c in cases] + [o.compress("zstd", p) for _, p in forms], [c.plain for c in cases] + [p for _, p in forms]
+
+
+def header_forms_through_the_one_kernel_decoder(g, o):
+    """(also run on the CPU emulator: tools/hostemu/check_serial.py)"""
+    frames, plains = header_form_items(o)
+    g.set_option("zstd.decompress.variant", 0)
+    try:
+        outs, status, err = g.run(OP_ZSTD_DECOMPRESS, frames, [len(p) for p in plains], unaligned=True)
+    finally:
+        g.set_option("zstd.decompress.variant", 1)
+    wrong = [(i, status[i], err[i]) for i in range(len(frames)) if status[i] != 0 or outs[i] != plains[i]]
+    assert not wrong, wrong[:8]
+
+
+def test_every_header_form_through_the_one_kernel_decoder_and_the_size_query(gb, o):
+    """the two readers that state the Java-exact walk (zstd_decompress.hip, decoded_size.hip), on every header form: the one-kernel decoder gives the plaintext at exact capacity, the size
+    query its length"""
+    from tests.test_gpu_decoded_size import size_on_gpu
+    header_forms_through_the_one_kernel_decoder(gb, o)
+    frames, plains = header_form_items(o)
+    size, status, err, _ = size_on_gpu(gb, OP_ZSTD_DECOMPRESS, frames)
+    wrong = [(i, int(status[i]), int(size[i]), len(plains[i])) for i in range(len(frames)) if status[i] != 0 or size[i] != len(plains[i])]
+    assert not wrong, wrong[:8]
+    assert (err == 0).all()
+
+
 LARGE_TILE = 32768
 
 

@@ -51,6 +51,23 @@ def test_every_edge_value_occurs(o):
     assert sum(1 for c in small if zc.is_long(c.cap, c.nseq, K)) >= 20 and sum(1 for c in small if not zc.is_long(c.cap, c.nseq, K)) >= 20
 
 
+def test_every_header_form_occurs(o):
+    """every literals block type x size format and every form of the sequence count, counted by the module's own reader over the frames the decode tests
+    run: the catalog's valid frames, the size query's clean items, and the encoder's frames for the forms only an encoder can write"""
+    from tests import decoded_size_cases
+    frames = [c.frame for c in zc.catalog() if not c.malformed] + [comp for _, comp, _ in decoded_size_cases.clean_items(o, "zstd", big=False)]
+    frames += [o.compress("zstd", p) for _, p in zc.form_plains()]
+    seen = {}
+    for f in frames:
+        for form in zc.header_forms(f):
+            seen[form] = seen.get(form, 0) + 1
+    print(sorted(seen.items()))
+    assert len(zc.HEADER_FORMS) == 19 and not [form for form in zc.HEADER_FORMS if seen.get(form, 0) == 0]
+    # the hand frames bring the forms no encoder here writes: RLE literals, the 255 form
+    hand = {form for c in zc.catalog() if not c.malformed for form in zc.header_forms(c.frame)}
+    assert hand >= {("literals", "rle", k) for k in range(4)} | {("literals", "raw", k) for k in range(4)} | {("count", n) for n in ("one byte", "two bytes", "255")}
+
+
 def test_sequence_counts_of_encoder_frames(o):
     """sequence_count() on the encoders' frames: Huffman and raw literal headers of every form; the oracle's encoder is the Java encoder restated"""
     text = b"".join(d for _, d, _ in common.corpus_sample()[:3])

@@ -2,7 +2,8 @@
 executor zstd_pipe_execute2_kernel), shared by the emulator check (tools/hostemu/check_zstd.py --part catalog) and the GPU tests (tests/test_gpu_zstd.py).
 Imports only numpy (and the standard library).
 
-build_frame() writes a single-segment frame of one compressed block: raw literals, the three sequence tables in RLE mode, a bit stream of extra bits only.
+build_frame() writes a single-segment frame of one compressed block: raw (or RLE) literals, the three sequence tables in RLE mode, a bit stream of extra bits
+only.  header_forms() reads the literals and sequences headers back, so that the tests can count that every form of them occurs in what they decode.
 Its plaintext comes from executing the sequences in plain Python (RFC 8878 3.1.1.4 / 3.1.1.5) -- not from the oracle, not from any library; the CPU suite
 checks that the oracle agrees (tests/test_zstd_frame_cases.py).
 
@@ -126,11 +127,12 @@ def execute(literals, sequences):
     return bytes(out), offs, -1
 
 
-def build_frame(literals, sequences, *, checksum=False, last_literals=None, content_size=None):
+def build_frame(literals, sequences, *, checksum=False, last_literals=None, content_size=None, rle_literals=False, size_format=None):
     """(frame, plaintext).  sequences: [(ll, ml, off)], off > 0 a real offset, -1 / -2 / -3 the repeat-offset values; all of them must share their three
     codes.  last_literals: how many of `literals` the sequences leave over (checked; None: not checked -- a frame that is malformed on purpose).
     content_size: the frame header's field where it is not the plaintext's length (malformed frames: what the lengths add up to).  The plaintext is
-    None where executing the sequences fails."""
+    None where executing the sequences fails.  rle_literals: `literals` (one byte repeated) as an RLE literals section; size_format: 1 or 3 for a
+    literals header of two or three bytes where the size would fit a shorter one."""
     literals = bytes(literals)
     plain, _, _ = execute(literals, sequences)
     if last_literals is not None:
@@ -138,19 +140,21 @@ def build_frame(literals, sequences, *, checksum=False, last_literals=None, cont
     if content_size is None:
         content_size = len(plain) if plain is not None else sum(s[0] + s[1] for s in sequences) + max(0, len(literals) - sum(s[0] for s in sequences))
     n = len(literals)
-    if n < 32:
-        block = bytes([n << 3])
-    elif n < 4096:
-        block = ((n << 4) | 4).to_bytes(2, "little")
+    kind = 1 if rle_literals else 0
+    assert not rle_literals or (n > 0 and literals == literals[:1] * n)
+    if n < 32 and size_format is None:
+        block = bytes([(n << 3) | kind])
+    elif n < 4096 and size_format in (None, 1):
+        block = ((n << 4) | 4 | kind).to_bytes(2, "little")
     else:
-        block = ((n << 4) | 12).to_bytes(3, "little")
-    block += literals
+        block = ((n << 4) | 12 | kind).to_bytes(3, "little")
+    block += literals[:1] if rle_literals else literals
     ns = len(sequences)
     if ns == 0:
         block += b"\x00"
     else:
-        assert ns < 0x7F00
-        block += bytes([ns]) if ns < 128 else bytes([128 + (ns >> 8), ns & 255])
+        assert ns < 0x7F00 + 65536
+        block += bytes([ns]) if ns < 128 else (bytes([128 + (ns >> 8), ns & 255]) if ns < 0x7F00 else b"\xff" + (ns - 0x7F00).to_bytes(2, "little"))
         cl, cm, co = ll_code(sequences[0][0]), ml_code(sequences[0][1]), of_value(sequences[0][2]).bit_length() - 1
         block += bytes([0x54, cl, co, cm])
         acc = nbits = 0
@@ -198,6 +202,66 @@ def sequence_count(frame):
     if n == 255:
         return int.from_bytes(frame[pos + 1:pos + 3], "little") + 0x7F00
     return n if n < 128 else ((n - 128) << 8) + frame[pos + 1]
+
+
+LITERAL_KINDS = ("raw", "rle", "compressed", "treeless")
+# every header form the format has (RFC 8878 3.1.1.3.1.1, 3.1.1.3.2.1): a literals block type with each value of its size format field -- for raw and RLE
+# literals the values 0 and 2 both mean one byte, and both are forms a reader must take -- and the three forms of the sequence count
+HEADER_FORMS = [("literals", kind, form) for kind in LITERAL_KINDS for form in range(4)] + [("count", n) for n in ("one byte", "two bytes", "255")]
+
+
+def header_forms(item):
+    """The header forms of every compressed block of `item` (one or more valid frames), read from the bytes: a list of HEADER_FORMS entries.  Test code
+    beside the writer above -- it takes its field positions from the RFC, not from the kernels."""
+    forms = []
+    pos = 0
+    while pos < len(item):
+        assert item[pos:pos + 4] == b"\x28\xb5\x2f\xfd", pos
+        fhd = item[pos + 4]
+        single = bool(fhd & 0x20)
+        pos += 5 + (0 if single else 1) + (0 if fhd & 3 == 0 else 1 << ((fhd & 3) - 1)) + ((1 if single else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6))
+        while True:
+            h = int.from_bytes(item[pos:pos + 3], "little")
+            pos += 3
+            last, kind, size = h & 1, (h >> 1) & 3, h >> 3
+            assert kind != 3
+            if kind == 2:
+                b0 = item[pos]
+                lit, form = b0 & 3, (b0 >> 2) & 3
+                forms.append(("literals", LITERAL_KINDS[lit], form))
+                if lit < 2:
+                    nbytes = 2 if form == 1 else (3 if form == 3 else 1)
+                    regenerated = int.from_bytes(item[pos:pos + nbytes], "little") >> (3 if nbytes == 1 else 4)
+                    at = pos + nbytes + (regenerated if lit == 0 else 1)
+                else:
+                    nbytes, bits = (3, 10) if form < 2 else ((4, 14) if form == 2 else (5, 18))
+                    at = pos + nbytes + ((int.from_bytes(item[pos:pos + 5], "little") >> (4 + bits)) & ((1 << bits) - 1))
+                assert at < pos + size
+                n = item[at]
+                forms.append(("count", "one byte" if n < 128 else ("two bytes" if n < 255 else "255")))
+            pos += 1 if kind == 1 else size
+            if last:
+                break
+        pos += 4 if fhd & 4 else 0
+    assert pos == len(item)
+    return forms
+
+
+def form_plains():
+    """[(name, plaintext)] whose frames, written by the oracle's encoder, hold the literal forms a hand frame cannot (Huffman literals need an encoder): treeless
+    literals in each size format and compressed literals of 256 .. 1023 bytes in four streams.  A block is 128 KiB; it begins with fresh draws from one skewed
+    alphabet -- the block's literals, which the Huffman table of the block before fits -- and goes on repeating them: matches."""
+    def draw(rng, n):
+        p = np.arange(1, 41) ** -1.1
+        return (rng.choice(40, n, p=p / p.sum()) + 48).astype(np.uint8).tobytes()
+
+    out = []
+    for fresh in (150, 600, 6000, 30000):  # the literals of the second and third block: below 256, below 1024, below 16384, beyond
+        rng = np.random.default_rng(fresh)
+        blocks = [draw(rng, 20000 if k == 0 else fresh) for k in range(3)]
+        out.append(("treeless-%d" % fresh, b"".join((r * (MAX_BLOCK // len(r) + 1))[:MAX_BLOCK] for r in blocks)))
+    out.append(("four-streams-600", (draw(np.random.default_rng(1), 600) * 9)[:5000]))
+    return out
 
 
 def kernel_constants():
@@ -392,6 +456,17 @@ def catalog():
     add("bad-cap-one-short-no-sequences", [], last=40, malformed=True, cap=39, extra_tags={"bad-cap-one-short"})
     add("bad-cap-one-short-checksum", mixed(9, [5], [4], [1, 2, 3, 4]), last=1, checksum=True, malformed=True, cap=9 * 9, extra_tags={"bad-cap-one-short"})
     assert all(c.malformed for c in cases[bad0:]) and not any(c.malformed for c in cases[:bad0])
+
+    # ---- header forms no other frame here and no frame of the oracle's encoder has (header_forms): RLE literals in each size format, the sequence count's 255 form ----
+    def add_form(name, literals, seqs, tags, **how):
+        frame, plain = build_frame(literals, seqs, checksum=len(cases) % 2 == 1, last_literals=len(literals) - sum(s[0] for s in seqs), **how)
+        cases.append(Case(name, frame, plain, len(plain), len(seqs), tags=tags, checksum=len(cases) % 2 == 1))
+
+    for name, n, how in (("rle-literals-form-0", 30, {}), ("rle-literals-form-2", 31, {}), ("rle-literals-form-1", 31, {"size_format": 1}), ("rle-literals-form-1-long", 4095, {}),
+                         ("rle-literals-form-3", 300, {"size_format": 3}), ("rle-literals-form-3-long", 70000, {})):
+        add_form(name, bytes([65 + len(cases) % 26]) * n, [(7, 5, 3), (7, 5, 2)], {"rle-literals"}, rle_literals=True, **how)
+    add_form("count-255", rng.integers(0, 256, 0x7F00 + 9, dtype=np.uint8).tobytes(), [(1, 3, 1)] * 0x7F00, {"count-form=3"})
+    add_form("count-255-more", rng.integers(0, 256, 0x7F00 + 300, dtype=np.uint8).tobytes(), [(1, 3, 1)] * (0x7F00 + 300), {"count-form=3"})
     _catalog = cases
     return cases
 

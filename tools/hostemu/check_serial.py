@@ -68,6 +68,16 @@ def main():
                     verdict = "skipped (%s: %s)" % (type(e).__name__, str(e)[:80])
                 ran += verdict == "ok"
                 print("%-16s %-70s %s  (%.0f s)" % (title, name + (str(p) if p else ""), verdict, time.time() - t0), flush=True)
+    if quick is None and (not only or only in "zstd"):  # every header form (tests/zstd_frame_cases.py) through the one-kernel decoder: the GPU test's own body
+        t0 = time.time()
+        try:
+            zs.header_forms_through_the_one_kernel_decoder(EmuAllBatch({"zstd.decompress.variant": 0}) if whole else EmuBatch(), o)
+            verdict = "ok"
+            ran += 1
+        except AssertionError as e:
+            verdict = "FAILED: " + str(e).splitlines()[0]
+            bad += 1
+        print("%-16s %-70s %s  (%.0f s)" % ("zstd", "header forms through the one-kernel decoder", verdict, time.time() - t0), flush=True)
     print("serial kernels under the emulator: %d tests passed, %d mismatches" % (ran, bad))
     if bad:
         sys.exit(1)

@@ -1,5 +1,5 @@
 """Runs the sizing kernels and the output planner (decoded_size.hip) on the CPU under the fiber emulator (tools/hostemu/libemu_size.so: tools/hostemu/build.sh size)
-against the oracle: every op's clean items must be sized exactly (R1), seeded damaged items must fall under R1 / R2 / "a fault is no false alarm"
+against the oracle: every op's clean items must be sized exactly (R1), seeded damaged items must fall under R1 / R2 / R3 "a reported fault is the reader's fault"
 (tests/decoded_size_cases.py has the rules), both LZ4 launch shapes must agree, and the planner must equal a numpy scan.  The way to develop the kernels on a
 machine without a GPU.  `--quick`: fewer damaged items, no multi-megabyte items."""
 import ctypes
@@ -83,18 +83,32 @@ def main():
                 if not ((g2 == got).all() and (s2 == st).all()):
                     bad += 1
                     print("LZ4 SHAPE %d differs from the launcher's choice" % shape)
+        if name == "zstd":  # every header form the format has (tests/zstd_frame_cases.py), as the GPU test sizes them
+            from tests import test_gpu_zstd
+            frames, plains = test_gpu_zstd.header_form_items(o)
+            got, st, _ = size(op, frames)
+            total += len(frames)
+            for i, (p, g, s) in enumerate(zip(plains, got, st)):
+                if s != 0 or g != len(p):
+                    bad += 1
+                    print("HEADER FORMS frame %d: want %d, got status %d size %d" % (i, len(p), s, g))
         items = cases.damaged_items(o, name, 100 + op, 120 if quick else 400)
-        seen = {"exact": 0, "r2": 0, "fault": 0}
+        seen = {"exact": 0, "r2": 0, "fault": 0, "payload": 0}
         for shape in ((0, 1, 2) if name == "lz4" else (0,)):
-            got, st, _ = size(op, [d for _, d, _ in items], shape)
-            for (kind, d, room), g, s in zip(items, got, st):
+            got, st, eo = size(op, [d for _, d, _ in items], shape)
+            for (kind, d, room), g, s, e in zip(items, got, st, eo):
                 total += 1
-                category, wrong = cases.judge(o, name, d, room, int(g), int(s))
+                category, wrong = cases.judge(o, name, d, room, int(g), int(s), int(e))
                 seen[category] += 1
                 if wrong:
                     bad += 1
                     print("DAMAGED %s (%s, %d bytes, shape %d): %s" % (name, kind, len(d), shape, wrong))
-        print("%-13s clean %3d   damaged: %d exact, %d status 0 but undecodable, %d faults" % (name, len(clean), seen["exact"], seen["r2"], seen["fault"]))
+        wrong = None if quick else cases.payload_share_wrong(name, seen)  # (the share is bounded at the tests' count of items)
+        if wrong:
+            bad += 1
+            print(wrong)
+        print("%-13s clean %3d   damaged: %d exact, %d status 0 but undecodable, %d faults the decoder's own (R3), %d more behind a payload fault of its" % (
+            name, len(clean), seen["exact"], seen["r2"], seen["fault"], seen["payload"]))
     bad += check_planner(np.random.default_rng(9))
     print("decoded-size emulator: %d checks, %d wrong" % (total, bad))
     return 1 if bad else 0

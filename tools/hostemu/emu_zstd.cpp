@@ -8,47 +8,17 @@
 thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
 extern "C" { long long achip_emu_counters[16]; }
 #include "../../aircompressor_amd/csrc/zstd_decompress_pipe.hip"
+#include "../../aircompressor_amd/csrc/zstd_default_tables.h"
 #include "../../aircompressor_amd/csrc/achip_zstd_frame.h"
 #include <vector>
 namespace achip {
 namespace {
-// the predefined FSE tables, built the way zstd_decompress.hip's zstd_default_tables_kernel builds them
-void emu_default_tables_kernel(zd::FseTable* dflt)
-{
-    using namespace zd;
-    __shared__ TableShared sh;
-    Ctx c;
-    c.in = nullptr;
-    c.inLen = 0;
-    c.out = nullptr;
-    c.outCap = 0;
-    c.lit = nullptr;
-    c.R = nullptr;
-    c.lane = threadIdx.x;
-    c.detail = 0;
-    c.errOff = 0;
-    const int16_t* norms[3] = {LL_DEFAULT_NORM, OF_DEFAULT_NORM, ML_DEFAULT_NORM};
-    const int32_t maxSym[3] = {35, 28, 52};
-    const int32_t logs[3] = {6, 5, 6};
-    for (int k = 0; k < 3; k++) {
-        __syncthreads();
-        for (int i = c.lane; i <= maxSym[k]; i += 64) {
-            sh.norm[i] = norms[k][i];
-        }
-        __syncthreads();
-        fse_build(c, sh, sh.fse[k], maxSym[k], logs[k], 0);
-        __syncthreads();
-        for (int i = c.lane; i < 512; i += 64) {
-            dflt[k].e[i] = sh.fse[k].e[i];
-        }
-    }
-}
 std::vector<int32_t> g_fallback;
 }  // namespace
 hipError_t launch_zstd_decompress_prepare(hipStream_t, void* generalScratch, const zd::FseTable** dflt)
 {
     zd::FseTable* t = (zd::FseTable*)((uint8_t*)generalScratch + 4096);
-    hipLaunchKernelGGL(emu_default_tables_kernel, dim3(1), dim3(64), 0, nullptr, t);
+    hipLaunchKernelGGL(zstd_default_tables_kernel, dim3(1), dim3(64), 0, nullptr, t);  // (the product's own build)
     *dflt = t;
     return hipSuccess;
 }
