@@ -119,8 +119,23 @@ class _HipDecompressor(_HipCodecBase, Decompressor):
         return r
 
 
-class Lz4HipCompressor(_HipCompressor):
-    """Drop-in for Lz4JavaCompressor (M/lz4/Lz4JavaCompressor.java:29-85)."""
+class _Lz4AcceleratedCompressor(_HipCompressor):
+    """The `acceleration` of Lz4Compressor.create(int) (M/lz4/Lz4Compressor.java:33-41; 1 .. 65537, M/lz4/Lz4Native.java:49-50): a property of the compressor
+    object, handed to its context before every call -- two compressors that share a context keep their own values."""
+
+    def __init__(self, device=0, native_ctx=None, acceleration=1):
+        if not 1 <= acceleration <= 65537:  # (the check of Lz4NativeCompressor's constructor, before anything asks for a device)
+            raise IllegalArgumentException("LZ4 acceleration should be in the [1, 65537] range but got %d" % acceleration)
+        super().__init__(device, native_ctx)
+        self.acceleration = int(acceleration)
+
+    def _compress(self, src, dst):
+        self._native.set_lz4_acceleration(self.acceleration)
+        return super()._compress(src, dst)
+
+
+class Lz4HipCompressor(_Lz4AcceleratedCompressor):
+    """Drop-in for Lz4JavaCompressor (M/lz4/Lz4JavaCompressor.java:29-85) and, with `acceleration`, for what Lz4Compressor.create(acceleration) returns."""
     _codec = "lz4"
 
     def get_retained_size_in_bytes(self, input_length):
@@ -142,9 +157,10 @@ class Lz4HipDecompressor(_HipDecompressor):
         return r
 
 
-class Lz4FrameHipCompressor(_HipCompressor):
+class Lz4FrameHipCompressor(_Lz4AcceleratedCompressor):
     """Drop-in for Lz4FrameJavaCompressor (M/lz4/Lz4FrameJavaCompressor.java:26-44 -> Lz4FrameCompression.compress): one LZ4
-    frame of independent 4 MiB blocks, each through the HIP block encoder, stored uncompressed when that is not smaller."""
+    frame of independent 4 MiB blocks, each through the HIP block encoder, stored uncompressed when that is not smaller; with
+    `acceleration`, for Lz4FrameNativeCompressor(acceleration) (M/lz4/Lz4FrameNativeCompressor.java:37-40)."""
     _codec = "lz4frame"
 
     def max_compressed_length(self, uncompressed_size):

@@ -341,6 +341,24 @@ int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value)
     return 0;
 }
 
+// Lz4Compressor.create(acceleration): the check and its text are Lz4NativeCompressor's (M/lz4/Lz4NativeCompressor.java:34-41)
+int32_t achip_ctx_set_lz4_acceleration(achip_ctx* ctx, int32_t acceleration)
+{
+    if (acceleration < ACHIP_LZ4_DEFAULT_ACCELERATION || acceleration > ACHIP_LZ4_MAX_ACCELERATION) {
+        const std::string text = "LZ4 acceleration should be in the [1, 65537] range but got " + std::to_string(acceleration);
+        return bad_argument(text.c_str());
+    }
+    if (!ctx) return bad_argument("ctx is null");
+    ctx->kernel.lz4Acceleration = acceleration;
+    return 0;
+}
+
+int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    return ctx->kernel.lz4Acceleration;
+}
+
 // n words at byte `offset` of the scratch, once everything the context has launched is done
 static bool read_scratch(achip_ctx* ctx, int64_t offset, int32_t* v, int n)
 {

@@ -320,7 +320,7 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
                 g_lastError.clear();
                 if (const int32_t r = ensure_scratch(ctx, achip::lz4frame_compress_scratch_bytes(a.nBlocks, true)); r < 0) return r;
             }
-            e = achip::launch_lz4frame_compress(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes);
+            e = achip::launch_lz4frame_compress(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes, ctx->kernel.lz4Acceleration);
             break;
         }
         case ACHIP_OP_ZSTDSTREAM_COMPRESS: {

@@ -99,7 +99,8 @@ hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t sc
 // ---- containers: LZ4 frames, x-snappy-framed, Hadoop block streams (the readers pass `ks` on to the two-pass decoders) ----
 hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
 int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant);
-hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes);
+// acceleration: KernelSettings::lz4Acceleration of the context (1: the kernel as it was)
+hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int32_t acceleration = 1);
 int64_t lz4frame_compress_scratch_bytes(int32_t items, bool least);
 hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
 int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams);

@@ -19,6 +19,9 @@ struct KernelSettings {
     int lz4MemWaves = 1;
     int lz4TierMinBlocks = 256 * 20;  // lz4.compress.tier_min_blocks: batches of at least this many blocks take the two-tier kernel (what the LDS tier holds at once)
     int lz4TierWorkgroups = 0;        // the two-tier LZ4 kernel's grid (no option; 0: lz4t::WORKGROUPS, tools/hostemu makes it small)
+    // Lz4Compressor.create(acceleration), 1 .. 65537 (no option: achip_ctx_set_lz4_acceleration -- a property of the compressor object, not a tuning knob): the LZ4
+    // block and LZ4 frame encoders' search advances by this many positions per probe from its second probe on.  Above 1 the launchers take the `_accel` kernels.
+    int lz4Acceleration = 1;
     // snappy.compress.mem_waves: wavefronts of a workgroup whose table lies in memory (0 .. 3).  Their tables are what the kernel's HBM traffic is made of -- 431 GB
     // a launch on the corpus batch, 100 x the input: 1 280 workgroups x 3 slabs x 32 KiB = 120 MB of tables, 15 MB per XCD against 4 MB of L2.
     int snappyMemWaves = 3;

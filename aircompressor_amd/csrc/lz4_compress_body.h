@@ -72,11 +72,29 @@ __device__ __forceinline__ int32_t lz4_scan_offset(int32_t m)
 }
 __device__ __forceinline__ int32_t lz4_scan_advance(int32_t k) { return k == 0 ? 1 : (63 + k) >> 6; }
 
+// ---- acceleration (Lz4Compressor.create(int), M/lz4/Lz4Compressor.java:33-41) ----
+// :115 with `acceleration << SKIP_TRIGGER` for `1 << SKIP_TRIGGER`, liblz4's rule: adv(0) = 1, adv(k) = (64a + k - 1) >> 6 = a + ((k - 1) >> 6) for k >= 1, which
+// is the schedule above with a - 1 more per advance from the second probe on.  The encoders take it as a compile-time form (ACCEL) with the value as an
+// argument: the ACCEL = false instantiations are the kernels as they were.
+// In 32 bits: a batch's first probe lies at most at matchFindLimit (the probe before it was valid), its other 63 lanes at most 63 advances behind it, an
+// advance is at most 65537 + 2^31 / 64 / 65537 + 1 -- 0x7E000000 + 64 * 66000 < 2^31.
+__device__ __forceinline__ int32_t lz4_scan_offset(int32_t m, int32_t a) { return m == 0 ? 0 : lz4_scan_offset(m) + (m - 1) * (a - 1); }
+__device__ __forceinline__ int32_t lz4_scan_advance(int32_t k, int32_t a) { return k == 0 ? 1 : ((63 + k) >> 6) + (a - 1); }
+// the probes of one search as a mask of the 64 positions from its start on: bit 0 and the bits 1 + j * a (inside a window the advance has not grown yet)
+__device__ __forceinline__ uint64_t lz4_probe_pattern(int32_t a)
+{
+    uint64_t p = 1;
+    for (int32_t b = 1; b < 64; b += a) {
+        p |= 1ull << b;
+    }
+    return p;
+}
+
 // The batch-probe encoder of one block (M/lz4/Lz4RawCompressor.java:74-187) by one wavefront; `table` is MAX_TABLE_SIZE
 // entries of LDS.  Returns the compressed length; stOut receives 0 or the status.  Shared by the batched block encoder
 // below and the LZ4 frame encoder (lz4_frame.hip).
-template <typename TableT>
-__device__ int32_t lz4_compress_block(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* __restrict__ out, int32_t outCap, TableT* table, int lane, int32_t& stOut)
+template <typename TableT, bool ACCEL = false>
+__device__ int32_t lz4_compress_block(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* __restrict__ out, int32_t outCap, TableT* table, int lane, int32_t& stOut, int32_t accel = 1)
 {
     using namespace lz4c;
     int32_t st = 0;
@@ -148,8 +166,14 @@ __device__ int32_t lz4_compress_block(const uint8_t* __restrict__ in, int32_t in
                 }
                 bool valid = true;  // a search probe whose next index passes matchFindLimit ends the block (:127-129)
                 if (k >= 0) {
-                    pos = scanStart + lz4_scan_offset(k);
-                    valid = pos + lz4_scan_advance(k) <= matchFindLimit;
+                    if constexpr (ACCEL) {
+                        pos = scanStart + lz4_scan_offset(k, accel);
+                        valid = pos + lz4_scan_advance(k, accel) <= matchFindLimit;
+                    }
+                    else {
+                        pos = scanStart + lz4_scan_offset(k);
+                        valid = pos + lz4_scan_advance(k) <= matchFindLimit;
+                    }
                 }
                 const unsigned long long invalidMask = __ballot(role == 2 && !valid);
                 const int firstInvalid = invalidMask ? __builtin_ctzll(invalidMask) : 64;

@@ -68,8 +68,13 @@ __device__ __forceinline__ uint64_t ext64(uint64_t lo, uint64_t hi, int off)
 }
 }  // namespace lz4mw
 
-template <typename TableT>
-__device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* __restrict__ out, int32_t outCap, TableT* table, int lane, int32_t& stOut)
+// ACCEL (Lz4Compressor.create(acceleration), lz4_compress_body.h): the window stays 64 consecutive positions -- literals still come from the lanes' registers, a
+// candidate inside the window is still a lane read -- and only WHICH LANES PROBE changes: a search that starts at lane c probes the lanes c, c + 1, c + 1 + a, ...,
+// the wave-uniform pattern lz4_probe_pattern(a) shifted by c.  The replay's three uses of "every lane from p0 on" (who probes, whose inserts a lane sees, who is
+// inserted up to the winner) take that mask; a probe ends the block when its successor -- one position on for the search's first probe, a positions behind it --
+// lies beyond matchFindLimit; a search that leaves the window has done as many probes as the mask has bits.  The ACCEL = false form is the encoder as it was.
+template <typename TableT, bool ACCEL = false>
+__device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* __restrict__ out, int32_t outCap, TableT* table, int lane, int32_t& stOut, int32_t accel = 1)
 {
     using namespace lz4c;
     using namespace lz4mw;
@@ -97,6 +102,11 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
         const int32_t matchFindLimit = inputLimit - MATCH_FIND_LIMIT;
         const int32_t matchLimit = inputLimit - LAST_LITERAL_SIZE;
         int32_t anchor = 0;
+        uint64_t pattern = 0;  // (ACCEL) the probes of a search from its first position on
+        if constexpr (ACCEL) {
+            accel = uni(accel);
+            pattern = lz4_probe_pattern(accel);
+        }
 
         // emitMatch :209-235 behind a literal run already in place; returns the new output position
         auto emit_match = [&](int32_t tokenPos, int32_t literalLength, int32_t offset, int32_t matchLength) {
@@ -160,8 +170,8 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                 if (mode == 2) {
                     // ---- the batch-probe step of lz4_compress_body.h for a search in progress: 64 probes at the positions of the skip schedule ----
                     const int32_t k = k0 + lane;
-                    const int32_t pos = scanStart + lz4_scan_offset(k);
-                    const bool valid = pos + lz4_scan_advance(k) <= matchFindLimit;
+                    const int32_t pos = scanStart + (ACCEL ? lz4_scan_offset(k, accel) : lz4_scan_offset(k));
+                    const bool valid = pos + (ACCEL ? lz4_scan_advance(k, accel) : lz4_scan_advance(k)) <= matchFindLimit;
                     const unsigned long long invalidMask = __ballot(!valid);
                     const int firstInvalid = invalidMask ? __builtin_ctzll(invalidMask) : 64;
                     const bool active = lane < firstInvalid;
@@ -244,6 +254,8 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                 const int32_t pos = base + lane;
                 const bool canLoad = pos + 8 <= inLen;
                 const bool canProbe = pos + 1 <= matchFindLimit;  // a search probe needs its successor inside the limit (:127-129)
+                // (ACCEL: the successor is one position on for a search's first probe and `accel` positions on behind it -- compared per step, below: two vector
+                // instructions there instead of two more lane masks held in scalar registers across the replay, which has none to spare)
                 uint64_t x = 0;
                 int32_t h = 0;
                 int32_t tc = 0;
@@ -321,31 +333,36 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                     if (r >= 0) {
                         c = r + 1;                  // where the search proper starts (its probe 0: the skip schedule counts from here if it runs through the window)
                     }
+                    // (ACCEL) the probing lanes of this step: the re-probe, and the search's pattern from lane c on (c = 64: the search starts behind the window)
+                    unsigned long long PM = 0;
+                    if constexpr (ACCEL) {
+                        PM = (c < 64 ? pattern << c : 0ull) | (r >= 0 ? 1ull << r : 0ull);
+                    }
                     // a lane sees the inserts of the replay so far and of the probing lanes before it
-                    const unsigned long long elig = sameBelow & (M | ~sbits(0, p0));  // (= same & (M | bits(p0, lane)) & bits(0, lane))
+                    const unsigned long long elig = ACCEL ? sameBelow & (M | PM) : sameBelow & (M | ~sbits(0, p0));  // (= same & (M | bits(p0, lane)) & bits(0, lane))
                     const int j = elig != 0 ? 63 - __builtin_clzll(elig) : -1;
                     const uint32_t cv = __shfl(x4, j >= 0 ? j : lane);
                     const uint32_t cmp = j >= 0 ? cv : c4;
                     const int32_t cp = j >= 0 ? base + j : tc;
-                    const bool probing = lane >= p0;
-                    const bool mayProbe = canProbe || lane == r;
+                    const bool probing = ACCEL ? ((PM >> lane) & 1ull) != 0 : lane >= p0;
+                    const bool mayProbe = ACCEL ? (lane == r || pos + (lane == c ? 1 : accel) <= matchFindLimit) : canProbe || lane == r;
                     const bool hit = probing && mayProbe && cmp == x4 && (j >= 0 || cp + MAX_DISTANCE >= pos);
                     const unsigned long long hm = __ballot(hit);
                     const unsigned long long im = __ballot(probing && !mayProbe);
                     const unsigned long long first = hm | im;
                     if (first == 0) {
-                        M |= sbits(p0, 64);
+                        M |= ACCEL ? PM : sbits(p0, 64);
                         searchGoesOn = true;
                         break;
                     }
                     const int w = __builtin_ctzll(first);
                     if (((im >> w) & 1ull) != 0) {  // the probe at lane w would step beyond matchFindLimit: the block ends in literals
                         MWC(31);
-                        M |= sbits(p0, w);
+                        M |= ACCEL ? PM & sbits(0, w) : sbits(p0, w);
                         blockDone = true;
                         break;
                     }
-                    M |= sbits(p0, w + 1);
+                    M |= ACCEL ? PM & (~0ull >> (63 - w)) : sbits(p0, w + 1);
                     const int wl = w;                                    // lane where the match starts
                     int32_t cand = (int32_t)rl32((uint32_t)cp, w);      // its candidate's position
                     const int jl = (int)rl32((uint32_t)j, w);           // ... as a lane of this window (-1: the table's entry)
@@ -583,7 +600,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                 if (searchGoesOn) {
                     mode = 2;
                     scanStart = base + c;
-                    k0 = 64 - c;
+                    k0 = ACCEL ? (c < 64 ? __builtin_popcountll(pattern << c) : 0) : 64 - c;  // (the search's probes inside the window)
                     continue;
                 }
                 mode = 1;

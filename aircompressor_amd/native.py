@@ -39,6 +39,8 @@ SIGNATURES = {
     "achip_ctx_synchronize": (_i32, [_vp]),
     "achip_ctx_set_option": (_i32, [_vp, ctypes.c_char_p, _i64]),
     "achip_ctx_get_stat": (_i64, [_vp, ctypes.c_char_p]),
+    "achip_ctx_set_lz4_acceleration": (_i32, [_vp, _i32]),
+    "achip_ctx_get_lz4_acceleration": (_i32, [_vp]),
     "achip_snappyframed_max_compressed_length": (_i32, [_i32]),
     "achip_snappyframed_decompress_batch": (_i32, _BATCH),
     "achip_snappyframed_compress_batch": (_i32, _BATCH),
@@ -204,6 +206,18 @@ class HipNative:
 
     def get_stat(self, name):
         return int(self.lib.achip_ctx_get_stat(self.ctx, name.encode()))
+
+    def set_lz4_acceleration(self, acceleration):
+        """Lz4Compressor.create(acceleration) for this context's LZ4 block and LZ4 frame encodes (1 .. 65537; 1: the Java encoder)"""
+        r = self.lib.achip_ctx_set_lz4_acceleration(self.ctx, int(acceleration))
+        if r < 0:
+            raise IllegalArgumentException(self.lib.achip_last_error().decode(), r)
+
+    def get_lz4_acceleration(self):
+        r = int(self.lib.achip_ctx_get_lz4_acceleration(self.ctx))
+        if r < 0:
+            raise_for_status(r)
+        return r
 
     def synchronize(self):
         r = self.lib.achip_ctx_synchronize(self.ctx)

@@ -187,6 +187,24 @@ int32_t achip_ctx_synchronize(achip_ctx* ctx);    /* hipStreamSynchronize */
 /* tuning knobs (kernel variant selection) of this context -- a mixed batch's helper contexts take a copy of them; name/value pairs documented
  * in DESIGN.md. returns 0 or status */
 int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value);
+/* replaces the argument of Lz4Compressor.create(int acceleration)  M/lz4/Lz4Compressor.java:33-41, Lz4NativeCompressor(int acceleration)
+ * M/lz4/Lz4NativeCompressor.java:34-41 and Lz4FrameNativeCompressor(int acceleration)  M/lz4/Lz4FrameNativeCompressor.java:37-40 (the bounds:
+ * M/lz4/Lz4Native.java:49-50).  A property of the context, as it is of the Java compressor object; a mixed batch's helper contexts take a copy of it.
+ * The encoders follow the Java encoder, so the parameter is defined on its loop by liblz4's rule: M/lz4/Lz4RawCompressor.java:115 reads
+ * `acceleration << SKIP_TRIGGER` -- the search advances by `acceleration` positions per probe from its second probe on; 1 is the
+ * Java encoder, byte for byte.
+ * It applies to every LZ4 block encode and every LZ4 frame encode the context launches: achip_lz4_compress_batch, achip_lz4_compress,
+ * achip_lz4frame_compress_batch, achip_lz4frame_compress, and ACHIP_OP_LZ4_COMPRESS / ACHIP_OP_LZ4FRAME_COMPRESS inside achip_batch_host,
+ * achip_mixed_batch, achip_mixed_batch_host and achip_multi_batch_host (each context its own value).
+ * It does NOT change: the Hadoop LZ4 writer in its one-shot or its window form (Lz4HadoopStreams creates a default compressor:
+ * M/lz4/Lz4HadoopStreams.java:52-66), any bound, any decoder, any other codec.
+ * set: 0, or for a value outside [1, 65537] a status of class INVALID_ARGUMENT with detail ACHIP_D_BAD_ARGUMENT -- the context keeps its value,
+ * achip_last_error has the reference's text "LZ4 acceleration should be in the [1, 65537] range but got N" (checked before the context is looked at).
+ * get: the value, or a status for a null context. */
+#define ACHIP_LZ4_DEFAULT_ACCELERATION 1
+#define ACHIP_LZ4_MAX_ACCELERATION 65537
+int32_t achip_ctx_set_lz4_acceleration(achip_ctx* ctx, int32_t acceleration);
+int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx);
 /* diagnostics of the LAST batched call on this context (synchronizes the stream); -1 = unknown name / nothing recorded.
  * "zstd.decompress.fallback_items": items the five-stage pipeline handed to the one-kernel decoder;
  * "zstd.decompress.fallback_stage1" .. "stage6": the same, by the stage that handed them over (6: the multi-block stages' walk);

@@ -47,6 +47,8 @@ public final class HipNative
     public static final int CLASS_INVALID_ARGUMENT = 3;
     public static final int CLASS_DEVICE = 4;
     public static final int DETAIL_LZ4_EMPTY_OUTPUT = 7;
+    public static final int LZ4_DEFAULT_ACCELERATION = 1;  // ACHIP_LZ4_DEFAULT_ACCELERATION
+    public static final int LZ4_MAX_ACCELERATION = 65537;  // ACHIP_LZ4_MAX_ACCELERATION
 
     public static final int OP_LZ4_DECOMPRESS = 0;
     public static final int OP_LZ4_COMPRESS = 1;
@@ -285,6 +287,10 @@ public final class HipNative
             MethodHandle ctxStream,
             @NativeSignature(name = "achip_ctx_get_stat", returnType = long.class, argumentTypes = {MemorySegment.class, MemorySegment.class})
             MethodHandle ctxGetStat,
+            @NativeSignature(name = "achip_ctx_set_lz4_acceleration", returnType = int.class, argumentTypes = {MemorySegment.class, int.class})
+            MethodHandle ctxSetLz4Acceleration,
+            @NativeSignature(name = "achip_ctx_get_lz4_acceleration", returnType = int.class, argumentTypes = MemorySegment.class)
+            MethodHandle ctxGetLz4Acceleration,
             @NativeSignature(name = "achip_memset_d", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, int.class, long.class})
             MethodHandle memsetDevice,
             @NativeSignature(name = "achip_event_create", returnType = MemorySegment.class, argumentTypes = {})
@@ -984,6 +990,45 @@ public final class HipNative
             catch (Throwable e) {
                 throw new AssertionError("should not reach here", e);
             }
+        }
+
+        /**
+         * achip_ctx_set_lz4_acceleration: the argument of Lz4Compressor.create(acceleration) for this context's LZ4 block and LZ4 frame encodes.
+         * The check and its text are Lz4NativeCompressor's.
+         */
+        public void setLz4Acceleration(int acceleration)
+        {
+            if (acceleration < LZ4_DEFAULT_ACCELERATION || acceleration > LZ4_MAX_ACCELERATION) {
+                throw new IllegalArgumentException("LZ4 acceleration should be in the [1, 65537] range but got " + acceleration);
+            }
+            int result;
+            try {
+                result = (int) HANDLES.ctxSetLz4Acceleration().invokeExact(handle(), acceleration);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /** achip_ctx_get_lz4_acceleration */
+        public int getLz4Acceleration()
+        {
+            int result;
+            try {
+                result = (int) HANDLES.ctxGetLz4Acceleration().invokeExact(handle());
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+            return result;
         }
 
         /** Single block through host memory: returns bytes written or throws the Java codec's exception. */

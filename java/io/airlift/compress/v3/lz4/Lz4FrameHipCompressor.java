@@ -44,8 +44,24 @@ public final class Lz4FrameHipCompressor
 
     public Lz4FrameHipCompressor(int device)
     {
+        this(device, HipNative.LZ4_DEFAULT_ACCELERATION);
+    }
+
+    /**
+     * @param acceleration 1 .. 65537, as for {@code new Lz4FrameNativeCompressor(acceleration)}: the search advances by this many positions per probe
+     * from its second probe on (1: the Java encoder's bytes)
+     */
+    public Lz4FrameHipCompressor(int device, int acceleration)
+    {
         HipNative.verifyEnabled();
         this.context = new HipNative.Context(device);
+        this.context.setLz4Acceleration(acceleration);
+    }
+
+    /** {@code new Lz4FrameNativeCompressor(acceleration)} on device 0 (a one-argument constructor is taken: it names the device) */
+    public static Lz4FrameHipCompressor create(int acceleration)
+    {
+        return new Lz4FrameHipCompressor(0, acceleration);
     }
 
     public static boolean isEnabled()

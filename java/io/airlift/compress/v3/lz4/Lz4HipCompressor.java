@@ -42,8 +42,24 @@ public final class Lz4HipCompressor
 
     public Lz4HipCompressor(int device)
     {
+        this(device, HipNative.LZ4_DEFAULT_ACCELERATION);
+    }
+
+    /**
+     * @param acceleration 1 .. 65537, as for {@code Lz4Compressor.create(acceleration)}: the search advances by this many positions per probe
+     * from its second probe on (1: the Java encoder's bytes)
+     */
+    public Lz4HipCompressor(int device, int acceleration)
+    {
         HipNative.verifyEnabled();
         this.context = new HipNative.Context(device);
+        this.context.setLz4Acceleration(acceleration);
+    }
+
+    /** {@code Lz4Compressor.create(acceleration)} on device 0 (a one-argument constructor is taken: it names the device) */
+    public static Lz4HipCompressor create(int acceleration)
+    {
+        return new Lz4HipCompressor(0, acceleration);
     }
 
     public static boolean isEnabled()
