@@ -31,7 +31,7 @@
 // 20 sequences of the replay, 21 vector path, 22 more than 4 bytes match backwards, 23 candidate inside the window, 24 no usable facts, 25 mode-2 matches, 26 windows,
 // 27 zero-literal hits, 28 / 29 scalar count from registers (okA && okB) / from memory, 30 / 34 the memory catch-up takes a second trip (window / mode 2),
 // 31 / 32 the block ends at a probe beyond matchFindLimit / behind a match, 33 a match ends beyond its window, 35 mode 2 runs off the end
-extern "C" long long g_zc_stats[64];
+extern "C" long long g_zc_stats[128];
 #define MWC(k) do { if (lane == 0) g_zc_stats[k]++; } while (0)
 #else
 #define MWC(k)

@@ -13,7 +13,7 @@
 // 40 copies of the replay, 41 candidate inside the window, 42 re-probe hits, 43 copies split into pieces of 64 / 60, 44 / 45 the last piece a copy with a 1-byte /
 // 2-byte offset, 46 mode-2 copies, 47 windows, 48 / 49 the search runs off the end in a window / in mode 2, 50 vector path, 51 a copy ends beyond its window,
 // 52 / 53 scalar count from registers / from memory
-extern "C" long long g_zc_stats[64];
+extern "C" long long g_zc_stats[128];
 #define SNWC(k) do { if (lane == 0) g_zc_stats[k]++; } while (0)
 #define SNWC_COPY(offset, matched) do { int32_t m_ = (matched); if (m_ > 64) SNWC(43); while (m_ >= 68) m_ -= 64; if (m_ > 64) m_ -= 60; \
                                         if (m_ < 12 && (offset) < 2048) SNWC(44); else SNWC(45); } while (0)

@@ -6,6 +6,19 @@
 #include "achip_device.h"
 #include "achip_seqexec.h"  // sx::wave_scan_incl, sx::wave_bcast
 
+#ifdef ACHIP_HOST_STATS  // (CPU emulator only: which way the encoder goes -- tools/hostemu/enc_paths.py, zc_stats.py, tests/test_zstd_encoder_cases.py)
+extern "C" long long g_zc_stats[128];
+// (out of line and not instrumented: under the emulator's access-granular lockstep every traced access is an order point of ALL lanes)
+static __attribute__((noinline, no_sanitize("coverage"))) void zc_stat_add(int i, long long n) { g_zc_stats[i] += n; }
+#define ZC_STAT(i, n) \
+    if (lane == 0) zc_stat_add((i), (n))
+#define ZC_STAT_C(i, n) \
+    if (c.lane == 0) zc_stat_add((i), (n))
+#else
+#define ZC_STAT(i, n)
+#define ZC_STAT_C(i, n)
+#endif
+
 namespace achip {
 
 namespace zc {
@@ -468,6 +481,7 @@ __device__ void fse_normalize_counts(int16_t* norm, int32_t tableLog, const int3
     const int32_t largest = top > 0 ? (int32_t)__builtin_ctzll(holders) : 0;
     const int32_t largestValue = __shfl(value, largest);
     if (-stillToDistribute >= (int32_t)((uint32_t)largestValue >> 1)) {  // (uniform)
+        ZC_STAT(112, 1);
         fse_normalize_counts2(norm, tableLog, counts, total, maxSymbol, lane);
     }
     else if (mine) {
@@ -522,6 +536,9 @@ __device__ int32_t fse_write_normalized_counts(Ctx& c, Shared& sh, uint8_t* base
             const unsigned long long above = nonZeros >> lane;  // (bit 0 is this lane: a zero)
             const int32_t run = above != 0 ? (int32_t)__builtin_ctzll(above) - 1 : 0;
             const int32_t ones = 16 * (run / 24) + 2 * ((run % 24) / 3);
+#ifdef ACHIP_HOST_STATS  // (any lane: a run belongs to the lane of its first zero)
+            zc_stat_add(run >= 24 ? 115 : (run >= 3 ? 114 : 113), 1);
+#endif
             const uint64_t code = ((1ull << ones) - 1ull) | ((uint64_t)((run % 24) % 3) << ones);
             bits |= code << width;
             width += ones + 2;
@@ -775,6 +792,7 @@ __device__ int32_t huf_set_max_height(Shared& sh, int32_t lastNonZero, int32_t m
     if (largestBits <= maxNumberOfBits) {  // (uniform)
         return largestBits;
     }
+    ZC_STAT(81, 1);
     constexpr int32_t NONE = (int32_t)0xF0F0F0F0;
     // ---- the cuts: the run of leaves longer than allowed at the end of the table, and the first leaf below it that is shorter than allowed ----
     int32_t bitsOf[4];
@@ -835,6 +853,7 @@ __device__ int32_t huf_set_max_height(Shared& sh, int32_t lastNonZero, int32_t m
         }
         const unsigned long long stopMask = __ballot(stops);
         int32_t dec = stopMask != 0 ? 63 - (int32_t)__builtin_clzll(stopMask) : 1;
+        ZC_STAT(stopMask != 0 ? 83 : 82, 1);
         // ... and moves up to the first rank that has a leaf (:351-353), 13 when none has
         const unsigned long long have = __ballot(rank != NONE && lane >= dec && lane <= 12);
         dec = have != 0 ? (int32_t)__builtin_ctzll(have) : 13;
@@ -858,6 +877,7 @@ __device__ int32_t huf_set_max_height(Shared& sh, int32_t lastNonZero, int32_t m
         int32_t rank1 = __shfl(rank, 1);
         if (lane == 0) {
             while (totalCost < 0) {
+                ZC_STAT(rank1 == NONE ? 84 : 85, 1);
                 if (rank1 == NONE) {
                     while ((int32_t)sh.nodeBits[n] == maxNumberOfBits) {
                         n--;
@@ -940,9 +960,11 @@ __device__ int32_t huf_compress_weights(Ctx& c, Shared& sh, uint8_t* base, int32
         }
     }
     if (maxCount == weightsLength) {
+        ZC_STAT_C(86, 1);
         return 1;
     }
     if (maxCount == 1) {
+        ZC_STAT_C(87, 1);
         return 0;
     }
     // the generic FSE routines index their inputs dynamically: park the 13 counts in LDS (rankLast is free once
@@ -985,9 +1007,11 @@ __device__ int32_t huf_table_write(Ctx& c, Shared& sh, const HufCTable& t, uint8
         return -1;
     }
     if (size != 0 && size != 1 && size < maxSymbol / 2) {
+        ZC_STAT_C(88, 1);
         base[output] = (uint8_t)size;
         return size + 1;
     }
+    ZC_STAT_C(89, 1);
     const int32_t entryCount = maxSymbol;
     size = (entryCount + 1) / 2;
     ZC_CHECK(c, size + 1 <= outputSize);
@@ -1131,6 +1155,7 @@ __device__ int32_t raw_literals(Ctx& c, uint8_t* base, int32_t outputAddress, in
 __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t outputAddress, int32_t outputSize, const uint8_t* literals, int32_t literalsSize)
 {
     if (literalsSize <= 63) {
+        ZC_STAT_C(64, 1);
         return raw_literals(c, base, outputAddress, outputSize, literals, literalsSize);
     }
     const int32_t headerSize = 3 + (literalsSize >= 1024 ? 1 : 0) + (literalsSize >= 16384 ? 1 : 0);
@@ -1140,6 +1165,7 @@ __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t ou
     const int32_t largestCount = find_largest_count(sh, maxSymbol);
     if (largestCount == literalsSize) {  // rleLiterals :380-398
         const int32_t hs = 1 + (literalsSize > 31 ? 1 : 0) + (literalsSize > 4095 ? 1 : 0);
+        ZC_STAT_C(64 + hs, 1);
         if (hs == 1) {
             base[outputAddress] = (uint8_t)(1 | (literalsSize << 3));
         }
@@ -1153,15 +1179,18 @@ __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t ou
         return hs + 1;
     }
     else if (largestCount <= (int32_t)((uint32_t)literalsSize >> 7) + 4) {
+        ZC_STAT_C(68, 1);
         return raw_literals(c, base, outputAddress, outputSize, literals, literalsSize);
     }
     HufCTable& previousTable = sh.huf[c.previousTable];
     const bool canReuse = huf_table_is_valid(sh, previousTable, maxSymbol);
     const bool preferReuse = literalsSize <= 1024;
+    ZC_STAT_C(canReuse ? 69 : (maxSymbol > previousTable.maxSymbol ? 60 : 70), 1);
     HufCTable* table;
     int32_t serializedTableSize;
     bool reuseTable;
     if (preferReuse && canReuse) {
+        ZC_STAT_C(71, 1);
         table = &previousTable;
         reuseTable = true;
         serializedTableSize = 0;
@@ -1171,9 +1200,17 @@ __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t ou
         c.temporaryCandidate = c.previousTable;
         HufCTable& newTable = sh.huf[c.temporaryTable];
         huf_table_initialize(sh, newTable, maxSymbol, huf_optimal_number_of_bits(11, literalsSize, maxSymbol));
+#ifdef ACHIP_HOST_STATS  // (which of optimalNumberOfBits' terms decides: the maximum, the input size, the symbol count, the floor of 5)
+        {
+            const int32_t bySize = highest_bit((uint32_t)(literalsSize - 1)) - 1, bySymbols = min_table_log(literalsSize, maxSymbol);
+            const int32_t capped = bySize < 11 ? bySize : 11;
+            ZC_STAT_C((capped > bySymbols ? capped : bySymbols) < 5 ? 61 : (bySymbols > capped ? 92 : (bySize < 11 ? 91 : 90)), 1);
+        }
+#endif
         serializedTableSize = huf_table_write(c, sh, newTable, base, outputAddress + headerSize, outputSize - headerSize);
         ZC_PROPAGATE(serializedTableSize);
         if (canReuse && huf_estimate_compressed_size(sh, previousTable, maxSymbol) <= serializedTableSize + huf_estimate_compressed_size(sh, newTable, maxSymbol)) {
+            ZC_STAT_C(72, 1);
             table = &previousTable;
             reuseTable = true;
             serializedTableSize = 0;
@@ -1181,6 +1218,7 @@ __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t ou
             c.temporaryCandidate = c.temporaryTable;
         }
         else {
+            ZC_STAT_C(canReuse ? 73 : 127, 1);
             table = &newTable;
             reuseTable = false;
         }
@@ -1189,6 +1227,7 @@ __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t ou
     const int32_t streamsAddress = outputAddress + headerSize + serializedTableSize;
     const int32_t streamsSize = outputSize - headerSize - serializedTableSize;
     const bool singleStream = literalsSize < 256;
+    ZC_STAT_C(singleStream ? 74 : 75, 1);
     int32_t compressedSize;
     wave_mem_order();
     if (singleStream) {
@@ -1244,11 +1283,14 @@ __device__ int32_t encode_literals(Ctx& c, Shared& sh, uint8_t* base, int32_t ou
     const int32_t totalSize = serializedTableSize + compressedSize;
     const int32_t minimumGain = (int32_t)((uint32_t)literalsSize >> 6) + 2;
     if (compressedSize == 0 || totalSize >= literalsSize - minimumGain) {
+        ZC_STAT_C(76, 1);
         c.previousCandidate = c.previousTable;
         c.temporaryCandidate = c.temporaryTable;
         return raw_literals(c, base, outputAddress, outputSize, literals, literalsSize);
     }
     const int32_t encodingType = reuseTable ? 3 : 2;
+    ZC_STAT_C(74 + headerSize, 1);
+    ZC_STAT_C(80, reuseTable ? 1 : 0);
     if (headerSize == 3) {
         st_le(base + outputAddress, (uint32_t)(encodingType | ((singleStream ? 0 : 1) << 2) | (literalsSize << 4) | (totalSize << 14)), 3);
     }
@@ -1286,6 +1328,8 @@ __device__ int32_t build_compression_table(Ctx& c, Shared& sh, FseCTable& table,
 {
     const int32_t tableLog = fse_optimal_table_log(maxTableLog, sequenceCount, maxSymbol);
     const int32_t lastCode = codes[sequenceCount - 1];
+    ZC_STAT_C(tableLog == maxTableLog ? 108 : (tableLog == 5 ? 111 : (tableLog == min_table_log(sequenceCount, maxSymbol) ? 110 : 109)), 1);
+    ZC_STAT_C(sh.counts[lastCode] > 1 ? 106 : 107, 1);
     if (sh.counts[lastCode] > 1) {
         sh.counts[lastCode] = sh.counts[lastCode] - 1;
         sequenceCount--;
@@ -1316,7 +1360,9 @@ __device__ int32_t compress_sequences(Ctx& c, Shared& sh, uint8_t* base, int32_t
         st2(base + output, (uint32_t)(sequenceCount - 0x7F00));
         output += 2;
     }
+    ZC_STAT_C(sequenceCount < 0x7F ? 116 : (sequenceCount < 0x7F00 ? 117 : 118), 1);
     if (sequenceCount == 0) {
+        ZC_STAT_C(119, 1);
         return output - outputAddress;
     }
     const int32_t headerAddress = output++;
@@ -1328,6 +1374,10 @@ __device__ int32_t compress_sequences(Ctx& c, Shared& sh, uint8_t* base, int32_t
     largestCount = find_largest_count(sh, maxSymbol);
     const int32_t llType = select_encoding_type(largestCount, sequenceCount, 6, true);
     const FseCTable* llTable;
+    ZC_STAT_C(93 + llType, 1);
+    ZC_STAT_C(102, llType == 0 && largestCount == sequenceCount ? 1 : 0);
+    ZC_STAT_C(103, llType == 0 && largestCount != sequenceCount && sequenceCount < ((1 << 6) * 9 >> 3) ? 1 : 0);
+    ZC_STAT_C(104, llType == 0 && largestCount != sequenceCount && sequenceCount >= ((1 << 6) * 9 >> 3) ? 1 : 0);
     if (llType == 1) {
         base[output] = c.codeLL[0];
         output++;
@@ -1350,6 +1400,11 @@ __device__ int32_t compress_sequences(Ctx& c, Shared& sh, uint8_t* base, int32_t
     largestCount = find_largest_count(sh, maxSymbol);
     const int32_t ofType = select_encoding_type(largestCount, sequenceCount, 5, maxSymbol < 28);
     const FseCTable* ofTable;
+    ZC_STAT_C(96 + ofType, 1);
+    ZC_STAT_C(102, ofType == 0 && largestCount == sequenceCount ? 1 : 0);
+    ZC_STAT_C(103, ofType == 0 && largestCount != sequenceCount && sequenceCount < ((1 << 5) * 9 >> 3) ? 1 : 0);
+    ZC_STAT_C(104, ofType == 0 && largestCount != sequenceCount && sequenceCount >= ((1 << 5) * 9 >> 3) ? 1 : 0);
+    ZC_STAT_C(105, maxSymbol < 28 ? 0 : 1);
     if (ofType == 1) {
         base[output] = c.codeOF[0];
         output++;
@@ -1372,6 +1427,10 @@ __device__ int32_t compress_sequences(Ctx& c, Shared& sh, uint8_t* base, int32_t
     largestCount = find_largest_count(sh, maxSymbol);
     const int32_t mlType = select_encoding_type(largestCount, sequenceCount, 6, true);
     const FseCTable* mlTable;
+    ZC_STAT_C(99 + mlType, 1);
+    ZC_STAT_C(102, mlType == 0 && largestCount == sequenceCount ? 1 : 0);
+    ZC_STAT_C(103, mlType == 0 && largestCount != sequenceCount && sequenceCount < ((1 << 6) * 9 >> 3) ? 1 : 0);
+    ZC_STAT_C(104, mlType == 0 && largestCount != sequenceCount && sequenceCount >= ((1 << 6) * 9 >> 3) ? 1 : 0);
     if (mlType == 1) {
         base[output] = c.codeML[0];
         output++;
@@ -1476,6 +1535,7 @@ __device__ int32_t compress_sequences(Ctx& c, Shared& sh, uint8_t* base, int32_t
     // The sequences 64 at a time: lane l fetches sequence top - l -- its codes, its three values, the bit counts of its codes and, from the
     // three tables, the two per-symbol deltas of each code (none of which depends on the states).
     for (int32_t top = sequenceCount - 2; top >= 0; top -= 64) {
+        ZC_STAT(top + 1 < 64 ? 120 : 121, 1);
         const int32_t mine = top - lane;
         int32_t vLL = 0, vML = 0, vOF = 0, bLL = 0, bML = 0, bOF = 0, nLL = 0, fLL = 0, nML = 0, fML = 0, nOF = 0, fOF = 0;
         if (mine >= 0) {
@@ -1628,6 +1688,7 @@ __device__ int32_t dfast_compress_block(Ctx& c, int32_t inputAddress, int32_t in
         int32_t shortHash = 0, longHash = 0, shortMatch = 0, longMatch = 0;
         bool repHit = false, longHit = false, shortHit = false;
         bool probed = false;
+        ZC_STAT_C(c.batchProbe && input - anchor < 256 - 64 ? 17 : 18, 1);
         if (c.batchProbe && input - anchor < 256 - 64) {
             // Batch probe: while nothing matches the serial loop visits input, input + 1, ... (its step is
             // ((input - anchor) >> 8) + 1 = 1 here) and changes nothing but the two tables, so the lanes test the next
@@ -1675,6 +1736,7 @@ __device__ int32_t dfast_compress_block(Ctx& c, int32_t inputAddress, int32_t in
             wave_mem_order();
             input += first;
             if (first >= 64 || ((hitMask >> first) & 1ull) == 0) {
+                ZC_STAT_C(19, 1);
                 width = 64;  // nothing in this batch (or the end of the block): keep going, wide
                 continue;
             }
@@ -1799,6 +1861,7 @@ __device__ int32_t compress_block(Ctx& c, Shared& sh, int32_t inputAddress, int3
     }
     const int32_t newOffset = (inputAddress + inputSize) - c.windowSize;  // enforceMaxDistance
     if (c.windowBaseOffset < newOffset) {
+        ZC_STAT_C(126, newOffset > 0 ? 1 : 0);
         c.windowBaseOffset = newOffset;
     }
     c.literalsLength = 0;
@@ -1829,9 +1892,11 @@ __device__ int32_t compress_block(Ctx& c, Shared& sh, int32_t inputAddress, int3
     }
     wave_mem_order();
     if (c.longLengthField == 1) {
+        ZC_STAT_C(122, 1);
         c.codeLL[c.longLengthPosition] = 35;
     }
     if (c.longLengthField == 2) {
+        ZC_STAT_C(123, 1);
         c.codeML[c.longLengthPosition] = 52;
     }
     wave_mem_order();
@@ -1848,8 +1913,10 @@ __device__ int32_t compress_block(Ctx& c, Shared& sh, int32_t inputAddress, int3
     }
     const int32_t maxCompressedSize = inputSize - ((int32_t)((uint32_t)inputSize >> 6) + 2);
     if (compressedSize > maxCompressedSize) {
+        ZC_STAT_C(124, 1);
         return 0;
     }
+    ZC_STAT_C(125, 1);
     c.offset0 = c.tempOffset0;  // context.commit()
     c.offset1 = c.tempOffset1;
     c.temporaryTable = c.temporaryCandidate;

@@ -23,15 +23,7 @@
 // :150); longer literal runs (incompressible data) take the serial step below, which is the Java loop as it stands.
 #pragma once
 
-#ifdef ACHIP_HOST_STATS  // (CPU emulator only: how often each part of the replay runs -- tools/hostemu/zc_stats.py)
-extern "C" long long g_zc_stats[64];
-// (out of line and not instrumented: under the emulator's access-granular lockstep every traced access is an order point of ALL lanes)
-static __attribute__((noinline, no_sanitize("coverage"))) void zc_stat_add(int i, long long n) { g_zc_stats[i] += n; }
-#define ZC_STAT(i, n) \
-    if (lane == 0) zc_stat_add((i), (n))
-#else
-#define ZC_STAT(i, n)
-#endif
+// (ZC_STAT: zstd_compress_body.h -- CPU emulator only: how often each part of the replay runs, tools/hostemu/zc_stats.py)
 
 namespace dmw {
 __device__ __forceinline__ uint32_t rl32(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }

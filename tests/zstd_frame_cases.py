@@ -179,35 +179,78 @@ def build_frame(literals, sequences, *, checksum=False, last_literals=None, cont
     return frame, plain
 
 
-def sequence_count(frame):
-    """the sequence count of a single-segment or windowed frame's first block, read from its literals and sequences headers (None: not one compressed block)"""
-    fhd = frame[4]
-    pos = 5 + (0 if fhd & 0x20 else 1) + ((1 if fhd & 0x20 else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6)) + (0 if fhd & 3 == 0 else 1 << ((fhd & 3) - 1))
-    h = int.from_bytes(frame[pos:pos + 3], "little")
-    if (h >> 1) & 3 != 2 or not h & 1:
-        return None
-    pos += 3
-    b0 = frame[pos]
+def read_frame_header(buf, pos=0):
+    """the fields of the frame header at `pos` (RFC 8878 3.1.1.1): a dict, with `end` the position of the first block"""
+    assert bytes(buf[pos:pos + 4]) == b"\x28\xb5\x2f\xfd", pos
+    fhd = buf[pos + 4]
+    single = bool(fhd & 0x20)
+    at = pos + 5
+    h = {"descriptor": fhd, "single_segment": single, "checksum": bool(fhd & 4), "content_size_flag": fhd >> 6, "window_descriptor": None, "window_log": None, "dictionary_id": None}
+    if not single:
+        h["window_descriptor"] = buf[at]
+        h["window_log"] = 10 + (buf[at] >> 3)
+        h["window_size"] = (1 << h["window_log"]) + ((1 << h["window_log"]) >> 3) * (buf[at] & 7)
+        at += 1
+    nd = 0 if fhd & 3 == 0 else 1 << ((fhd & 3) - 1)
+    if nd:
+        h["dictionary_id"] = int.from_bytes(buf[at:at + nd], "little")
+    at += nd
+    nc = (1 if single else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6)
+    h["content_size_bytes"] = nc
+    h["content_size"] = (int.from_bytes(buf[at:at + nc], "little") + (256 if nc == 2 else 0)) if nc else None
+    if single:
+        h["window_size"] = h["content_size"]
+    h["end"] = at + nc
+    return h
+
+
+def read_block_header(buf, pos):
+    """(last, type 0 raw / 1 RLE / 2 compressed / 3 reserved, the size field) of the block header at `pos` (3.1.1.2)"""
+    h = int.from_bytes(buf[pos:pos + 3], "little")
+    return h & 1, (h >> 1) & 3, h >> 3
+
+
+def read_literals_header(buf, pos):
+    """the literals section header at `pos` (3.1.1.3.1.1): a dict -- kind (index of LITERAL_KINDS), form (the size format field), header_bytes, regenerated,
+    compressed (None for raw and RLE literals), streams, and `end`: where the section ends"""
+    b0 = buf[pos]
     kind, form = b0 & 3, (b0 >> 2) & 3
     if kind < 2:
-        nbytes = 1 if form in (0, 2) else (2 if form == 1 else 3)
-        size = int.from_bytes(frame[pos:pos + nbytes], "little") >> (3 if nbytes == 1 else 4)
-        pos += nbytes + (size if kind == 0 else 1)
-    else:
-        nbytes = 3 if form < 2 else (4 if form == 2 else 5)
-        hh = int.from_bytes(frame[pos:pos + 5], "little")
-        comp = (hh >> 14) & 0x3FF if nbytes == 3 else ((hh >> 18) & 0x3FFF if nbytes == 4 else (hh >> 22) & 0x3FFFF)
-        pos += nbytes + comp
-    n = frame[pos]
-    if n == 255:
-        return int.from_bytes(frame[pos + 1:pos + 3], "little") + 0x7F00
-    return n if n < 128 else ((n - 128) << 8) + frame[pos + 1]
+        nbytes = 2 if form == 1 else (3 if form == 3 else 1)
+        regenerated = int.from_bytes(buf[pos:pos + nbytes], "little") >> (3 if nbytes == 1 else 4)
+        return {"kind": kind, "form": form, "header_bytes": nbytes, "regenerated": regenerated, "compressed": None, "streams": 0, "end": pos + nbytes + (regenerated if kind == 0 else 1)}
+    nbytes, bits = (3, 10) if form < 2 else ((4, 14) if form == 2 else (5, 18))
+    hh = int.from_bytes(buf[pos:pos + 5], "little")
+    regenerated, compressed = (hh >> 4) & ((1 << bits) - 1), (hh >> (4 + bits)) & ((1 << bits) - 1)
+    return {"kind": kind, "form": form, "header_bytes": nbytes, "regenerated": regenerated, "compressed": compressed, "streams": 1 if form == 0 else 4, "end": pos + nbytes + compressed}
+
+
+COUNT_FORMS = ("one byte", "two bytes", "255")
+
+
+def read_sequence_count(buf, pos):
+    """(the count, the index of its byte form in COUNT_FORMS, the position behind it) of the sequences section at `pos` (3.1.1.3.2.1)"""
+    n = buf[pos]
+    if n < 128:
+        return n, 0, pos + 1
+    if n < 255:
+        return ((n - 128) << 8) + buf[pos + 1], 1, pos + 2
+    return int.from_bytes(buf[pos + 1:pos + 3], "little") + 0x7F00, 2, pos + 3
+
+
+def sequence_count(frame):
+    """the sequence count of a single-segment or windowed frame's first block, read from its literals and sequences headers (None: not one compressed block)"""
+    pos = read_frame_header(frame)["end"]
+    last, kind, _ = read_block_header(frame, pos)
+    if kind != 2 or not last:
+        return None
+    return read_sequence_count(frame, read_literals_header(frame, pos + 3)["end"])[0]
 
 
 LITERAL_KINDS = ("raw", "rle", "compressed", "treeless")
 # every header form the format has (RFC 8878 3.1.1.3.1.1, 3.1.1.3.2.1): a literals block type with each value of its size format field -- for raw and RLE
 # literals the values 0 and 2 both mean one byte, and both are forms a reader must take -- and the three forms of the sequence count
-HEADER_FORMS = [("literals", kind, form) for kind in LITERAL_KINDS for form in range(4)] + [("count", n) for n in ("one byte", "two bytes", "255")]
+HEADER_FORMS = [("literals", kind, form) for kind in LITERAL_KINDS for form in range(4)] + [("count", n) for n in COUNT_FORMS]
 
 
 def header_forms(item):
@@ -216,33 +259,21 @@ def header_forms(item):
     forms = []
     pos = 0
     while pos < len(item):
-        assert item[pos:pos + 4] == b"\x28\xb5\x2f\xfd", pos
-        fhd = item[pos + 4]
-        single = bool(fhd & 0x20)
-        pos += 5 + (0 if single else 1) + (0 if fhd & 3 == 0 else 1 << ((fhd & 3) - 1)) + ((1 if single else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6))
+        fh = read_frame_header(item, pos)
+        pos = fh["end"]
         while True:
-            h = int.from_bytes(item[pos:pos + 3], "little")
+            last, kind, size = read_block_header(item, pos)
             pos += 3
-            last, kind, size = h & 1, (h >> 1) & 3, h >> 3
             assert kind != 3
             if kind == 2:
-                b0 = item[pos]
-                lit, form = b0 & 3, (b0 >> 2) & 3
-                forms.append(("literals", LITERAL_KINDS[lit], form))
-                if lit < 2:
-                    nbytes = 2 if form == 1 else (3 if form == 3 else 1)
-                    regenerated = int.from_bytes(item[pos:pos + nbytes], "little") >> (3 if nbytes == 1 else 4)
-                    at = pos + nbytes + (regenerated if lit == 0 else 1)
-                else:
-                    nbytes, bits = (3, 10) if form < 2 else ((4, 14) if form == 2 else (5, 18))
-                    at = pos + nbytes + ((int.from_bytes(item[pos:pos + 5], "little") >> (4 + bits)) & ((1 << bits) - 1))
-                assert at < pos + size
-                n = item[at]
-                forms.append(("count", "one byte" if n < 128 else ("two bytes" if n < 255 else "255")))
+                lit = read_literals_header(item, pos)
+                forms.append(("literals", LITERAL_KINDS[lit["kind"]], lit["form"]))
+                assert lit["end"] < pos + size
+                forms.append(("count", COUNT_FORMS[read_sequence_count(item, lit["end"])[1]]))
             pos += 1 if kind == 1 else size
             if last:
                 break
-        pos += 4 if fhd & 4 else 0
+        pos += 4 if fh["checksum"] else 0
     assert pos == len(item)
     return forms
 

@@ -3,8 +3,9 @@ order point -- the lockstep of a wavefront at the granularity of memory operatio
 parse on all 64 lanes and updates its tables in place).  Output, status and length against the oracle's restatement of the Java encoders:
 byte-identical or a mismatch.
 
-  check_enc.py [--quick] [--part block|zstd|stream|containers|snappyfan|edges]   the encoders' parity cases at sizes the emulator finishes in minutes
-                                                                   (edges: the constructed inputs of tests/encoder_edge_cases.py, every LZ4 / Snappy variant)
+  check_enc.py [--quick] [--part block|zstd|stream|containers|snappyfan|edges|zedges]   the encoders' parity cases at sizes the emulator finishes in minutes
+                                                                   (edges: the constructed inputs of tests/encoder_edge_cases.py, every LZ4 / Snappy variant;
+                                                                   zedges: those of tests/zstd_encoder_cases.py, every Zstd variant; with --quick without the larger ones)
   check_enc.py --chunked N                                         one ZstdOutputStream of N bytes (N >= 4 MiB: the chunked writer with its
                                                                    window slides, behind zstd.stream.chunked = 1 in the product)"""
 import ctypes, os, sys, time
@@ -177,6 +178,27 @@ def part_edges():
     return bad
 
 
+def part_zedges():
+    """the catalog of constructed Zstd inputs (tests/zstd_encoder_cases.py: emulator_cases(); a mismatch names its case) through every variant"""
+    from tests import zstd_encoder_cases
+    bad = 0
+    for v in (3, 0, 1, 2):
+        entries = zstd_encoder_cases.emulator_cases(v)
+        if quick:  # (without the larger cases: tests/test_zstd_encoder_cases.py runs them through the variants of the counting build)
+            entries = [e for e in entries if e[0] not in zstd_encoder_cases.EMULATOR_LARGE]
+        blocks = [d for _, d, _ in entries]
+        caps = [o.max_compressed_length("zstd", len(b)) for b in blocks]
+        want = [o.compress("zstd", b) for b in blocks]
+        t = time.time()
+        outs, status, _ = EncBatch(v).run(5, blocks, caps, unaligned=True)
+        wrong = [e[0] for e, c, s, w in zip(entries, outs, status, want) if s != 0 or c != w]
+        for name in wrong:
+            print("  MISMATCH zstd compress, variant %d: %s" % (v, name))
+        bad += len(wrong)
+        print("%-64s %4d items %8d bytes  %d mismatches  (%.0f s)" % ("zstd compress, variant %d, catalog of edges" % v, len(blocks), sum(len(b) for b in blocks), len(wrong), time.time() - t), flush=True)
+    return bad
+
+
 def chunked(n):
     src = b"".join(common.multi_block_plains())
     while len(src) < n:
@@ -222,7 +244,7 @@ def main():
         sys.exit(1 if ostream(sizes) else 0)
     if "--chunked" in sys.argv:
         sys.exit(1 if chunked(int(sys.argv[sys.argv.index("--chunked") + 1])) else 0)
-    parts = {"block": part_block, "zstd": part_zstd, "stream": part_stream, "containers": part_containers, "snappyfan": part_snappyfan, "edges": part_edges}
+    parts = {"block": part_block, "zstd": part_zstd, "stream": part_stream, "containers": part_containers, "snappyfan": part_snappyfan, "edges": part_edges, "zedges": part_zedges}
     only = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else None
     bad = 0
     for name, fn in parts.items():

@@ -9,7 +9,7 @@
 #include "../../aircompressor_amd/csrc/lz4_compress.hip"
 #include "../../aircompressor_amd/csrc/snappy_compress.hip"
 #ifdef ACHIP_HOST_STATS
-extern "C" { long long g_zc_stats[64]; }  // tools/hostemu/zc_stats.py (0..19: Zstd), enc_paths.py (20..39: LZ4, 40..59: Snappy)
+extern "C" { long long g_zc_stats[128]; }  // tools/hostemu/zc_stats.py (0..19: the Zstd window match finder), enc_paths.py (20..39: LZ4, 40..59: Snappy, 60, 61, 64..127: the Zstd encoder)
 #endif
 #include "../../aircompressor_amd/csrc/zstd_compress.hip"
 #include "../../aircompressor_amd/csrc/zstd_stream.hip"

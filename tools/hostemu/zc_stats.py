@@ -10,7 +10,7 @@ src = os.path.join(ROOT, "tools", "hostemu", "emu_enc.cpp")
 subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fno-omit-frame-pointer", "-DACHIP_HOST_STATS", "-fsanitize-coverage=inline-8bit-counters,trace-loads,trace-stores",
                 "-I", os.path.join(ROOT, "tools", "hostemu"), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"), "-o", so, src], check=True)
 lib = ctypes.CDLL(so)
-stats = (ctypes.c_longlong * 64).in_dll(lib, "g_zc_stats")
+stats = (ctypes.c_longlong * 128).in_dll(lib, "g_zc_stats")
 o = oracle_lib.load()
 class EncBatch(EmuBatch):
     def __init__(self, option): self.lib = lib; self.options = {}; self.option = option
@@ -22,7 +22,7 @@ files = common.corpus_files() if hasattr(common, "corpus_files") else None
 sample = [d for _, d, _ in common.corpus_sample()]
 for idx in [int(a) for a in sys.argv[1:]] or [0, 1, 2]:
     data = (sample[idx] * 3)[:131072] if len(sample[idx]) < 131072 else sample[idx][:131072]
-    for i in range(64): stats[i] = 0
+    for i in range(128): stats[i] = 0
     outs, status, _ = EncBatch(3).run(5, [data], [o.max_compressed_length("zstd", len(data))])
     assert status[0] == 0 and outs[0] == o.compress("zstd", data)
     print("sample %d (%d bytes -> %d):" % (idx, len(data), len(outs[0])), ", ".join("%s %d" % (n, stats[i]) for i, n in enumerate(names)))

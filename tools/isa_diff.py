@@ -43,10 +43,10 @@ def main():
                 jobs.append((tree, src, os.path.join(tmp, "%s-%s.s" % (tag, os.path.basename(src)[:-4]))))
         with ThreadPoolExecutor(8) as ex:
             list(ex.map(lambda j: build(*j), jobs))
-        before = {}
-        for p in glob.glob(os.path.join(tmp, "old-*.s")):
-            before.update(functions(p))
         for p in sorted(glob.glob(os.path.join(tmp, "new-*.s"))):
+            # (per unit: a function of a shared header is compiled into several units, each with its own inlining around it)
+            old_unit = os.path.join(tmp, "old-" + os.path.basename(p)[4:])
+            before = functions(old_unit) if os.path.exists(old_unit) else {}
             now = functions(p)
             changed = [k for k, v in now.items() if k in before and before[k] != v]
             added = [k for k in now if k not in before]
