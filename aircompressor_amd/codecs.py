@@ -177,15 +177,39 @@ class Lz4FrameHipDecompressor(_HipDecompressor):
     _codec = "lz4frame"
 
 
+def _check_snappyframed_writer(block_size, min_compression_ratio):
+    # SnappyFramedOutputStream's constructor  M/snappy/SnappyFramedOutputStream.java:83, :90; the text is the library's for the same value
+    if not (min_compression_ratio > 0 and min_compression_ratio <= 1.0):
+        raise IllegalArgumentException("minCompressionRatio %s must be between (0,1.0]." % native.java_double_text(min_compression_ratio))
+    if not 0 < block_size <= 65536:
+        raise IllegalArgumentException("blockSize must be in (0, 65536]")
+
+
 class SnappyFramedHipCompressor(_HipCompressor):
     """One-shot form of SnappyFramedOutputStream (M/snappy/SnappyFramedOutputStream.java:73-96, 113-145, 200-255): what
     `new SnappyFramedOutputStream(c, out); write(data); close()` leaves in `out` -- the stream header, then per 64 KiB block a
     chunk with the masked CRC-32C of its plaintext, Snappy-compressed by the HIP block encoder or stored raw when it does not
-    reach 0.85.  max_compressed_length is the capacity this form asks for (the stream class has none)."""
+    reach 0.85.  max_compressed_length is the capacity this form asks for (the stream class has none).
+    write_checksums, block_size and min_compression_ratio are the arguments of the five-argument constructor (:77-91), checked as it checks them and handed
+    to the context before every call -- two compressors that share a context keep their own values; write_checksums=False at the defaults is
+    newChecksumFreeBenchmarkOutputStream (:65-69)."""
     _codec = "snappyframed"
 
+    def __init__(self, device=0, native_ctx=None, write_checksums=True, block_size=65536, min_compression_ratio=0.85):
+        _check_snappyframed_writer(block_size, min_compression_ratio)  # (before anything asks for a device)
+        super().__init__(device, native_ctx)
+        self.write_checksums, self.block_size, self.min_compression_ratio = bool(write_checksums), int(block_size), float(min_compression_ratio)
+
+    @classmethod
+    def new_checksum_free_benchmark_compressor(cls, device=0, native_ctx=None):
+        return cls(device, native_ctx, write_checksums=False)
+
+    def _compress(self, src, dst):
+        self._native.set_snappyframed_writer(self.write_checksums, self.block_size, self.min_compression_ratio)
+        return super()._compress(src, dst)
+
     def max_compressed_length(self, uncompressed_size):
-        r = self._lib.achip_snappyframed_max_compressed_length(uncompressed_size)
+        r = self._lib.achip_snappyframed_max_compressed_length_for(uncompressed_size, self.block_size)
         if r < 0:
             raise IllegalArgumentException("uncompressedSize is negative: %d" % uncompressed_size if uncompressed_size < 0 else
                                            "Maximum compressed length exceeds Integer.MAX_VALUE for uncompressedSize: %d" % uncompressed_size)
@@ -195,8 +219,17 @@ class SnappyFramedHipCompressor(_HipCompressor):
 class SnappyFramedHipDecompressor(_HipDecompressor):
     """One-shot form of SnappyFramedInputStream read to the end of the stream (M/snappy/SnappyFramedInputStream.java:52-73,
     135-305; checksums verified): compressed, raw, skippable and stream-identifier chunks, the reference's error for every
-    malformed stream (its IOException / EOFException texts are the ACHIP_D_SNF_* messages)."""
+    malformed stream (its IOException / EOFException texts are the ACHIP_D_SNF_* messages).  verify_checksums=False is the reader's third constructor
+    argument (:74-79): the CRC fields are not looked at."""
     _codec = "snappyframed"
+
+    def __init__(self, device=0, native_ctx=None, verify_checksums=True):
+        super().__init__(device, native_ctx)
+        self.verify_checksums = bool(verify_checksums)
+
+    def _decompress(self, src, dst):
+        self._native.set_snappyframed_verify_checksums(self.verify_checksums)
+        return super()._decompress(src, dst)
 
 
 class _HadoopHipCompressor(_HipCompressor):

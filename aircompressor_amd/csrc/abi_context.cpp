@@ -186,6 +186,13 @@ int32_t achip_lz4frame_max_compressed_length(int32_t n) { return int_bound(n, [&
 // stream header + per 64 KiB block a chunk header, the masked CRC and at most the block itself (a compressed chunk is kept
 // only at <= 0.85 of its block: M/snappy/SnappyFramedOutputStream.java:214)
 int32_t achip_snappyframed_max_compressed_length(int32_t n) { return int_bound(n, [&] { return achip::bound::snappyframed(n); }); }
+// the same for a writer built with another block size (achip_ctx_set_snappyframed_writer)
+int32_t achip_snappyframed_max_compressed_length_for(int32_t n, int32_t blockSize)
+{
+    if (n < 0) return bad_argument("uncompressedSize is negative");
+    if (blockSize <= 0 || blockSize > ACHIP_SNF_MAX_BLOCK_SIZE) return bad_argument("blockSize must be in (0, 65536]");
+    return int_bound(n, [&] { return achip::bound::snappyframed(n, blockSize); });
+}
 int32_t achip_hadoop_max_compressed_length(int32_t codec, int32_t n, int32_t bufferSize)
 {
     // per chunk of bufferSize - overhead plaintext bytes: two big-endian ints and at most the codec's maxCompressedLength
@@ -357,6 +364,86 @@ int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx)
 {
     if (!ctx) return bad_argument("ctx is null");
     return ctx->kernel.lz4Acceleration;
+}
+
+// Double.toString(v), which the reference's "%1s" prints: the shortest digits -- two at least -- that read back as v (Double.MIN_VALUE is 4.9E-324), d.d in
+// [1e-3, 1e7) and d.dE±n outside.  aircompressor_amd/native.py has the same function for the Python classes' own check (tests/test_snf_params_abi.py compares).
+static std::string java_double_text(double v)
+{
+    if (v != v) return "NaN";
+    if (v == 0) return std::signbit(v) ? "-0.0" : "0.0";
+    if (std::isinf(v)) return v < 0 ? "-Infinity" : "Infinity";
+    char digits[40];
+    int precision = 2;
+    for (; precision < 17; precision++) {
+        snprintf(digits, sizeof(digits), "%.*e", precision - 1, v);
+        if (strtod(digits, nullptr) == v) break;
+    }
+    snprintf(digits, sizeof(digits), "%.*e", precision - 1, v);  // [-]d[.ddd]e[+-]xx
+    std::string mantissa(digits, strchr(digits, 'e'));
+    const int exponent = atoi(strchr(digits, 'e') + 1);
+    const std::string sign = mantissa[0] == '-' ? "-" : "";
+    std::string d;
+    for (char c : mantissa) {
+        if (c >= '0' && c <= '9') d += c;
+    }
+    while (d.size() > 1 && d.back() == '0') d.pop_back();
+    if (exponent >= -3 && exponent < 7) {
+        std::string whole, frac;
+        if (exponent < 0) {
+            whole = "0";
+            frac = std::string((size_t)(-exponent - 1), '0') + d;
+        }
+        else {
+            if ((int)d.size() < exponent + 1) d.append((size_t)(exponent + 1) - d.size(), '0');
+            whole = d.substr(0, (size_t)exponent + 1);
+            frac = d.substr((size_t)exponent + 1);
+        }
+        return sign + whole + "." + (frac.empty() ? "0" : frac);
+    }
+    return sign + d.substr(0, 1) + "." + (d.size() > 1 ? d.substr(1) : "0") + "E" + std::to_string(exponent);
+}
+
+// SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio): the checks, their order and their texts are the constructor's
+// (M/snappy/SnappyFramedOutputStream.java:83, :90); the ratio arrives as Double.doubleToRawLongBits of it
+int32_t achip_ctx_set_snappyframed_writer(achip_ctx* ctx, int32_t writeChecksums, int32_t blockSize, int64_t minCompressionRatioBits)
+{
+    switch (achip::check_snf_writer(writeChecksums, blockSize, minCompressionRatioBits)) {
+        case achip::SnfRefusal::Ratio: {
+            const std::string text = "minCompressionRatio " + java_double_text(achip::snf_ratio(minCompressionRatioBits)) + " must be between (0,1.0].";
+            return bad_argument(text.c_str());
+        }
+        case achip::SnfRefusal::BlockSize: return bad_argument("blockSize must be in (0, 65536]");
+        case achip::SnfRefusal::Flag: return bad_argument("writeChecksums must be 0 or 1");
+        case achip::SnfRefusal::None: break;
+    }
+    if (!ctx) return bad_argument("ctx is null");
+    achip::set_snf_writer(ctx->kernel, writeChecksums, blockSize, minCompressionRatioBits);
+    return 0;
+}
+
+int32_t achip_ctx_get_snappyframed_writer(achip_ctx* ctx, int32_t* writeChecksums, int32_t* blockSize, int64_t* minCompressionRatioBits)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    if (writeChecksums) *writeChecksums = ctx->kernel.snfWriteChecksums;
+    if (blockSize) *blockSize = ctx->kernel.snfBlockSize;
+    if (minCompressionRatioBits) *minCompressionRatioBits = ctx->kernel.snfMinRatioBits;
+    return 0;
+}
+
+// SnappyFramedInputStream(decompressor, in, verifyChecksums)  M/snappy/SnappyFramedInputStream.java:74-79
+int32_t achip_ctx_set_snappyframed_verify_checksums(achip_ctx* ctx, int32_t verify)
+{
+    if (verify != 0 && verify != 1) return bad_argument("verifyChecksums must be 0 or 1");
+    if (!ctx) return bad_argument("ctx is null");
+    achip::set_snf_verify(ctx->kernel, verify);
+    return 0;
+}
+
+int32_t achip_ctx_get_snappyframed_verify_checksums(achip_ctx* ctx)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    return ctx->kernel.snfVerifyChecksums;
 }
 
 // n words at byte `offset` of the scratch, once everything the context has launched is done

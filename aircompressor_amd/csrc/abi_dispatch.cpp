@@ -298,7 +298,7 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
         }
         case ACHIP_OP_SNAPPYFRAMED_COMPRESS: {
             if (const int32_t r = ensure_scratch(ctx, achip::snappyframed_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
-            e = achip::launch_snappyframed_compress(a, ctx->stream.get(), ctx->scratch.get(), ctx->snappyFramedCompressVariant);
+            e = achip::launch_snappyframed_compress(a, ctx->stream.get(), ctx->scratch.get(), ctx->snappyFramedCompressVariant, ctx->kernel);
             break;
         }
         case ACHIP_OP_LZ4HADOOP_DECOMPRESS:
@@ -556,7 +556,7 @@ int32_t achip_compress_bound_batch(achip_ctx* ctx, int32_t codecOp, const int32_
     if (!ctx) return bad_argument("ctx is null");
     if (!srcLen || !outSize || !status) return bad_argument("null array");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(achip::launch_compress_bound(codecOp, srcLen, outSize, status, nBlocks, ctx->hadoopBufferSize, ctx->stream.get()));
+    HIP_TRY(achip::launch_compress_bound(codecOp, srcLen, outSize, status, nBlocks, ctx->hadoopBufferSize, ctx->stream.get(), ctx->kernel.snfBlockSize));
     return 0;
 }
 

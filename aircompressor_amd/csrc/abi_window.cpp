@@ -43,7 +43,7 @@ int32_t launch_window(achip_ctx* ctx, int32_t op, const achip::BatchArgs& args, 
             break;
         case ACHIP_OP_SNAPPYFRAMED_COMPRESS:
             if (const int32_t r = window_scratch(ctx, achip::snappyframed_window_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
-            e = achip::launch_snappyframed_window_compress(a, w, ctx->stream.get(), ctx->scratch.get());
+            e = achip::launch_snappyframed_window_compress(a, w, ctx->stream.get(), ctx->scratch.get(), ctx->kernel);
             break;
         default:
             if (const int32_t r = window_scratch(ctx, achip::hadoop_window_compress_scratch_bytes(a.nBlocks)); r < 0) return r;

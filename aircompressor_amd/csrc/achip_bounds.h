@@ -30,13 +30,15 @@ __host__ __device__ inline int64_t lz4frame(int64_t n)
     const int64_t blocks = (n + (4 << 20) - 1) / (4 << 20);
     return 7 + 4 + n + 4 * blocks;
 }
-// stream header + per 64 KiB block a chunk header, the masked CRC and at most the block itself (a compressed chunk is kept only at <= 0.85 of its
-// block: M/snappy/SnappyFramedOutputStream.java:214)
-__host__ __device__ inline int64_t snappyframed(int64_t n)
+// stream header + per block of blockSize bytes (1 .. 65536: the writer's constructor argument, M/snappy/SnappyFramedOutputStream.java:77-91) a chunk header, the
+// CRC field and at most the block itself (a compressed chunk is kept only at <= minCompressionRatio <= 1.0 of its block: :213)
+__host__ __device__ inline int64_t snappyframed(int64_t n, int32_t blockSize)
 {
-    const int64_t blocks = (n + 65535) / 65536;
+    const int64_t blocks = (n + blockSize - 1) / blockSize;
     return 10 + 8 * blocks + n;
 }
+// the same at the default block size of 64 KiB
+__host__ __device__ inline int64_t snappyframed(int64_t n) { return snappyframed(n, 65536); }
 // per chunk of bufferSize - overhead plaintext bytes: two big-endian ints and at most the codec's maxCompressedLength (M/lz4/Lz4HadoopOutputStream.java:44-46,
 // 107-118, 128-131; M/snappy/SnappyHadoopOutputStream.java likewise).  -1: the buffer leaves a chunk no room
 __host__ __device__ inline int64_t hadoop(bool snappyCodec, int64_t n, int32_t bufferSize)

@@ -104,7 +104,9 @@ hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void
 int64_t lz4frame_compress_scratch_bytes(int32_t items, bool least);
 hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
 int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams);
-hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant);
+// ks: the writer's constructor arguments (KernelSettings::snf*; the defaults: the stream as new SnappyFramedOutputStream(compressor, out) writes it); the readers take
+// snfVerifyChecksums from the `ks` they have
+hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const KernelSettings& ks);
 int64_t snappyframed_compress_scratch_bytes(int32_t nStreams);
 hipError_t launch_hadoop_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux, const KernelSettings& ks);
 int64_t hadoop_decompress_scratch_bytes(int32_t nStreams, int32_t bufferSize);
@@ -113,7 +115,7 @@ int64_t hadoop_compress_scratch_bytes(int32_t nStreams);
 // ... and their window forms (WindowArgs, achip_device.h): an item is a piece of a stream that begins at a unit boundary; `w` says per item what was taken and why the call stopped
 hipError_t launch_snappyframed_window_decompress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
 int64_t snappyframed_window_decompress_scratch_bytes(int32_t nStreams);
-hipError_t launch_snappyframed_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch);
+hipError_t launch_snappyframed_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, const KernelSettings& ks);
 int64_t snappyframed_window_compress_scratch_bytes(int32_t nStreams);
 hipError_t launch_hadoop_window_decompress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, bool snappy, int32_t bufferSize, int variant, const AuxScratch* aux,
                                            const KernelSettings& ks);
@@ -142,8 +144,10 @@ hipError_t launch_plan_outputs(const int64_t* outSize, const int32_t* status, in
 int64_t plan_outputs_scratch_bytes(int32_t nBlocks);
 
 // ---- compress bounds and the dense copy of a compressed batch (pack_outputs.hip) ----
-// `op`: one of the eight ACHIP_OP_*_COMPRESS (achip_compress_bound_batch has refused any other); hadoopBufferSize: the context's, for the two Hadoop ops
-hipError_t launch_compress_bound(int32_t op, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks, int32_t hadoopBufferSize, hipStream_t stream);
+// `op`: one of the eight ACHIP_OP_*_COMPRESS (achip_compress_bound_batch has refused any other); hadoopBufferSize: the context's, for the two Hadoop ops;
+// snfBlockSize: the context's x-snappy-framed block size, for that op
+hipError_t launch_compress_bound(int32_t op, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks, int32_t hadoopBufferSize, hipStream_t stream,
+                                 int32_t snfBlockSize);
 // The copy's unit of work: this many bytes of destination address.  Chosen by the kernel's shape, not by a sweep: a workgroup of 256 lanes keeps eight 16-byte
 // loads per lane in flight (8 x 256 x 16), which amortises the two searches a tile costs and still cuts a 64 KiB-block batch's ~1.5 GiB stream into ~50 000 tiles,
 // 25 per workgroup of the grid.  Not tuned on a device (profiles/pack_rate.txt).

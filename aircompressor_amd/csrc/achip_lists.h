@@ -67,7 +67,7 @@ struct WriterList {
     int32_t* bStream;   // per entry; -1: a hole (its stream did not fit)
     int32_t* bIndex;
     int32_t* bSize;     // bytes written at the worst-case place
-    int32_t* counters;  // [0] entries allocated, [1] entries in the list (sealed), [2] encode cursor, [3] compact cursor
+    int32_t* counters;  // [0] entries allocated, at most the capacity, [1] entries in the list (sealed), [2] encode cursor, [3] compact cursor, [4, 5] the plan's 64-bit cursor
     void carve(Carver& k, int32_t* counterWords, int64_t nStreams, bool serialRoute)
     {
         counters = counterWords;
@@ -108,14 +108,26 @@ inline BatchArgs ChunkBatch::as_batch(const BatchArgs& a, int32_t capacity) cons
 }
 
 // A writer's plan, the part every stream shares: reserve `n` entries for `stream` and fill them in.  Returns whether they fit; what becomes of
-// a stream that does not (an error, another kernel) is the caller's.
-__device__ __forceinline__ bool plan_entries(const WriterList& L, int32_t stream, int32_t n)
+// a stream that does not (an error, another kernel) is the caller's.  `capacity`: the entries the launcher seals the list at (<= CAPACITY).
+// The reservation cannot wrap, whatever the batch: a stream with more entries than the whole list reserves nothing (with a block size of 1 one stream may
+// bring 2^27 blocks), so every addition is at most `capacity` <= 2^20, and the cursor the additions go to is the 64-bit word at counters[4, 5] -- fewer than
+// 2^31 streams of at most 2^20 entries stay below 2^51.  counters[0], which seal_kernel reads, is kept as min(reserved, capacity) by an atomicMax: no index
+// below is ever negative or beyond `capacity`.
+__device__ __forceinline__ bool plan_entries(const WriterList& L, int32_t stream, int32_t n, int32_t capacity = CAPACITY)
 {
-    const int32_t first = n > 0 ? atomicAdd(L.counters, n) : 0;
-    const bool fits = (int64_t)first + n <= CAPACITY;
-    L.sFirst[stream] = first;
+    if (n > capacity) {
+        L.sFirst[stream] = 0;
+        L.sCount[stream] = 0;
+        return false;
+    }
+    const int64_t first = n > 0 ? (int64_t)atomicAdd((unsigned long long*)(L.counters + 4), (unsigned long long)n) : 0;
+    const bool fits = first + n <= capacity;
+    if (n > 0 && first < capacity) {
+        atomicMax(L.counters, fits ? (int32_t)(first + n) : capacity);
+    }
+    L.sFirst[stream] = fits ? (int32_t)first : 0;
     L.sCount[stream] = fits ? n : 0;
-    for (int64_t k = 0; k < n && first + k < CAPACITY; k++) {
+    for (int64_t k = 0; k < n && first + k < capacity; k++) {
         L.bStream[first + k] = fits ? stream : -1;
         L.bIndex[first + k] = (int32_t)k;
     }

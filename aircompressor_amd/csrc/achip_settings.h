@@ -26,7 +26,53 @@ struct KernelSettings {
     // a launch on the corpus batch, 100 x the input: 1 280 workgroups x 3 slabs x 32 KiB = 120 MB of tables, 15 MB per XCD against 4 MB of L2.
     int snappyMemWaves = 3;
     int snappyTierWorkgroups = 256 * 5;  // the persistent grid where the unit count is known on the device only (no option; tools/hostemu makes it small)
+    // SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio) and SnappyFramedInputStream(decompressor, in, verifyChecksums)
+    // (no options: achip_ctx_set_snappyframed_writer / _verify_checksums -- properties of the stream objects, not tuning knobs).  Every x-snappy-framed encode of
+    // the context cuts its input at snfBlockSize (1 .. 65536), keeps a chunk compressed at compressed / length <= the double whose bits snfMinRatioBits holds
+    // (0.85), and writes the masked CRC-32C or 0; every x-snappy-framed decode compares the CRC field or skips the CRC pass altogether.
+    int snfWriteChecksums = 1;
+    int snfBlockSize = 65536;
+    int64_t snfMinRatioBits = 0x3FEB333333333333LL;
+    int snfVerifyChecksums = 1;
+    int snfEncodeWorkgroups = 0;  // the block-list writer's persistent encode grid (no option; 0: 768, tools/hostemu makes it small)
+    int snfListEntries = 0;  // entries of the x-snappy-framed writer's block list (no option; 0: lists::CAPACITY, tools/hostemu makes it small: streams beyond it take the serial kernel)
 };
+
+// achip_ctx_set_snappyframed_writer's checks, in the order of SnappyFramedOutputStream's constructor (M/snappy/SnappyFramedOutputStream.java:83, :90): the ratio
+// (its IEEE-754 bits) must be > 0 and <= 1.0 -- NaN fails --, then the block size must be in (0, 65536], then the flag 0 or 1.  set_ stores only what passed all
+// three: a refused call leaves `ks` as it was.
+enum class SnfRefusal { None, Ratio, BlockSize, Flag };
+inline double snf_ratio(int64_t bits)
+{
+    double ratio;
+    static_assert(sizeof(ratio) == sizeof(bits), "a double is 64 bits");
+    memcpy(&ratio, &bits, sizeof(ratio));
+    return ratio;
+}
+inline SnfRefusal check_snf_writer(int32_t writeChecksums, int32_t blockSize, int64_t minRatioBits)
+{
+    const double ratio = snf_ratio(minRatioBits);
+    if (!(ratio > 0 && ratio <= 1.0)) return SnfRefusal::Ratio;
+    if (blockSize <= 0 || blockSize > 65536) return SnfRefusal::BlockSize;
+    if (writeChecksums != 0 && writeChecksums != 1) return SnfRefusal::Flag;
+    return SnfRefusal::None;
+}
+inline SnfRefusal set_snf_writer(KernelSettings& ks, int32_t writeChecksums, int32_t blockSize, int64_t minRatioBits)
+{
+    const SnfRefusal r = check_snf_writer(writeChecksums, blockSize, minRatioBits);
+    if (r == SnfRefusal::None) {
+        ks.snfWriteChecksums = writeChecksums;
+        ks.snfBlockSize = blockSize;
+        ks.snfMinRatioBits = minRatioBits;
+    }
+    return r;
+}
+inline SnfRefusal set_snf_verify(KernelSettings& ks, int32_t verify)
+{
+    if (verify != 0 && verify != 1) return SnfRefusal::Flag;
+    ks.snfVerifyChecksums = verify;
+    return SnfRefusal::None;
+}
 
 // Everything achip_ctx_set_option writes.  A mixed batch's helper contexts take a copy of their caller's (abi_dispatch.cpp: mix_lane).
 struct Settings {

@@ -30,14 +30,14 @@ static_assert(PACK_TILE_BYTES == (int64_t)PACK_THREADS * PACK_CHUNKS * 16, "a ti
 
 // ---------------------------------------------------------------------------------------------------------------------
 // bounds
-__device__ __forceinline__ int64_t compress_bound(int32_t op, int32_t n, int32_t hadoopBufferSize)
+__device__ __forceinline__ int64_t compress_bound(int32_t op, int32_t n, int32_t hadoopBufferSize, int32_t snfBlockSize)
 {
     switch (op) {
         case ACHIP_OP_LZ4_COMPRESS: return bound::lz4(n);
         case ACHIP_OP_SNAPPY_COMPRESS: return bound::snappy(n);
         case ACHIP_OP_ZSTD_COMPRESS: return bound::zstd(n);
         case ACHIP_OP_LZ4FRAME_COMPRESS: return bound::lz4frame(n);
-        case ACHIP_OP_SNAPPYFRAMED_COMPRESS: return bound::snappyframed(n);
+        case ACHIP_OP_SNAPPYFRAMED_COMPRESS: return bound::snappyframed(n, snfBlockSize);
         case ACHIP_OP_LZ4HADOOP_COMPRESS: return bound::hadoop(false, n, hadoopBufferSize);
         case ACHIP_OP_SNAPPYHADOOP_COMPRESS: return bound::hadoop(true, n, hadoopBufferSize);
         case ACHIP_OP_ZSTDSTREAM_COMPRESS: return bound::zstdstream(n);
@@ -182,14 +182,14 @@ __device__ __forceinline__ void copy_mixed_chunk(PACK_SOURCES_DECL, const int64_
 }  // namespace pk
 
 __global__ __launch_bounds__(256) void compress_bound_kernel(int32_t op, const int32_t* __restrict__ srcLen, int64_t* __restrict__ outSize, int32_t* __restrict__ status, int32_t n,
-                                                             int32_t hadoopBufferSize)
+                                                             int32_t hadoopBufferSize, int32_t snfBlockSize)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) {
         return;
     }
     const int32_t len = srcLen[i];
-    const int64_t b = len < 0 ? -1 : pk::compress_bound(op, len, hadoopBufferSize);
+    const int64_t b = len < 0 ? -1 : pk::compress_bound(op, len, hadoopBufferSize, snfBlockSize);
     const bool bad = b < 0 || b > 0x7FFFFFFF;
     outSize[i] = bad ? 0 : b;
     status[i] = bad ? mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT) : 0;
@@ -270,12 +270,12 @@ __global__ __launch_bounds__(256) void pack_copy_kernel(PACK_SOURCES_DECL, const
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers
-hipError_t launch_compress_bound(int32_t op, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks, int32_t hadoopBufferSize, hipStream_t stream)
+hipError_t launch_compress_bound(int32_t op, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks, int32_t hadoopBufferSize, hipStream_t stream, int32_t snfBlockSize)
 {
     if (nBlocks <= 0) {
         return hipSuccess;
     }
-    hipLaunchKernelGGL(compress_bound_kernel, dim3((unsigned)(((int64_t)nBlocks + 255) / 256)), dim3(256), 0, stream, op, srcLen, outSize, status, nBlocks, hadoopBufferSize);
+    hipLaunchKernelGGL(compress_bound_kernel, dim3((unsigned)(((int64_t)nBlocks + 255) / 256)), dim3(256), 0, stream, op, srcLen, outSize, status, nBlocks, hadoopBufferSize, snfBlockSize);
     return hipGetLastError();
 }
 

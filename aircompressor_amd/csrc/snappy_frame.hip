@@ -18,6 +18,7 @@
 #include "achip_launch.h"
 #include "achip_lists.h"
 #include "achip_window.h"
+#include "achip_bounds.h"
 
 namespace achip {
 
@@ -62,6 +63,8 @@ __device__ __forceinline__ int32_t read_uncompressed_length(const uint8_t* in, i
     return 0;
 }
 
+// VERIFY: SnappyFramedInputStream's verifyChecksums (:74-79, :188-193).  false: the checksum field is not looked at and no CRC is computed.
+template <bool VERIFY>
 __device__ int32_t decompress_item(const Crc32cTables& tables, const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* lds, int lane,
                                    int32_t& opOut, int64_t& eo)
 {
@@ -144,7 +147,9 @@ __device__ int32_t decompress_item(const Crc32cTables& tables, const uint8_t* __
             wave_mem_order();
             produced = dlen;
         }
-        if (stored != crc32c_mask(wave_crc32c(tables, out + o, produced, lane))) SNF_FAIL(ACHIP_D_SNF_CHECKSUM, chunk);  // :188-193
+        if constexpr (VERIFY) {
+            if (stored != crc32c_mask(wave_crc32c(tables, out + o, produced, lane))) SNF_FAIL(ACHIP_D_SNF_CHECKSUM, chunk);  // :188-193
+        }
         o += produced;
         pos += length;
     }
@@ -155,13 +160,16 @@ __device__ int32_t decompress_item(const Crc32cTables& tables, const uint8_t* __
 
 }  // namespace snf
 
-__global__ __launch_bounds__(64) void snappyframed_decompress_kernel(BatchArgs a, int32_t* nextItem, const int32_t* only)
+template <bool VERIFY>
+__device__ __forceinline__ void snappyframed_decompress_items(const BatchArgs& a, int32_t* nextItem, const int32_t* only)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[snf::IN_RING + snf::OUT_RING];
     __shared__ Crc32cTables tables;
     __shared__ int32_t item;
     const int lane = threadIdx.x;
-    crc32c_tables_init(tables, lane);
+    if constexpr (VERIFY) {
+        crc32c_tables_init(tables, lane);
+    }
     for (;;) {
         __syncthreads();
         if (lane == 0) {
@@ -177,7 +185,7 @@ __global__ __launch_bounds__(64) void snappyframed_decompress_kernel(BatchArgs a
         }
         int32_t op = 0;
         int64_t eo = 0;
-        const int32_t st = snf::decompress_item(tables, a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], a.dstCap[block], lds, lane, op, eo);
+        const int32_t st = snf::decompress_item<VERIFY>(tables, a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], a.dstCap[block], lds, lane, op, eo);
         if (lane == 0) {
             a.outLen[block] = st == 0 ? op : 0;
             a.status[block] = st;
@@ -186,19 +194,39 @@ __global__ __launch_bounds__(64) void snappyframed_decompress_kernel(BatchArgs a
     }
 }
 
+__global__ __launch_bounds__(64) void snappyframed_decompress_kernel(BatchArgs a, int32_t* nextItem, const int32_t* only)
+{
+    snappyframed_decompress_items<true>(a, nextItem, only);
+}
+
+// verifyChecksums = false (achip_ctx_set_snappyframed_verify_checksums)
+__global__ __launch_bounds__(64) void snappyframed_decompress_noverify_kernel(BatchArgs a, int32_t* nextItem, const int32_t* only)
+{
+    snappyframed_decompress_items<false>(a, nextItem, only);
+}
+
 namespace snf {
 constexpr int64_t SLAB_BYTES = (32 + MAX_BLOCK_SIZE + MAX_BLOCK_SIZE / 6 + 63) / 64 * 64;  // maxCompressedLength(65536), rounded
 
-// new SnappyFramedOutputStream(c, out); write(all); close()  -- M/snappy/SnappyFramedOutputStream.java:73-96, 113-145, 158-171
-__device__ int32_t compress_item(const Crc32cTables& tables, uint16_t* table, const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* slab,
-                                 int lane, int32_t& opOut)
+// The constructor's arguments (SnappyFramedOutputStream.java:77-91; achip_ctx_set_snappyframed_writer), the same for every lane of a launch: blockSize in
+// (0, 65536] cuts the input, a chunk is kept compressed at (double)compressed / (double)length <= minRatio (:213, a correctly rounded fp64 division: this
+// file is built without fast-math), and without checksums the CRC field is 0 and no CRC is computed (:203).
+struct WriterParams {
+    int32_t blockSize;
+    int32_t checksums;
+    double minRatio;
+};
+
+// new SnappyFramedOutputStream(c, out, writeChecksums, blockSize, minCompressionRatio); write(all); close()  -- M/snappy/SnappyFramedOutputStream.java:73-96, 113-145, 158-171
+__device__ int32_t compress_item(const WriterParams& p, const Crc32cTables& tables, uint16_t* table, const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap,
+                                 uint8_t* slab, int lane, int32_t& opOut)
 {
+    const int32_t blockSize = p.blockSize;
     opOut = 0;
     if (inLen < 0) {
         return mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT);
     }
-    const int64_t blocks = ((int64_t)inLen + MAX_BLOCK_SIZE - 1) / MAX_BLOCK_SIZE;
-    const int64_t bound = 10 + 8 * blocks + (int64_t)inLen;  // achip_snappyframed_max_compressed_length
+    const int64_t bound = bound::snappyframed(inLen, blockSize);  // achip_snappyframed_max_compressed_length_for
     if (bound > 0x7FFFFFFF) {
         return mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT);
     }
@@ -211,17 +239,17 @@ __device__ int32_t compress_item(const Crc32cTables& tables, uint16_t* table, co
         out[9] = 0x59;
     }
     int32_t o = 10;
-    for (int64_t pos = 0; pos < inLen; pos += MAX_BLOCK_SIZE) {  // full blocks straight from the input, the rest through the buffer :126-145, :186-192
-        const int32_t length = (int32_t)(inLen - pos < MAX_BLOCK_SIZE ? inLen - pos : MAX_BLOCK_SIZE);
+    for (int64_t pos = 0; pos < inLen; pos += blockSize) {  // full blocks straight from the input, the rest through the buffer :126-145, :186-192
+        const int32_t length = (int32_t)(inLen - pos < blockSize ? inLen - pos : blockSize);
         const uint8_t* block = in + pos;
-        const uint32_t crc = crc32c_mask(wave_crc32c(tables, block, length, lane));  // writeCompressed :204
+        const uint32_t crc = p.checksums != 0 ? crc32c_mask(wave_crc32c(tables, block, length, lane)) : 0u;  // writeCompressed :203
         int32_t cst = 0, compressed = 0;
         snappy_compress_buffer_mw(table, block, length, slab, (int32_t)SLAB_BYTES, lane, cst, compressed);  // :206-211
         wave_mem_order();
         if (cst != 0) {
             return cst;
         }
-        const bool keep = ((double)compressed / (double)length) <= 0.85;  // :214
+        const bool keep = ((double)compressed / (double)length) <= p.minRatio;  // :213
         const uint8_t* data = keep ? slab : block;
         const int32_t dlen = keep ? compressed : length;
         if (lane == 0) {  // writeBlock :241-254
@@ -238,13 +266,15 @@ __device__ int32_t compress_item(const Crc32cTables& tables, uint16_t* table, co
 }
 }  // namespace snf
 
-__global__ __launch_bounds__(64) void snappyframed_compress_kernel(BatchArgs a, uint8_t* slabs, int32_t* nextItem, const int32_t* only)
+__global__ __launch_bounds__(64) void snappyframed_compress_kernel(BatchArgs a, snf::WriterParams p, uint8_t* slabs, int32_t* nextItem, const int32_t* only)
 {
     __shared__ uint16_t table[snc::MAX_HASH_TABLE_SIZE];
     __shared__ Crc32cTables tables;
     __shared__ int32_t item;
     const int lane = threadIdx.x;
-    crc32c_tables_init(tables, lane);
+    if (p.checksums != 0) {
+        crc32c_tables_init(tables, lane);
+    }
     uint8_t* slab = slabs + (size_t)blockIdx.x * snf::SLAB_BYTES;
     for (;;) {
         __syncthreads();
@@ -260,7 +290,7 @@ __global__ __launch_bounds__(64) void snappyframed_compress_kernel(BatchArgs a, 
             continue;  // done by the block-parallel path
         }
         int32_t op = 0;
-        const int32_t st = snf::compress_item(tables, table, a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], a.dstCap[block], slab, lane, op);
+        const int32_t st = snf::compress_item(p, tables, table, a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], a.dstCap[block], slab, lane, op);
         if (lane == 0) {
             a.outLen[block] = st == 0 ? op : 0;
             a.status[block] = st;
@@ -272,18 +302,18 @@ __global__ __launch_bounds__(64) void snappyframed_compress_kernel(BatchArgs a, 
 // ---------------------------------------------------------------------------------------------------------------------
 // Block-parallel writer (the default).  The blocks of a stream are independent; only a chunk's position depends on the
 // sizes of the chunks before it.  But every block except a stream's last is full, and a chunk is never larger than its block
-// stored raw, so block k can be written at its WORST-CASE position 10 + k * (8 + 65536) without knowing anything else:
+// stored raw, so block k can be written at its WORST-CASE position 10 + k * (8 + blockSize) without knowing anything else:
 //   plan     one lane per stream checks the arguments and appends its blocks to one list;
 //   encode   persistent wavefronts (two tiers, as in snappy_compress.hip) take blocks from the list: masked CRC-32C, the block
-//            encoder into a private slab, the 0.85 rule, chunk header + body to the worst-case position, the chunk's size noted;
+//            encoder into a private slab, the ratio rule (0.85 unless set), chunk header + body to the worst-case position, the chunk's size noted;
 //   compact  one wavefront per stream writes the stream header and moves the chunks left into place, in order (a move to the
 //            left with all loads of a round before its stores is safe at any distance).
 // Streams whose blocks do not fit into the list go to the one-wavefront-per-stream kernel above.
 namespace snf {
-constexpr int32_t WORST_CHUNK = 8 + MAX_BLOCK_SIZE;
+__device__ __forceinline__ int64_t worst_chunk(int32_t blockSize) { return 8 + (int64_t)blockSize; }
 using BlockList = lists::WriterList;  // (bSize: a chunk's bytes, header included; counters [32]: the serial kernel's cursor)
 
-__global__ __launch_bounds__(64) void snappyframed_plan_kernel(BatchArgs a, BlockList L)
+__global__ __launch_bounds__(64) void snappyframed_plan_kernel(BatchArgs a, BlockList L, int32_t blockSize, int32_t capacity)
 {
     const int32_t stream = blockIdx.x * 64 + threadIdx.x;
     if (stream >= a.nBlocks) {
@@ -296,8 +326,8 @@ __global__ __launch_bounds__(64) void snappyframed_plan_kernel(BatchArgs a, Bloc
         st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT);
     }
     else {
-        blocks = ((int64_t)inLen + MAX_BLOCK_SIZE - 1) / MAX_BLOCK_SIZE;
-        const int64_t bound = 10 + 8 * blocks + (int64_t)inLen;  // achip_snappyframed_max_compressed_length
+        blocks = ((int64_t)inLen + blockSize - 1) / blockSize;
+        const int64_t bound = bound::snappyframed(inLen, blockSize);  // achip_snappyframed_max_compressed_length_for
         if (bound > 0x7FFFFFFF) {
             st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT);
         }
@@ -305,20 +335,23 @@ __global__ __launch_bounds__(64) void snappyframed_plan_kernel(BatchArgs a, Bloc
             st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_SNF_MAX_OUTPUT);
         }
     }
-    const bool fits = lists::plan_entries(L, stream, st == 0 ? (int32_t)blocks : 0);
+    const bool fits = lists::plan_entries(L, stream, st == 0 ? (int32_t)blocks : 0, capacity);
     L.sStatus[stream] = st;
     L.sSerial[stream] = fits ? 0 : 1;  // (its stream goes the other way)
 }
 
 // WINDOW (achip_window_compress_batch): the stream identifier is there only where head[stream] says so, and a.srcLen is what the window plan took
 template <bool WINDOW>
-__device__ __forceinline__ void encode_blocks(const BatchArgs& a, const BlockList& L, uint8_t* outSlabs, uint16_t* tableSlabs, const int32_t* head)
+__device__ __forceinline__ void encode_blocks(const BatchArgs& a, const BlockList& L, const WriterParams& p, uint8_t* outSlabs, uint16_t* tableSlabs, const int32_t* head)
 {
     __shared__ uint16_t ldsTable[snc::MAX_HASH_TABLE_SIZE];
     __shared__ Crc32cTables tables;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    crc32c_tables_init(tables, lane);  // (all four wavefronts write the same values between the same barriers)
+    const int32_t blockSize = p.blockSize;
+    if (p.checksums != 0) {
+        crc32c_tables_init(tables, lane);  // (all four wavefronts write the same values between the same barriers)
+    }
     uint8_t* const slab = outSlabs + ((size_t)blockIdx.x * 4 + wave) * SLAB_BYTES;
     uint16_t* const tableSlab = tableSlabs + ((size_t)blockIdx.x * 3 + (wave > 0 ? wave - 1 : 0)) * snc::MAX_HASH_TABLE_SIZE;
     const int32_t total = L.counters[1];
@@ -336,12 +369,12 @@ __device__ __forceinline__ void encode_blocks(const BatchArgs& a, const BlockLis
             continue;
         }
         const int32_t k = L.bIndex[b];
-        const int64_t pos = (int64_t)k * MAX_BLOCK_SIZE;
+        const int64_t pos = (int64_t)k * blockSize;
         const int32_t inLen = a.srcLen[stream];
-        const int32_t length = (int32_t)(inLen - pos < MAX_BLOCK_SIZE ? inLen - pos : MAX_BLOCK_SIZE);
+        const int32_t length = (int32_t)(inLen - pos < blockSize ? inLen - pos : blockSize);
         const uint8_t* block = a.srcBase + a.srcOff[stream] + pos;
-        uint8_t* out = a.dstBase + a.dstOff[stream] + (WINDOW ? head[stream] : 10) + (int64_t)k * WORST_CHUNK;
-        const uint32_t crc = crc32c_mask(wave_crc32c(tables, block, length, lane));  // writeCompressed :204
+        uint8_t* out = a.dstBase + a.dstOff[stream] + (WINDOW ? head[stream] : 10) + (int64_t)k * worst_chunk(blockSize);
+        const uint32_t crc = p.checksums != 0 ? crc32c_mask(wave_crc32c(tables, block, length, lane)) : 0u;  // writeCompressed :203
         int32_t cst = 0, compressed = 0;
         if (wave == 0) {
             snappy_compress_buffer_mw(ldsTable, block, length, slab, (int32_t)SLAB_BYTES, lane, cst, compressed);  // :206-211
@@ -350,7 +383,7 @@ __device__ __forceinline__ void encode_blocks(const BatchArgs& a, const BlockLis
             snappy_compress_buffer_mw(tableSlab, block, length, slab, (int32_t)SLAB_BYTES, lane, cst, compressed);
         }
         wave_mem_order();
-        const bool keep = ((double)compressed / (double)length) <= 0.85;  // :214
+        const bool keep = ((double)compressed / (double)length) <= p.minRatio;  // :213
         const uint8_t* data = keep ? slab : block;
         const int32_t dlen = keep ? compressed : length;
         if (lane == 0) {  // writeBlock :241-254
@@ -364,18 +397,18 @@ __device__ __forceinline__ void encode_blocks(const BatchArgs& a, const BlockLis
     }
 }
 
-__global__ __launch_bounds__(256) void snappyframed_encode_kernel(BatchArgs a, BlockList L, uint8_t* outSlabs, uint16_t* tableSlabs)
+__global__ __launch_bounds__(256) void snappyframed_encode_kernel(BatchArgs a, BlockList L, WriterParams p, uint8_t* outSlabs, uint16_t* tableSlabs)
 {
-    encode_blocks<false>(a, L, outSlabs, tableSlabs, nullptr);
+    encode_blocks<false>(a, L, p, outSlabs, tableSlabs, nullptr);
 }
 
-__global__ __launch_bounds__(256) void snappyframed_window_encode_kernel(BatchArgs a, BlockList L, uint8_t* outSlabs, uint16_t* tableSlabs, const int32_t* head)
+__global__ __launch_bounds__(256) void snappyframed_window_encode_kernel(BatchArgs a, BlockList L, WriterParams p, uint8_t* outSlabs, uint16_t* tableSlabs, const int32_t* head)
 {
-    encode_blocks<true>(a, L, outSlabs, tableSlabs, head);
+    encode_blocks<true>(a, L, p, outSlabs, tableSlabs, head);
 }
 
 template <bool WINDOW>
-__device__ __forceinline__ void compact_streams(const BatchArgs& a, const BlockList& L, const int32_t* head)
+__device__ __forceinline__ void compact_streams(const BatchArgs& a, const BlockList& L, int32_t blockSize, const int32_t* head)
 {
     const int lane = threadIdx.x;
     for (;;) {
@@ -404,7 +437,7 @@ __device__ __forceinline__ void compact_streams(const BatchArgs& a, const BlockL
             const int32_t first = L.sFirst[stream], n = L.sCount[stream];
             for (int32_t k = 0; k < n; k++) {
                 const int32_t size = L.bSize[first + k];
-                const int64_t from = lead + (int64_t)k * WORST_CHUNK;
+                const int64_t from = lead + (int64_t)k * worst_chunk(blockSize);
                 if (from != o) {
                     wave_mem_order();
                     group_copy<64>(out + o, out + from, size, lane);  // to the left; every lane loads before it stores
@@ -421,19 +454,22 @@ __device__ __forceinline__ void compact_streams(const BatchArgs& a, const BlockL
     }
 }
 
-__global__ __launch_bounds__(64) void snappyframed_compact_kernel(BatchArgs a, BlockList L)
+__global__ __launch_bounds__(64) void snappyframed_compact_kernel(BatchArgs a, BlockList L, int32_t blockSize)
 {
-    compact_streams<false>(a, L, nullptr);
+    compact_streams<false>(a, L, blockSize, nullptr);
 }
 
-__global__ __launch_bounds__(64) void snappyframed_window_compact_kernel(BatchArgs a, BlockList L, const int32_t* head)
+__global__ __launch_bounds__(64) void snappyframed_window_compact_kernel(BatchArgs a, BlockList L, int32_t blockSize, const int32_t* head)
 {
-    compact_streams<true>(a, L, head);
+    compact_streams<true>(a, L, blockSize, head);
 }
 
 // The window form of the plan (achip_window_compress_batch): the stream identifier under ACHIP_WINDOW_FIRST, the full blocks the window holds and the
 // destination has worst-case room for, the partial tail only under ACHIP_WINDOW_LAST; taken[] is what the encode kernel sees as the input's length.
-__global__ __launch_bounds__(64) void snappyframed_window_plan_kernel(BatchArgs a, BlockList L, WindowArgs w, int32_t* taken, int32_t* head)
+// A window takes at most its share of the block list, capacity / windows blocks (at least one): with small blocks a call can hold more blocks than the list has
+// entries, and such a window stops behind its share with NEED_ROOM, need 0 -- the caller's loop calls again, as for any other stop with progress.  Only a call of
+// more windows than the list has entries still fails (ACHIP_D_UNSUPPORTED).
+__global__ __launch_bounds__(64) void snappyframed_window_plan_kernel(BatchArgs a, BlockList L, WindowArgs w, int32_t blockSize, int32_t capacity, int32_t* taken, int32_t* head)
 {
     const int32_t stream = blockIdx.x * 64 + threadIdx.x;
     if (stream >= a.nBlocks) {
@@ -447,20 +483,28 @@ __global__ __launch_bounds__(64) void snappyframed_window_plan_kernel(BatchArgs 
         st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_BAD_ARGUMENT);
     }
     else {
-        const int64_t full = inLen / MAX_BLOCK_SIZE, rest = inLen % MAX_BLOCK_SIZE;
+        const int64_t worst = worst_chunk(blockSize);
+        const int64_t full = inLen / blockSize, rest = inLen % blockSize;
         const int64_t missing = cap < lead ? lead : 0;  // not even the stream identifier fits: nothing is written
         const int64_t room = cap < lead ? 0 : cap - lead;
-        blocks = full < room / WORST_CHUNK ? full : room / WORST_CHUNK;
-        consumed = blocks * MAX_BLOCK_SIZE;
-        if (blocks < full) {
+        const int64_t share = capacity / a.nBlocks > 1 ? capacity / a.nBlocks : 1;
+        blocks = full < room / worst ? full : room / worst;
+        const bool listFull = blocks > share || (blocks == share && blocks == full && rest > 0 && (flags & ACHIP_WINDOW_LAST) != 0 && room - blocks * worst >= 8 + rest);
+        blocks = blocks < share ? blocks : share;
+        consumed = blocks * blockSize;
+        if (listFull) {  // (there is input and room for more: the list's share is what ends the call)
             stop = ACHIP_STOP_NEED_ROOM;
-            need = missing + WORST_CHUNK;
+            need = 0;
+        }
+        else if (blocks < full) {
+            stop = ACHIP_STOP_NEED_ROOM;
+            need = missing + worst;
         }
         else if (rest > 0 && (flags & ACHIP_WINDOW_LAST) == 0) {
             stop = missing != 0 ? ACHIP_STOP_NEED_ROOM : ACHIP_STOP_NEED_INPUT;
-            need = missing != 0 ? missing : MAX_BLOCK_SIZE;
+            need = missing != 0 ? missing : blockSize;
         }
-        else if (rest > 0 && room - blocks * WORST_CHUNK < 8 + rest) {
+        else if (rest > 0 && room - blocks * worst < 8 + rest) {
             stop = ACHIP_STOP_NEED_ROOM;
             need = missing + 8 + rest;
         }
@@ -476,7 +520,7 @@ __global__ __launch_bounds__(64) void snappyframed_window_plan_kernel(BatchArgs 
             lead = 0;
         }
     }
-    if (!lists::plan_entries(L, stream, st == 0 ? (int32_t)blocks : 0)) {  // (more than a million blocks in one call)
+    if (!lists::plan_entries(L, stream, st == 0 ? (int32_t)blocks : 0, capacity)) {  // (more windows in one call than the list has entries)
         st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_UNSUPPORTED);
     }
     L.sStatus[stream] = st;
@@ -516,11 +560,31 @@ int64_t snappyframed_compress_scratch_bytes(int32_t nStreams)
     return k.used();
 }
 
-hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant)
+namespace {
+snf::WriterParams writer_params(const KernelSettings& ks)
+{
+    snf::WriterParams p;
+    p.blockSize = ks.snfBlockSize;
+    p.checksums = ks.snfWriteChecksums;
+    p.minRatio = snf_ratio(ks.snfMinRatioBits);  // (the ratio crosses the C ABI as its bit pattern)
+    return p;
+}
+int32_t list_entries(const KernelSettings& ks)
+{
+    return ks.snfListEntries > 0 && ks.snfListEntries < lists::CAPACITY ? ks.snfListEntries : lists::CAPACITY;
+}
+unsigned encode_grid(const KernelSettings& ks)
+{
+    return (unsigned)(ks.snfEncodeWorkgroups > 0 && ks.snfEncodeWorkgroups < SNF_ENCODE_WORKGROUPS ? ks.snfEncodeWorkgroups : SNF_ENCODE_WORKGROUPS);
+}
+}  // namespace
+
+hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
+    const snf::WriterParams p = writer_params(ks);
     lists::Carver k(scratch);
     SnfWriterScratch S;
     S.carve(k, a.nBlocks);
@@ -530,15 +594,16 @@ hipError_t launch_snappyframed_compress(const BatchArgs& a, hipStream_t stream, 
     if (e != hipSuccess) return e;
     const unsigned serialGrid = (unsigned)(a.nBlocks < SNF_COMPRESS_WAVES ? a.nBlocks : SNF_COMPRESS_WAVES);
     if (variant == 0) {  // one wavefront per stream
-        hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, S.serialSlabs, counters + 32, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, p, S.serialSlabs, counters + 32, (const int32_t*)nullptr);
         return hipGetLastError();
     }
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
-    hipLaunchKernelGGL(snf::snappyframed_plan_kernel, dim3(perStream), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, counters, lists::CAPACITY);
-    hipLaunchKernelGGL(snf::snappyframed_encode_kernel, dim3(SNF_ENCODE_WORKGROUPS), dim3(256), 0, stream, a, L, S.outSlabs, S.tableSlabs);
-    hipLaunchKernelGGL(snf::snappyframed_compact_kernel, dim3((unsigned)(a.nBlocks < 2048 ? a.nBlocks : 2048)), dim3(64), 0, stream, a, L);
-    hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, S.serialSlabs, counters + 32, (const int32_t*)L.sSerial);
+    const int32_t capacity = list_entries(ks);
+    hipLaunchKernelGGL(snf::snappyframed_plan_kernel, dim3(perStream), dim3(64), 0, stream, a, L, p.blockSize, capacity);
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, counters, capacity);
+    hipLaunchKernelGGL(snf::snappyframed_encode_kernel, dim3(encode_grid(ks)), dim3(256), 0, stream, a, L, p, S.outSlabs, S.tableSlabs);
+    hipLaunchKernelGGL(snf::snappyframed_compact_kernel, dim3((unsigned)(a.nBlocks < 2048 ? a.nBlocks : 2048)), dim3(64), 0, stream, a, L, p.blockSize);
+    hipLaunchKernelGGL(snappyframed_compress_kernel, dim3(serialGrid), dim3(64), 0, stream, a, p, S.serialSlabs, counters + 32, (const int32_t*)L.sSerial);
     return hipGetLastError();
 }
 
@@ -762,12 +827,16 @@ __global__ __launch_bounds__(64) void snappyframed_walk_kernel(BatchArgs a, Chun
     }
 }
 
-__global__ __launch_bounds__(64) void snappyframed_verify_kernel(BatchArgs a, ChunkList L)
+// VERIFY = false (verifyChecksums off): what is left of the step is the copy of the stored chunks
+template <bool VERIFY>
+__device__ __forceinline__ void verify_chunks(const BatchArgs& a, const ChunkList& L)
 {
     __shared__ Crc32cTables tables;
     __shared__ int32_t item;
     const int lane = threadIdx.x;
-    crc32c_tables_init(tables, lane);
+    if constexpr (VERIFY) {
+        crc32c_tables_init(tables, lane);
+    }
     const int32_t total = L.counters[1];
     for (;;) {
         __syncthreads();
@@ -788,17 +857,30 @@ __global__ __launch_bounds__(64) void snappyframed_verify_kernel(BatchArgs a, Ch
             produced = rawLen;
         }
         else {
-            if (L.cStatus[c] != 0) {
+            if (!VERIFY || L.cStatus[c] != 0) {
                 continue;  // the block decoder's verdict stands
             }
             produced = L.cOutLen[c];
         }
-        const bool ok = L.cCrc[c] == crc32c_mask(wave_crc32c(tables, dst, produced, lane));
+        bool ok = true;
+        if constexpr (VERIFY) {
+            ok = L.cCrc[c] == crc32c_mask(wave_crc32c(tables, dst, produced, lane));
+        }
         if (lane == 0) {
             L.cStatus[c] = ok ? 0 : mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_SNF_CHECKSUM);
             L.cErrOff[c] = ok ? 0 : (int64_t)L.cPos[c];
         }
     }
+}
+
+__global__ __launch_bounds__(64) void snappyframed_verify_kernel(BatchArgs a, ChunkList L)
+{
+    verify_chunks<true>(a, L);
+}
+
+__global__ __launch_bounds__(64) void snappyframed_stored_kernel(BatchArgs a, ChunkList L)
+{
+    verify_chunks<false>(a, L);
 }
 
 __global__ __launch_bounds__(64) void snappyframed_fold_kernel(BatchArgs a, ChunkList L)
@@ -922,9 +1004,11 @@ hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream
     hipError_t e = hipMemsetAsync(counters, 0, 4096, stream);
     if (e != hipSuccess) return e;
     const int32_t maxWaves = 256 * 8;
+    const bool verify = ks.snfVerifyChecksums != 0;
+    const auto serial = verify ? snappyframed_decompress_kernel : snappyframed_decompress_noverify_kernel;
     if (variant == 0) {  // one wavefront per stream
         const unsigned grid = (unsigned)(a.nBlocks < maxWaves ? a.nBlocks : maxWaves);
-        hipLaunchKernelGGL(snappyframed_decompress_kernel, dim3(grid), dim3(64), 0, stream, a, counters + 32, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(serial, dim3(grid), dim3(64), 0, stream, a, counters + 32, (const int32_t*)nullptr);
         return hipGetLastError();
     }
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
@@ -935,12 +1019,13 @@ hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream
     bool decoded = false;
     e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), 1, stream, counters, counters + 16, aux, ks, want, &decoded);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(snf::snappyframed_verify_kernel, dim3(maxWaves), dim3(64), 0, stream, a, L);
+    const auto check = verify ? snf::snappyframed_verify_kernel : snf::snappyframed_stored_kernel;  // verify off: no CRC pass, the stored chunks' copy alone
+    hipLaunchKernelGGL(check, dim3(maxWaves), dim3(64), 0, stream, a, L);
     hipLaunchKernelGGL(snf::snappyframed_fold_kernel, dim3(perStream), dim3(64), 0, stream, a, L);
     // streams that did not fit into the lists
     {
         const unsigned grid = (unsigned)(a.nBlocks < maxWaves ? a.nBlocks : maxWaves);
-        hipLaunchKernelGGL(snappyframed_decompress_kernel, dim3(grid), dim3(64), 0, stream, a, counters + 32, (const int32_t*)L.sSerial);
+        hipLaunchKernelGGL(serial, dim3(grid), dim3(64), 0, stream, a, counters + 32, (const int32_t*)L.sSerial);
     }
     return hipGetLastError();
 }
@@ -975,7 +1060,8 @@ hipError_t launch_snappyframed_window_decompress(const BatchArgs& a, const Windo
     bool decoded = false;
     e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), 1, stream, counters, counters + 16, aux, ks, want, &decoded);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(snf::snappyframed_verify_kernel, dim3(maxWaves), dim3(64), 0, stream, a, (const snf::ChunkList&)L);
+    const auto check = ks.snfVerifyChecksums != 0 ? snf::snappyframed_verify_kernel : snf::snappyframed_stored_kernel;
+    hipLaunchKernelGGL(check, dim3(maxWaves), dim3(64), 0, stream, a, (const snf::ChunkList&)L);
     hipLaunchKernelGGL(snf::snappyframed_window_fold_kernel, dim3(perStream), dim3(64), 0, stream, a, L, w);
     return hipGetLastError();
 }
@@ -1001,11 +1087,13 @@ int64_t snappyframed_window_compress_scratch_bytes(int32_t nStreams)
 }
 
 // the window plan, then the block-parallel writer's encode and compact over what the plan took
-hipError_t launch_snappyframed_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch)
+hipError_t launch_snappyframed_window_compress(const BatchArgs& a, const WindowArgs& w, hipStream_t stream, void* scratch, const KernelSettings& ks)
 {
     if (a.nBlocks <= 0) {
         return hipSuccess;
     }
+    const snf::WriterParams p = writer_params(ks);
+    const int32_t capacity = list_entries(ks);
     lists::Carver k(scratch);
     SnfWindowWriterScratch S;
     S.carve(k, a.nBlocks);
@@ -1015,10 +1103,10 @@ hipError_t launch_snappyframed_window_compress(const BatchArgs& a, const WindowA
     BatchArgs t = a;
     t.srcLen = S.taken;
     const unsigned perStream = (unsigned)((a.nBlocks + 63) / 64);
-    hipLaunchKernelGGL(snf::snappyframed_window_plan_kernel, dim3(perStream), dim3(64), 0, stream, a, L, w, S.taken, S.head);
-    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, lists::CAPACITY);
-    hipLaunchKernelGGL(snf::snappyframed_window_encode_kernel, dim3(SNF_ENCODE_WORKGROUPS), dim3(256), 0, stream, t, L, S.outSlabs, S.tableSlabs, (const int32_t*)S.head);
-    hipLaunchKernelGGL(snf::snappyframed_window_compact_kernel, dim3((unsigned)(a.nBlocks < 2048 ? a.nBlocks : 2048)), dim3(64), 0, stream, t, L, (const int32_t*)S.head);
+    hipLaunchKernelGGL(snf::snappyframed_window_plan_kernel, dim3(perStream), dim3(64), 0, stream, a, L, w, p.blockSize, capacity, S.taken, S.head);
+    hipLaunchKernelGGL(lists::seal_kernel, dim3(1), dim3(1), 0, stream, L.counters, capacity);
+    hipLaunchKernelGGL(snf::snappyframed_window_encode_kernel, dim3(encode_grid(ks)), dim3(256), 0, stream, t, L, p, S.outSlabs, S.tableSlabs, (const int32_t*)S.head);
+    hipLaunchKernelGGL(snf::snappyframed_window_compact_kernel, dim3((unsigned)(a.nBlocks < 2048 ? a.nBlocks : 2048)), dim3(64), 0, stream, t, L, p.blockSize, (const int32_t*)S.head);
     hipLaunchKernelGGL(win::writer_verdict_kernel, dim3(perStream), dim3(64), 0, stream, a, w);
     return hipGetLastError();
 }

@@ -3,6 +3,8 @@
 """
 import ctypes
 import os
+import math
+import struct
 
 from .errors import HipUnavailableError, IllegalArgumentException, MalformedInputException
 
@@ -42,6 +44,11 @@ SIGNATURES = {
     "achip_ctx_set_lz4_acceleration": (_i32, [_vp, _i32]),
     "achip_ctx_get_lz4_acceleration": (_i32, [_vp]),
     "achip_snappyframed_max_compressed_length": (_i32, [_i32]),
+    "achip_snappyframed_max_compressed_length_for": (_i32, [_i32, _i32]),
+    "achip_ctx_set_snappyframed_writer": (_i32, [_vp, _i32, _i32, _i64]),
+    "achip_ctx_get_snappyframed_writer": (_i32, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
+    "achip_ctx_set_snappyframed_verify_checksums": (_i32, [_vp, _i32]),
+    "achip_ctx_get_snappyframed_verify_checksums": (_i32, [_vp]),
     "achip_snappyframed_decompress_batch": (_i32, _BATCH),
     "achip_snappyframed_compress_batch": (_i32, _BATCH),
     "achip_snappyframed_compress": (_i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64)]),
@@ -149,6 +156,39 @@ def load_library():
     return _lib
 
 
+SNF_DEFAULT_BLOCK_SIZE = SNF_MAX_BLOCK_SIZE = 65536
+SNF_DEFAULT_MIN_RATIO = 0.85  # ACHIP_SNF_DEFAULT_MIN_RATIO_BITS
+
+
+def double_bits(value):
+    """Double.doubleToRawLongBits"""
+    return struct.unpack("<q", struct.pack("<d", float(value)))[0]
+
+
+def java_double_text(value):
+    """Double.toString(value), as the library prints a refused ratio (abi_context.cpp): the shortest digits, two at least, that read back as the value"""
+    v = float(value)
+    if v != v:
+        return "NaN"
+    if v == 0:
+        return "-0.0" if math.copysign(1.0, v) < 0 else "0.0"
+    if math.isinf(v):
+        return "-Infinity" if v < 0 else "Infinity"
+    text = next(t for t in ("%.*e" % (p - 1, v) for p in range(2, 18)) if float(t) == v)
+    mantissa, exponent = text.split("e")
+    sign, digits, exponent = ("-" if v < 0 else ""), mantissa.lstrip("-").replace(".", "").rstrip("0") or "0", int(exponent)
+    if -3 <= exponent < 7:
+        digits = digits.ljust(exponent + 1, "0") if exponent >= 0 else "0" * -exponent + digits
+        whole, frac = (digits[:exponent + 1], digits[exponent + 1:]) if exponent >= 0 else ("0", digits[1:])
+        return sign + whole + "." + (frac or "0")
+    return sign + digits[0] + "." + (digits[1:] or "0") + "E%d" % exponent
+
+
+def bits_double(bits):
+    """Double.longBitsToDouble"""
+    return struct.unpack("<d", struct.pack("<q", int(bits)))[0]
+
+
 def status_class(status):
     return (-status) & 15 if status < 0 else 0
 
@@ -218,6 +258,33 @@ class HipNative:
         if r < 0:
             raise_for_status(r)
         return r
+
+    def set_snappyframed_writer(self, write_checksums=True, block_size=SNF_DEFAULT_BLOCK_SIZE, min_compression_ratio=SNF_DEFAULT_MIN_RATIO):
+        """SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio) for this context's x-snappy-framed encodes; the ratio
+        crosses as its IEEE-754 bits"""
+        r = self.lib.achip_ctx_set_snappyframed_writer(self.ctx, 1 if write_checksums else 0, int(block_size), double_bits(min_compression_ratio))
+        if r < 0:
+            raise IllegalArgumentException(self.lib.achip_last_error().decode(), r)
+
+    def get_snappyframed_writer(self):
+        """-> (write_checksums, block_size, min_compression_ratio)"""
+        checksums, block_size, bits = _i32(0), _i32(0), _i64(0)
+        r = self.lib.achip_ctx_get_snappyframed_writer(self.ctx, ctypes.byref(checksums), ctypes.byref(block_size), ctypes.byref(bits))
+        if r < 0:
+            raise_for_status(r)
+        return bool(checksums.value), block_size.value, bits_double(bits.value)
+
+    def set_snappyframed_verify_checksums(self, verify):
+        """SnappyFramedInputStream(decompressor, in, verifyChecksums) for this context's x-snappy-framed decodes"""
+        r = self.lib.achip_ctx_set_snappyframed_verify_checksums(self.ctx, 1 if verify else 0)
+        if r < 0:
+            raise IllegalArgumentException(self.lib.achip_last_error().decode(), r)
+
+    def get_snappyframed_verify_checksums(self):
+        r = int(self.lib.achip_ctx_get_snappyframed_verify_checksums(self.ctx))
+        if r < 0:
+            raise_for_status(r)
+        return bool(r)
 
     def synchronize(self):
         r = self.lib.achip_ctx_synchronize(self.ctx)

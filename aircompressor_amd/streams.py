@@ -5,6 +5,7 @@ holds the stream position and a pending buffer; the library keeps nothing betwee
 """
 from . import native
 from .batch import HipBatchCodec, OP_SNAPPYFRAMED_DECOMPRESS, OP_SNAPPYFRAMED_COMPRESS, OP_LZ4HADOOP_DECOMPRESS, OP_LZ4HADOOP_COMPRESS, OP_SNAPPYHADOOP_DECOMPRESS, OP_SNAPPYHADOOP_COMPRESS
+from .codecs import _check_snappyframed_writer
 from .errors import MalformedInputException
 
 DEFAULT_WINDOW_BYTES = 4 << 20  # what a stream holds of its source / sink at a time, unless a single unit wants more
@@ -13,10 +14,11 @@ DEFAULT_WINDOW_BYTES = 4 << 20  # what a stream holds of its source / sink at a 
 class HipWindowInputStream:
     """read(n) / readall() over a binary source (anything with read(n)); `op` is one of the three container decode ops."""
 
-    def __init__(self, source, op, device=0, native_ctx=None, window_bytes=DEFAULT_WINDOW_BYTES, buffer_size=None):
+    def __init__(self, source, op, device=0, native_ctx=None, window_bytes=DEFAULT_WINDOW_BYTES, buffer_size=None, configure=None):
         self._codec = HipBatchCodec(device, native_ctx)
         self._source, self._op, self._window = source, op, int(window_bytes)
         self._buffer_size = buffer_size
+        self._configure = configure  # called with the context before every window call: the stream object's constructor arguments
         self._pending = b""       # compressed bytes not yet taken: begins at a unit boundary
         self._want = self._window  # how many of them a call wants in hand
         self._room = self._window
@@ -40,6 +42,8 @@ class HipWindowInputStream:
             return False
         if self._buffer_size is not None:
             self._codec.native.set_option("hadoop.buffer_size", self._buffer_size)
+        if self._configure is not None:
+            self._configure(self._codec.native)
         flags = (native.WINDOW_FIRST if self._first else 0) | (native.WINDOW_LAST if self._eof else 0)
         consumed, out, stop, need, status, err = self._codec.window_host(self._op, flags, self._pending, self._room)
         self._plain += out
@@ -89,10 +93,11 @@ class HipWindowInputStream:
 class HipWindowOutputStream:
     """write(b) / finish() / close() onto a binary sink (anything with write(b)); `op` is one of the three container compress ops."""
 
-    def __init__(self, sink, op, device=0, native_ctx=None, window_bytes=DEFAULT_WINDOW_BYTES, buffer_size=None):
+    def __init__(self, sink, op, device=0, native_ctx=None, window_bytes=DEFAULT_WINDOW_BYTES, buffer_size=None, configure=None):
         self._codec = HipBatchCodec(device, native_ctx)
         self._sink, self._op, self._window = sink, op, int(window_bytes)
         self._buffer_size = buffer_size
+        self._configure = configure
         self._pending = b""
         self._room = 2 * self._window + 65536
         self._first, self._finished = True, False
@@ -101,6 +106,8 @@ class HipWindowOutputStream:
         while True:
             if self._buffer_size is not None:
                 self._codec.native.set_option("hadoop.buffer_size", self._buffer_size)
+            if self._configure is not None:
+                self._configure(self._codec.native)
             flags = (native.WINDOW_FIRST if self._first else 0) | (native.WINDOW_LAST if closing else 0)
             consumed, out, stop, need, status, _ = self._codec.window_host(self._op, flags, self._pending, self._room, compress=True)
             if stop == native.STOP_FAILED:
@@ -138,14 +145,25 @@ class HipWindowOutputStream:
 
 
 def _twins(name, decode_op, encode_op, hadoop, doc):
+    framed = decode_op == OP_SNAPPYFRAMED_DECOMPRESS  # the x-snappy-framed twins take their reference classes' constructor arguments
+
     class In(HipWindowInputStream):
         def __init__(self, source, device=0, native_ctx=None, window_bytes=DEFAULT_WINDOW_BYTES, **kw):
-            super().__init__(source, decode_op, device, native_ctx, window_bytes, kw.pop("buffer_size", 262144) if hadoop else None)
+            configure = None
+            if framed:
+                verify = bool(kw.pop("verify_checksums", True))
+                configure = lambda ctx: ctx.set_snappyframed_verify_checksums(verify)  # noqa: E731
+            super().__init__(source, decode_op, device, native_ctx, window_bytes, kw.pop("buffer_size", 262144) if hadoop else None, configure)
             assert not kw, kw
 
     class Out(HipWindowOutputStream):
         def __init__(self, sink, device=0, native_ctx=None, window_bytes=DEFAULT_WINDOW_BYTES, **kw):
-            super().__init__(sink, encode_op, device, native_ctx, window_bytes, kw.pop("buffer_size", 262144) if hadoop else None)
+            configure = None
+            if framed:
+                writer = (bool(kw.pop("write_checksums", True)), int(kw.pop("block_size", 65536)), float(kw.pop("min_compression_ratio", 0.85)))
+                _check_snappyframed_writer(writer[1], writer[2])
+                configure = lambda ctx: ctx.set_snappyframed_writer(*writer)  # noqa: E731
+            super().__init__(sink, encode_op, device, native_ctx, window_bytes, kw.pop("buffer_size", 262144) if hadoop else None, configure)
             assert not kw, kw
 
     In.__name__ = In.__qualname__ = name + "HipInputStream"

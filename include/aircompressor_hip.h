@@ -205,6 +205,39 @@ int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value);
 #define ACHIP_LZ4_MAX_ACCELERATION 65537
 int32_t achip_ctx_set_lz4_acceleration(achip_ctx* ctx, int32_t acceleration);
 int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx);
+/* replaces the arguments of SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio)
+ * M/snappy/SnappyFramedOutputStream.java:77-91 (newChecksumFreeBenchmarkOutputStream :65-69 is writeChecksums = 0 at the defaults) and of
+ * SnappyFramedInputStream(decompressor, in, verifyChecksums)  M/snappy/SnappyFramedInputStream.java:74-79.  Properties of the context, as they are of the
+ * Java stream objects; a mixed batch's helper contexts take a copy of them.  Every type here is one NativeLoader.getMemoryLayout binds, so the ratio
+ * crosses as its IEEE-754 bit pattern (Double.doubleToRawLongBits), never as a double.
+ * The writer cuts its input into blocks of blockSize bytes (:116-141), keeps a chunk compressed where (double) compressed / (double) length <=
+ * minCompressionRatio (:213, the same correctly rounded division on the device) and stores the block raw otherwise, and writes the masked CRC-32C of
+ * the block's plaintext or, without checksums, 0 (:203 -- the CRC is then not computed at all).  The reader with verify = 0 does not look at the CRC
+ * field and runs no CRC pass: ACHIP_D_SNF_CHECKSUM cannot arise; every structure error, its offset, the lengths and the window calls' stop reasons stay
+ * as they are.  At the defaults every byte, status and offset is what it was before these calls existed.
+ * The writer's values apply to every x-snappy-framed encode the context launches: achip_snappyframed_compress_batch, achip_snappyframed_compress,
+ * ACHIP_OP_SNAPPYFRAMED_COMPRESS inside achip_batch_host, achip_mixed_batch, achip_mixed_batch_host and achip_multi_batch_host (each context its own
+ * values), achip_window_compress_batch and achip_window_compress under that op (consumed, need and the worst-case room count in blocks of blockSize:
+ * need = blockSize on a partial block, 8 + blockSize (+ 10) on want of room), and to that op's line of achip_compress_bound_batch -- the bound at the
+ * context's block size, as the Hadoop ops use "hadoop.buffer_size"; the encoders' ACHIP_D_SNF_MAX_OUTPUT check asks for the same bound,
+ * achip_snappyframed_max_compressed_length_for(n, blockSize).  verify applies to every x-snappy-framed decode: the one-shot calls, host and mixed
+ * batches, achip_window_decompress_batch and achip_window_decompress.
+ * They do NOT change: raw Snappy, the Hadoop Snappy streams, achip_decoded_size_batch (checksums are not its business), any other codec, or
+ * achip_snappyframed_max_compressed_length (the bound at 65536).
+ * set_writer: 0, or a status of class INVALID_ARGUMENT with detail ACHIP_D_BAD_ARGUMENT -- the context keeps all of its values.  Checked before the
+ * context is looked at, in the constructor's order: the ratio must be > 0 and <= 1.0 (NaN is refused), achip_last_error "minCompressionRatio <value>
+ * must be between (0,1.0]." (:83); then blockSize, "blockSize must be in (0, 65536]" (:90); then both flags must be 0 or 1.
+ * get_writer: 0 with the values stored through the non-null pointers, or a status for a null context.  get_verify: 0 / 1, or a status.
+ * achip_snappyframed_max_compressed_length_for: 10 + 8 * ceil(n / blockSize) + n in 64-bit arithmetic; a negative status for n < 0, a block size outside
+ * (0, 65536] or a result above INT32_MAX (n = 2^30 at blockSize 1). */
+#define ACHIP_SNF_DEFAULT_BLOCK_SIZE 65536
+#define ACHIP_SNF_MAX_BLOCK_SIZE     65536
+#define ACHIP_SNF_DEFAULT_MIN_RATIO_BITS 0x3FEB333333333333LL   /* 0.85 */
+int32_t achip_ctx_set_snappyframed_writer(achip_ctx* ctx, int32_t writeChecksums, int32_t blockSize, int64_t minCompressionRatioBits);
+int32_t achip_ctx_get_snappyframed_writer(achip_ctx* ctx, int32_t* writeChecksums, int32_t* blockSize, int64_t* minCompressionRatioBits);
+int32_t achip_ctx_set_snappyframed_verify_checksums(achip_ctx* ctx, int32_t verify);
+int32_t achip_ctx_get_snappyframed_verify_checksums(achip_ctx* ctx);
+int32_t achip_snappyframed_max_compressed_length_for(int32_t uncompressedSize, int32_t blockSize);
 /* diagnostics of the LAST batched call on this context (synchronizes the stream); -1 = unknown name / nothing recorded.
  * "zstd.decompress.fallback_items": items the five-stage pipeline handed to the one-kernel decoder;
  * "zstd.decompress.fallback_stage1" .. "stage6": the same, by the stage that handed them over (6: the multi-block stages' walk);
@@ -570,12 +603,14 @@ int32_t achip_zstdstream_compress_end(achip_ctx* ctx, void* state);
  *   FAILED      status != 0: status, its detail and errOffset - consumed are what the one-shot reader reports for W[consumed:] with room dstCap - outLen; under LAST an
  *               incomplete tail is among them (the one-shot reader's truncation errors).  Everything in front of the damage has been delivered: consumed and outLen
  *               describe it (the feed contract of achip_zstdstream_decompress_feed).  x-snappy-framed checksums are verified as in the one-shot reader.
- * ENCODE: consumed = the largest multiple of the writer's block size (x-snappy-framed: 64 KiB; Hadoop: bufferSize minus the codec's overhead, as the one-shot
+ * ENCODE: consumed = the largest multiple of the writer's block size (x-snappy-framed: the context's blockSize, 64 KiB unless set; Hadoop: bufferSize minus the codec's overhead, as the one-shot
  * writer cuts) that the window holds and whose worst-case output fits dstCap; with LAST the partial tail block too.  The bytes written are the one-shot writer's for
  * W[:consumed] -- the x-snappy-framed stream identifier only under FIRST, which a caller sets until the stream's first byte is out -- so the windows' outputs, one
  * behind the other, are the one-shot writer's stream however the stream was cut.  NEED_INPUT: a partial block is left (need = the block size); NEED_ROOM: a block is
  * left for want of room (need = its worst case: the codec's bound and the two Hadoop length words, or the chunk's 8 bytes of header and CRC and the block; plus the
- * stream identifier's 10 bytes where not even they fit); FAILED only for argument faults (a negative length: INVALID_ARGUMENT). */
+ * stream identifier's 10 bytes where not even they fit); need == 0: the window has taken its share of the call's block list (2^20 entries for all its windows together:
+ * 2^20 / nBlocks blocks a window, at least one -- reached with small x-snappy-framed blocks, e.g. one window of more than 1 MiB at blockSize 1) -- call again with what
+ * is left.  FAILED only for argument faults (a negative length: INVALID_ARGUMENT; more than 2^20 windows in one call: INVALID_ARGUMENT / ACHIP_D_UNSUPPORTED). */
 #define ACHIP_WINDOW_FIRST 1   /* the window starts the stream (x-snappy-framed: the stream identifier is required / written) */
 #define ACHIP_WINDOW_LAST  2   /* the stream ends with this window */
 #define ACHIP_STOP_END        0  /* the whole window was taken */

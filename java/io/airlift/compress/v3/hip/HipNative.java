@@ -49,6 +49,9 @@ public final class HipNative
     public static final int DETAIL_LZ4_EMPTY_OUTPUT = 7;
     public static final int LZ4_DEFAULT_ACCELERATION = 1;  // ACHIP_LZ4_DEFAULT_ACCELERATION
     public static final int LZ4_MAX_ACCELERATION = 65537;  // ACHIP_LZ4_MAX_ACCELERATION
+    public static final int SNF_DEFAULT_BLOCK_SIZE = 65536;  // ACHIP_SNF_DEFAULT_BLOCK_SIZE
+    public static final int SNF_MAX_BLOCK_SIZE = 65536;      // ACHIP_SNF_MAX_BLOCK_SIZE
+    public static final double SNF_DEFAULT_MIN_COMPRESSION_RATIO = 0.85;  // Double.longBitsToDouble(ACHIP_SNF_DEFAULT_MIN_RATIO_BITS)
 
     public static final int OP_LZ4_DECOMPRESS = 0;
     public static final int OP_LZ4_COMPRESS = 1;
@@ -135,6 +138,8 @@ public final class HipNative
             MethodHandle lz4FrameMaxCompressedLength,
             @NativeSignature(name = "achip_snappyframed_max_compressed_length", returnType = int.class, argumentTypes = int.class)
             MethodHandle snappyFramedMaxCompressedLength,
+            @NativeSignature(name = "achip_snappyframed_max_compressed_length_for", returnType = int.class, argumentTypes = {int.class, int.class})
+            MethodHandle snappyFramedMaxCompressedLengthFor,
             // Hadoop block streams (SURVEY 8f row 2, second half)
             @NativeSignature(name = "achip_lz4hadoop_compress", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class})
             MethodHandle lz4HadoopCompress,
@@ -291,6 +296,14 @@ public final class HipNative
             MethodHandle ctxSetLz4Acceleration,
             @NativeSignature(name = "achip_ctx_get_lz4_acceleration", returnType = int.class, argumentTypes = MemorySegment.class)
             MethodHandle ctxGetLz4Acceleration,
+            @NativeSignature(name = "achip_ctx_set_snappyframed_writer", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, long.class})
+            MethodHandle ctxSetSnappyFramedWriter,
+            @NativeSignature(name = "achip_ctx_get_snappyframed_writer", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle ctxGetSnappyFramedWriter,
+            @NativeSignature(name = "achip_ctx_set_snappyframed_verify_checksums", returnType = int.class, argumentTypes = {MemorySegment.class, int.class})
+            MethodHandle ctxSetSnappyFramedVerifyChecksums,
+            @NativeSignature(name = "achip_ctx_get_snappyframed_verify_checksums", returnType = int.class, argumentTypes = MemorySegment.class)
+            MethodHandle ctxGetSnappyFramedVerifyChecksums,
             @NativeSignature(name = "achip_memset_d", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, int.class, long.class})
             MethodHandle memsetDevice,
             @NativeSignature(name = "achip_event_create", returnType = MemorySegment.class, argumentTypes = {})
@@ -615,6 +628,27 @@ public final class HipNative
     {
         try {
             int result = (int) HANDLES.snappyFramedMaxCompressedLength().invokeExact(n);
+            if (result < 0) {
+                throw new IllegalArgumentException(n < 0 ? "uncompressedSize is negative: " + n : "Maximum compressed length exceeds Integer.MAX_VALUE for uncompressedSize: " + n);
+            }
+            return result;
+        }
+        catch (RuntimeException e) {
+            throw e;
+        }
+        catch (Throwable e) {
+            throw new AssertionError("should not reach here", e);
+        }
+    }
+
+    /** the same for a writer built with another block size (achip_snappyframed_max_compressed_length_for) */
+    public static int snappyFramedMaxCompressedLength(int n, int blockSize)
+    {
+        if (blockSize <= 0 || blockSize > SNF_MAX_BLOCK_SIZE) {
+            throw new IllegalArgumentException("blockSize must be in (0, 65536]");
+        }
+        try {
+            int result = (int) HANDLES.snappyFramedMaxCompressedLengthFor().invokeExact(n, blockSize);
             if (result < 0) {
                 throw new IllegalArgumentException(n < 0 ? "uncompressedSize is negative: " + n : "Maximum compressed length exceeds Integer.MAX_VALUE for uncompressedSize: " + n);
             }
@@ -1029,6 +1063,87 @@ public final class HipNative
             }
             throwIfError(result, 0);
             return result;
+        }
+
+        /**
+         * achip_ctx_set_snappyframed_writer: the arguments of SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio) for this
+         * context's x-snappy-framed encodes.  The checks, their order and their texts are the constructor's; the ratio crosses as its bit pattern.
+         */
+        public void setSnappyFramedWriter(boolean writeChecksums, int blockSize, double minCompressionRatio)
+        {
+            if (!(minCompressionRatio > 0 && minCompressionRatio <= 1.0)) {
+                throw new IllegalArgumentException("minCompressionRatio " + minCompressionRatio + " must be between (0,1.0].");
+            }
+            if (blockSize <= 0 || blockSize > SNF_MAX_BLOCK_SIZE) {
+                throw new IllegalArgumentException("blockSize must be in (0, 65536]");
+            }
+            int result;
+            try {
+                result = (int) HANDLES.ctxSetSnappyFramedWriter().invokeExact(handle(), writeChecksums ? 1 : 0, blockSize, Double.doubleToRawLongBits(minCompressionRatio));
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /** what achip_ctx_get_snappyframed_writer reports */
+        public record SnappyFramedWriter(boolean writeChecksums, int blockSize, double minCompressionRatio) {}
+
+        /** achip_ctx_get_snappyframed_writer */
+        public SnappyFramedWriter getSnappyFramedWriter()
+        {
+            try (Arena arena = Arena.ofConfined()) {
+                MemorySegment checksums = arena.allocate(java.lang.foreign.ValueLayout.JAVA_INT);
+                MemorySegment blockSize = arena.allocate(java.lang.foreign.ValueLayout.JAVA_INT);
+                MemorySegment ratioBits = arena.allocate(JAVA_LONG);
+                int result = (int) HANDLES.ctxGetSnappyFramedWriter().invokeExact(handle(), checksums, blockSize, ratioBits);
+                throwIfError(result, 0);
+                return new SnappyFramedWriter(checksums.get(java.lang.foreign.ValueLayout.JAVA_INT, 0) != 0, blockSize.get(java.lang.foreign.ValueLayout.JAVA_INT, 0),
+                        Double.longBitsToDouble(ratioBits.get(JAVA_LONG, 0)));
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+        }
+
+        /** achip_ctx_set_snappyframed_verify_checksums: the third argument of SnappyFramedInputStream(decompressor, in, verifyChecksums) for this context's x-snappy-framed decodes */
+        public void setSnappyFramedVerifyChecksums(boolean verifyChecksums)
+        {
+            int result;
+            try {
+                result = (int) HANDLES.ctxSetSnappyFramedVerifyChecksums().invokeExact(handle(), verifyChecksums ? 1 : 0);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /** achip_ctx_get_snappyframed_verify_checksums */
+        public boolean getSnappyFramedVerifyChecksums()
+        {
+            int result;
+            try {
+                result = (int) HANDLES.ctxGetSnappyFramedVerifyChecksums().invokeExact(handle());
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+            return result != 0;
         }
 
         /** Single block through host memory: returns bytes written or throws the Java codec's exception. */

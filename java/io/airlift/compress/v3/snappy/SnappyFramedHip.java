@@ -32,7 +32,11 @@ import static java.util.Objects.requireNonNull;
  * does not reach 0.85 -- raw); {@link #decompress(byte[], int)} returns what reading a {@link SnappyFramedInputStream} (checksums verified) to its
  * end returns, and fails where it fails: the stream-level errors come back as {@link IOException} with the stream class's message, a corrupt
  * chunk body as the block codec's {@code MalformedInputException}.
- * Bindings: {@code achip_snappyframed_compress}, {@code achip_snappyframed_decompress}, {@code achip_snappyframed_max_compressed_length}
+ * The five-argument constructor takes what {@code SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio)} and
+ * {@code SnappyFramedInputStream(decompressor, in, verifyChecksums)} take, checked as the stream classes check them;
+ * {@link #newChecksumFreeBenchmarkCodec(int)} is {@code SnappyFramedOutputStream.newChecksumFreeBenchmarkOutputStream}: no CRC is computed, the fields are 0.
+ * Bindings: {@code achip_snappyframed_compress}, {@code achip_snappyframed_decompress}, {@code achip_snappyframed_max_compressed_length},
+ * {@code achip_snappyframed_max_compressed_length_for}, {@code achip_ctx_set_snappyframed_writer}, {@code achip_ctx_set_snappyframed_verify_checksums}
  * (include/aircompressor_hip.h).  For many streams per call use {@link io.airlift.compress.v3.hip.HipBatchCodec} with
  * {@code OP_SNAPPYFRAMED_COMPRESS} / {@code OP_SNAPPYFRAMED_DECOMPRESS}.
  * <p>
@@ -50,6 +54,7 @@ public final class SnappyFramedHip
     }
 
     private final HipNative.Context context;
+    private final int blockSize;
 
     public SnappyFramedHip()
     {
@@ -58,8 +63,29 @@ public final class SnappyFramedHip
 
     public SnappyFramedHip(int device)
     {
+        this(device, true, HipNative.SNF_DEFAULT_BLOCK_SIZE, HipNative.SNF_DEFAULT_MIN_COMPRESSION_RATIO, true);
+    }
+
+    /** the writer's writeChecksums, blockSize and minCompressionRatio and the reader's verifyChecksums, as the stream classes' constructors take them */
+    public SnappyFramedHip(int device, boolean writeChecksums, int blockSize, double minCompressionRatio, boolean verifyChecksums)
+    {
+        if (!(minCompressionRatio > 0 && minCompressionRatio <= 1.0)) {
+            throw new IllegalArgumentException("minCompressionRatio " + minCompressionRatio + " must be between (0,1.0].");
+        }
+        if (blockSize <= 0 || blockSize > HipNative.SNF_MAX_BLOCK_SIZE) {
+            throw new IllegalArgumentException("blockSize must be in (0, 65536]");
+        }
         HipNative.verifyEnabled();
         this.context = new HipNative.Context(device);
+        this.blockSize = blockSize;
+        context.setSnappyFramedWriter(writeChecksums, blockSize, minCompressionRatio);
+        context.setSnappyFramedVerifyChecksums(verifyChecksums);
+    }
+
+    /** SnappyFramedOutputStream.newChecksumFreeBenchmarkOutputStream: the default writer without checksums (the reader of this codec does not verify them either) */
+    public static SnappyFramedHip newChecksumFreeBenchmarkCodec(int device)
+    {
+        return new SnappyFramedHip(device, false, HipNative.SNF_DEFAULT_BLOCK_SIZE, HipNative.SNF_DEFAULT_MIN_COMPRESSION_RATIO, false);
     }
 
     public static boolean isEnabled()
@@ -72,10 +98,15 @@ public final class SnappyFramedHip
         return HipNative.snappyFramedMaxCompressedLength(uncompressedSize);
     }
 
+    public static int maxCompressedLength(int uncompressedSize, int blockSize)
+    {
+        return HipNative.snappyFramedMaxCompressedLength(uncompressedSize, blockSize);
+    }
+
     public byte[] compress(byte[] data)
     {
         requireNonNull(data, "data is null");
-        byte[] output = new byte[maxCompressedLength(data.length)];
+        byte[] output = new byte[maxCompressedLength(data.length, blockSize)];
         int written = context.singleBlock(HipNative.OP_SNAPPYFRAMED_COMPRESS, MemorySegment.ofArray(data), data.length, MemorySegment.ofArray(output), output.length);
         return Arrays.copyOf(output, written);
     }

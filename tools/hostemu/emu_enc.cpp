@@ -49,7 +49,7 @@ extern "C" int emu_encode(int op, const uint8_t* srcBase, const int64_t* srcOff,
     if (op == 9) {
         static GuardedScratch guarded;
         guarded.assign(achip::snappyframed_compress_scratch_bytes(n));
-        return guarded.check("the x-snappy-framed writer", achip::launch_snappyframed_compress(a, nullptr, guarded.v.data(), option));
+        return guarded.check("the x-snappy-framed writer", achip::launch_snappyframed_compress(a, nullptr, guarded.v.data(), option, achip::KernelSettings()));
     }
     if (op == 11 || op == 13) {
         static GuardedScratch guarded;

@@ -8,7 +8,7 @@ extern "C" { long long achip_emu_counters[16]; }
 extern "C" long long emu_pack_tile_bytes() { return achip::PACK_TILE_BYTES; }
 extern "C" int emu_compress_bound(int32_t op, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t n, int32_t hadoopBufferSize)
 {
-    return (int)achip::launch_compress_bound(op, srcLen, outSize, status, n, hadoopBufferSize, nullptr);
+    return (int)achip::launch_compress_bound(op, srcLen, outSize, status, n, hadoopBufferSize, nullptr, achip::KernelSettings().snfBlockSize);
 }
 extern "C" int emu_pack_outputs(const uint8_t* srcBase, const int64_t* srcOff, const int32_t* outLen, const int32_t* status, const uint8_t* rawBase, const int64_t* rawOff,
                                 const int32_t* rawLen, int32_t n, int32_t align, uint8_t* packedBase, int64_t packedCap, int64_t* packedOff, int32_t* packedLen, int32_t* stored,

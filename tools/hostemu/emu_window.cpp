@@ -28,7 +28,7 @@ extern "C" int emu_window(int op, int bufferSize, int variant, const int32_t* fl
             break;
         case ACHIP_OP_SNAPPYFRAMED_COMPRESS:
             scratch.assign(achip::snappyframed_window_compress_scratch_bytes(n));
-            r = achip::launch_snappyframed_window_compress(a, w, nullptr, scratch.v.data());
+            r = achip::launch_snappyframed_window_compress(a, w, nullptr, scratch.v.data(), achip::KernelSettings());
             break;
         case ACHIP_OP_LZ4HADOOP_COMPRESS:
         case ACHIP_OP_SNAPPYHADOOP_COMPRESS:
