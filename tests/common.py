@@ -1,11 +1,38 @@
 """Shared test inputs: the reference harness' hand cases, the committed corpus sample, synthetic blocks."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
+HOSTEMU = os.path.join(os.path.dirname(HERE), "tools", "hostemu")
+
+
+def emulib():
+    """tools/hostemu/emulib.py (the table of emulator libraries) as a module; the test is skipped where there is no compiler for it"""
+    import pytest
+    if HOSTEMU not in sys.path:
+        sys.path.insert(0, HOSTEMU)
+    import emulib
+    if emulib.compiler() is None:
+        pytest.skip("no clang++ for the host build of the kernel source")
+    return emulib
+
+
+def emulator_checks(targets, jobs, merge=True):
+    """Rebuilds the emulator libraries `targets` -- always: a test never trusts a library that was lying around -- and runs the scripts of tools/hostemu
+    jobs = {name: (script, *args)} side by side (separate processes; the libraries are read-only).  -> {name: CompletedProcess}, stderr in stdout unless merge is False"""
+    emulib().build(*targets)
+    started = {name: subprocess.Popen([sys.executable, os.path.join(HOSTEMU, script), *args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT if merge else subprocess.PIPE,
+                                      text=True, cwd=os.path.dirname(HERE)) for name, (script, *args) in jobs.items()}
+    done = {}
+    for name, job in started.items():
+        out, err = job.communicate()
+        done[name] = subprocess.CompletedProcess(job.args, job.returncode, out, err)
+    return done
 
 # T/AbstractTestCompression.java:47-56
 HAND_CASES = [

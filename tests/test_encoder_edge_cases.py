@@ -3,13 +3,13 @@ every case reaches the edge it is named for (the oracle's stream of it, parsed, 
 window encoders take every one of their paths (a counting build of the kernel source on the emulator) and write the oracle's bytes."""
 import json
 import os
-import shutil
 import subprocess
 import sys
 
 import pytest
 
 from tests import encoder_edge_cases as ec
+from tests import common
 from tests import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,16 +75,10 @@ VARIANTS = [("lz4", 4), ("lz4", 4 | 16), ("lz4", 4 | 48), ("snappy", 4)]
 def test_every_encoder_path_is_reached():
     """2b: the catalog entries the emulator takes (all but 64 KiB and more of mixed data) through the window encoders (variant 4; LZ4 also as a wavefront per block and with two memory-tier wavefronts)
     built with -DACHIP_HOST_STATS: the oracle's bytes for every entry, and every counter raised by some entry -- LZ4's 20 .. 26 without exception."""
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    sys.path.insert(0, os.path.join(ROOT, "tools", "hostemu"))
+    jobs = common.emulator_checks(["enc_stats"], {v: ("enc_paths.py", v[0], "catalog", "--json", "--option", str(v[1])) for v in VARIANTS}, merge=False)  # (side by side)
     import enc_paths
-    enc_paths.build(clang)
-    jobs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "hostemu", "enc_paths.py"), codec, "catalog", "--json", "--option", str(option)], stdout=subprocess.PIPE,
-                             stderr=subprocess.PIPE, text=True, cwd=ROOT) for codec, option in VARIANTS]  # (side by side)
-    for (codec, option), job in zip(VARIANTS, jobs):
-        out, err = job.communicate()
+    for (codec, option), job in jobs.items():
+        out, err = job.stdout, job.stderr
         assert job.returncode == 0, err
         results = json.loads(out.strip().splitlines()[-1])
         assert len(results) == len(ec.emulator_cases(codec)) > 200

@@ -4,6 +4,8 @@ import os
 import subprocess
 import tempfile
 
+from tests import common
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CHECK = r"""
@@ -78,11 +80,7 @@ def test_decoder_choice_rule_on_the_cpu():
     """achip_device.h lz4_pick -- what auto mode's probes amount to -- compiled for the host (tools/hostemu's shim) and asked directly: the pooled
     bytes-per-sequence rule where no per-block count exists (the stream readers), the per-block rule where it does (round 4: a third of the sampled
     blocks short => two passes, whatever the pooled mean says), mixed groups, and "no record scratch => rings"."""
-    import shutil
-    import pytest
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
+    emulib = common.emulib()
     prog = r"""
 #include "hip/hip_runtime.h"
 #include "achip_device.h"
@@ -109,8 +107,7 @@ int main()
     with tempfile.TemporaryDirectory() as tmp:
         cfile, exe = os.path.join(tmp, "t.cpp"), os.path.join(tmp, "t")
         open(cfile, "w").write(prog)
-        subprocess.run([clang, "-O1", "-std=c++17", "-I", os.path.join(ROOT, "tools", "hostemu"), "-I", os.path.join(ROOT, "include"),
-                        "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"), "-o", exe, cfile], check=True)
+        subprocess.run(emulib.program_command(cfile, exe), check=True)
         got = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
     assert got == [3, 0, 3, 0, 0, 0, 3, 0, 3, 0], got
 
@@ -123,46 +120,35 @@ def test_lane_private_decoder_kernels_on_the_cpu():
     fall back) -- plaintext, status, error offset and guard bands against the oracle, on the cases of the GPU parity suite, without a GPU.  And
     every ring instantiation the product launches (16 and 64 lanes per block and the latency class among them) on the catalog of constructed
     streams built for its own ring sizes (check_v3.py --part edges)."""
-    import shutil
-    import sys
-    import pytest
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    emu_dir = os.path.join(ROOT, "tools", "hostemu")
-    subprocess.run([clang, "-O1", "-std=c++17", "-fPIC", "-shared", "-I", emu_dir, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"),
-                    "-o", os.path.join(emu_dir, "libemu.so"), os.path.join(emu_dir, "emu.cpp")], check=True)
     # the checks run side by side (separate processes; the library is read-only): check_v3.py in three parts by decoder family
-    def start(script, *args):
-        return subprocess.Popen([sys.executable, os.path.join(emu_dir, script), *args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
     jobs = {
-        "rings-1-lane": start("check_v3.py", "--quick", "--ops", "16,17,12,13"),
-        "two-pass-lz4": start("check_v3.py", "--quick", "--ops", "24,25,26,27"),  # (26 / 27, 36 / 37: parsed by a wavefront per block)
-        "two-pass-snappy": start("check_v3.py", "--quick", "--ops", "34,35,36,37"),
-        "rings-4-lanes": start("check_v3.py", "--quick", "--ops", "44,54"),
+        "rings-1-lane": ("check_v3.py", "--quick", "--ops", "16,17,12,13"),
+        "two-pass-lz4": ("check_v3.py", "--quick", "--ops", "24,25,26,27"),  # (26 / 27, 36 / 37: parsed by a wavefront per block)
+        "two-pass-snappy": ("check_v3.py", "--quick", "--ops", "34,35,36,37"),
+        "rings-4-lanes": ("check_v3.py", "--quick", "--ops", "44,54"),
         # the executor for records of any length (the Zstd pipeline's execute stage): LZ4 blocks re-expressed as Zstd-style records + one
         # literal buffer, executed and compared with the plaintext; records that run outside their buffers must be refused
-        "records": start("check_records.py"),
+        "records": ("check_records.py",),
         # the Hadoop block-stream reader's variant 2 (walk, chunks through the two-pass decoders with an arena sized after the chunk count is
         # read back, fold): LZ4 and Snappy streams at three buffer sizes against the plaintext
-        "hadoop": start("check_hadoop.py"),
+        "hadoop": ("check_hadoop.py",),
         # the LZ4 frame reader's variant 1 (walk, the frames' blocks as one batch through the two-pass decoder, fold with stored blocks,
         # content size and content checksum): the Java writer's frames and hand-built ones of 64 / 256 KiB blocks against the plaintext
-        "lz4frame": start("check_lz4frame.py"),
+        "lz4frame": ("check_lz4frame.py",),
         # the x-snappy-framed reader's variant 2 (walk, chunks through the two-pass Snappy decoder, CRC-32C verification, fold)
-        "snappyframed": start("check_snappyframed.py"),
+        "snappyframed": ("check_snappyframed.py",),
         # the catalog of constructed streams (tests/decoder_edge_cases.py: one edge of one ring instantiation per stream, valid and malformed) through every
         # ring instantiation of the launch tables -- 1 .. 64 lanes per block, both ring classes, the latency class: the non-unified copy paths of 8 lanes and
         # more run on the CPU here and nowhere else -- and through the two-pass decoders, at four (source, destination) misalignments: a line per op and pair
-        "edges-rings": start("check_v3.py", "--part", "edges", "--ops", "16,17,12,13,44,54,46,56,49,59"),
-        "edges-two-pass": start("check_v3.py", "--part", "edges", "--ops", "24,25,26,27,34,35,36,37"),
-        "edges-64-lanes": start("check_v3.py", "--part", "edges", "--ops", "48,58,2641,3641"),
-        "edges-other-widths": start("check_v3.py", "--part", "edges", "--ops", "2020,2021,2041,2042,2080,2081,2161,2320,2321,3020,3021,3041,3042,3080,3081,3161,3320,3321"),
+        "edges-rings": ("check_v3.py", "--part", "edges", "--ops", "16,17,12,13,44,54,46,56,49,59"),
+        "edges-two-pass": ("check_v3.py", "--part", "edges", "--ops", "24,25,26,27,34,35,36,37"),
+        "edges-64-lanes": ("check_v3.py", "--part", "edges", "--ops", "48,58,2641,3641"),
+        "edges-other-widths": ("check_v3.py", "--part", "edges", "--ops", "2020,2021,2041,2042,2080,2081,2161,2320,2321,3020,3021,3041,3042,3080,3081,3161,3320,3321"),
     }
     expected = {"rings-1-lane": 4, "two-pass-lz4": 4, "two-pass-snappy": 4, "rings-4-lanes": 2, "records": 1, "hadoop": 6, "lz4frame": 2, "snappyframed": 1,
                 "edges-rings": 40, "edges-two-pass": 32, "edges-64-lanes": 16, "edges-other-widths": 72}
-    for name, job in jobs.items():
-        out = job.communicate()[0]
+    for name, job in common.emulator_checks(["emu"], jobs).items():
+        out = job.stdout
         assert job.returncode == 0, (name, out)
         lines = [l for l in out.splitlines() if "mismatches" in l]
         assert len(lines) == expected[name] and all(l.endswith(" 0 mismatches") for l in lines), (name, out)
@@ -175,18 +161,8 @@ def test_zstd_pipeline_kernels_on_the_cpu():
     multi-block frames must either leave the fast path or decode to exactly what the oracle's decoder returns.  The case catalog of
     tests/zstd_frame_cases.py (hand-built frames at the execute stage's edges, valid and malformed, and encoders' frames) runs under BOTH execute
     stages: the ring executor (exec mode 0, with and without its staging area for far matches) and the record executor (mode 1)."""
-    import shutil
-    import sys
-    import pytest
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    emu_dir = os.path.join(ROOT, "tools", "hostemu")
-    subprocess.run([clang, "-O1", "-std=c++17", "-fPIC", "-shared", "-I", emu_dir, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"),
-                    "-o", os.path.join(emu_dir, "libemu_zstd.so"), os.path.join(emu_dir, "emu_zstd.cpp")], check=True)
-    jobs = [subprocess.Popen([sys.executable, os.path.join(emu_dir, "check_zstd.py"), "--quick", "--part", part], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
-            for part in ("single", "multi", "damaged", "catalog")]  # (side by side)
-    outs = [j.communicate()[0] for j in jobs]
+    jobs = list(common.emulator_checks(["zstd"], {part: ("check_zstd.py", "--quick", "--part", part) for part in ("single", "multi", "damaged", "catalog")}).values())  # (side by side)
+    outs = [j.stdout for j in jobs]
     assert all(j.returncode == 0 for j in jobs), "\n".join(outs)
     out = "\n".join(outs)
     lines = [l for l in out.splitlines() if "mismatches" in l]
@@ -202,16 +178,7 @@ def test_wavefront_per_item_kernels_on_the_cpu():
     (tools/hostemu/emu_harness.py): the reference's LZ4 frame vectors, every branch of the Hadoop readers, the framed format's error cases,
     the Zstd fixtures and corruptions -- output, status and error offset as the oracle has them.  (tools/hostemu/check_serial.py without
     --quick runs the long tests too: liblz4 / libzstd frames, random corruption of every container.)"""
-    import shutil
-    import sys
-    import pytest
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    emu_dir = os.path.join(ROOT, "tools", "hostemu")
-    subprocess.run([clang, "-O1", "-std=c++17", "-fPIC", "-shared", "-I", emu_dir, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"),
-                    "-o", os.path.join(emu_dir, "libemu_serial.so"), os.path.join(emu_dir, "emu_serial.cpp")], check=True)
-    r = subprocess.run([sys.executable, os.path.join(emu_dir, "check_serial.py"), "--quick"], capture_output=True, text=True, cwd=ROOT)
+    r = common.emulator_checks(["serial"], {"serial": ("check_serial.py", "--quick")}, merge=False)["serial"]
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and r.stdout.strip().endswith("8 tests passed, 0 mismatches"), r.stdout
 
@@ -222,16 +189,7 @@ def test_whole_decode_paths_on_the_cpu():
     that the product's own launch functions -- launch_hadoop_decompress, launch_lz4frame_decompress, launch_snappyframed_decompress,
     launch_zstd_decompress with every reader variant, the experimental ones included -- run start to end on the CPU, driven by the GPU
     parity tests themselves.  (tools/hostemu/check_serial.py --all without --quick runs the long tests too.)"""
-    import shutil
-    import sys
-    import pytest
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    emu_dir = os.path.join(ROOT, "tools", "hostemu")
-    subprocess.run([clang, "-O1", "-std=c++17", "-fPIC", "-shared", "-I", emu_dir, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"),
-                    "-o", os.path.join(emu_dir, "libemu_all.so"), os.path.join(emu_dir, "emu_all.cpp")], check=True)
-    r = subprocess.run([sys.executable, os.path.join(emu_dir, "check_serial.py"), "--all", "--quick"], capture_output=True, text=True, cwd=ROOT)
+    r = common.emulator_checks(["all"], {"all": ("check_serial.py", "--all", "--quick")}, merge=False)["all"]
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and r.stdout.strip().endswith("23 tests passed, 0 mismatches"), r.stdout
 
@@ -243,19 +201,9 @@ def test_encoders_and_writers_on_the_cpu():
     updated in place needs): bytes, lengths and statuses (capacities below the bound included) against the oracle's restatement of the Java
     encoders.  (tools/hostemu/check_enc.py without --quick: blocks beyond 64 / 128 / 256 KiB, every Zstd variant, the Hadoop buffer sizes;
     --chunked N: a ZstdOutputStream of N >= 4 MiB bytes through the chunked writer.)"""
-    import shutil
-    import sys
-    import pytest
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    emu_dir = os.path.join(ROOT, "tools", "hostemu")
-    subprocess.run([clang, "-O2", "-std=c++17", "-fPIC", "-shared", "-fno-omit-frame-pointer", "-fsanitize-coverage=inline-8bit-counters,trace-loads,trace-stores", "-I", emu_dir,
-                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"),
-                    "-o", os.path.join(emu_dir, "libemu_enc.so"), os.path.join(emu_dir, "emu_enc.cpp")], check=True)
-    jobs = [subprocess.Popen([sys.executable, os.path.join(emu_dir, "check_enc.py"), "--quick", "--part", part], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
-            for part in ("block", "zstd", "stream", "containers", "snappyfan", "edges", "zedges")]  # (side by side; edges / zedges: the catalogs of tests/encoder_edge_cases.py / zstd_encoder_cases.py)
-    outs = [j.communicate()[0] for j in jobs]
+    parts = ("block", "zstd", "stream", "containers", "snappyfan", "edges", "zedges")  # (side by side; edges / zedges: the catalogs of tests/encoder_edge_cases.py / zstd_encoder_cases.py)
+    jobs = list(common.emulator_checks(["enc"], {part: ("check_enc.py", "--quick", "--part", part) for part in parts}).values())
+    outs = [j.stdout for j in jobs]
     assert all(j.returncode == 0 for j in jobs), "\n".join(outs)
     assert all(o.strip().endswith("encoders under the emulator: 0 mismatches") for o in outs) and "MISMATCH" not in "".join(outs), "\n".join(outs)
 

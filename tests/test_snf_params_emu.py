@@ -5,29 +5,13 @@ off -- on the CPU under the fiber emulator, bytes, statuses and offsets against 
 What --quick leaves to the GPU test (tests/test_gpu_snf_params.py runs the whole catalog): the block encoder costs an order point per memory access here, so block
 sizes 1, 2, 63 and 64 run whole at ratios 0.85 and 0.5 (1.0 and the smallest double once each), 4096 with inputs of up to a block and a byte and the several-block
 run at two parameter sets, and 65535 / 65536 not at all; without --quick the script runs the whole catalog (hours)."""
-import os
 import re
-import shutil
-import subprocess
-import sys
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import common
 
 
 def test_snappyframed_parameters_on_the_emulator():
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    emu_dir = os.path.join(ROOT, "tools", "hostemu")
-    include = ["-I", emu_dir, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "aircompressor_amd", "csrc")]
-    source = os.path.join(emu_dir, "emu_snf_params.cpp")
-    builds = [subprocess.Popen([clang, "-O2", "-std=c++17", "-fPIC", "-shared", "-fno-omit-frame-pointer", "-fsanitize-coverage=inline-8bit-counters,trace-loads,trace-stores",
-                                "-DSNF_PARAMS_WRITERS"] + include + ["-o", os.path.join(emu_dir, "libemu_snf_params_w.so"), source]),
-              subprocess.Popen([clang, "-O1", "-std=c++17", "-fPIC", "-shared"] + include + ["-o", os.path.join(emu_dir, "libemu_snf_params_r.so"), source])]
-    assert [b.wait() for b in builds] == [0, 0]
-    r = subprocess.run([sys.executable, os.path.join(emu_dir, "check_snf_params.py"), "--quick"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
+    r = common.emulator_checks(["snf_params"], {"snf_params": ("check_snf_params.py", "--quick")})["snf_params"]  # (the writers' and the readers' library, built side by side)
     print(r.stdout)
     assert r.returncode == 0, r.stdout
     m = re.search(r"snf parameters emulator: (\d+) items, 0 wrong", r.stdout)

@@ -5,12 +5,12 @@ kernel source on the emulator, every variant) and writes the oracle's bytes."""
 import hashlib
 import json
 import os
-import shutil
 import subprocess
 import sys
 
 import pytest
 
+from tests import common
 from tests import oracle_lib
 from tests import zstd_encoder_cases as ze
 from tests import zstd_frame_cases as zc
@@ -146,18 +146,12 @@ def test_every_encoder_path_is_reached():
     """emulator_cases(v) through the four variants of a -DACHIP_HOST_STATS build, side by side: the oracle's bytes for every entry, and every counter raised by
     some entry under the default variant -- the match finder's under the variant they belong to, the others under every variant but for the two that only
     the cases of thousands of sequences raise (left out under variants 0 and 2)."""
-    clang = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(clang):
-        pytest.skip("no clang++ for the host build of the kernel source")
-    sys.path.insert(0, os.path.join(ROOT, "tools", "hostemu"))
+    jobs = common.emulator_checks(["enc_stats"], {v: ("enc_paths.py", "zstd", "catalog", "--json", "--option", str(v)) for v in VARIANTS}, merge=False)  # (side by side)
     import enc_paths
-    enc_paths.build(clang)
-    jobs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "hostemu", "enc_paths.py"), "zstd", "catalog", "--json", "--option", str(v)], stdout=subprocess.PIPE,
-                             stderr=subprocess.PIPE, text=True, cwd=ROOT) for v in VARIANTS]
     names = enc_paths.COUNTERS["zstd"]
     assert set(UNREACHABLE) | set(NOT_REACHED) <= set(names) and set(NOT_REACHED) <= {112, 118}
-    for v, job in zip(VARIANTS, jobs):
-        out, err = job.communicate()
+    for v, job in jobs.items():
+        out, err = job.stdout, job.stderr
         assert job.returncode == 0, err
         results = json.loads(out.strip().splitlines()[-1])
         assert len(results) == len(ze.emulator_cases(v)) > 120

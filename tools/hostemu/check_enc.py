@@ -13,12 +13,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
+import emulib
 from emu_harness import EmuBatch, P
 from tests import common, oracle_lib
 from tests.oracle_lib import OracleError
 
 o = oracle_lib.load()
-lib = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_enc.so"))
+lib = emulib.load("enc")
 quick = "--quick" in sys.argv
 
 
@@ -29,8 +30,8 @@ class EncBatch(EmuBatch):
         self.option = option
         self.buffer_size = buffer_size
 
-    def _call(self, op, src, src_off, src_len, dst, dst_off, caps, out_len, status, err, n):
-        return self.lib.emu_encode(op, P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(caps), P(out_len), P(status), P(err), n, self.option, self.buffer_size)
+    def _call(self, op, *batch):
+        return self.lib.emu_encode(op, *batch, self.option, self.buffer_size)
 
 
 def expect(fn, *args):

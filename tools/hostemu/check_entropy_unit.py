@@ -3,13 +3,14 @@ emulator (libemu_entropy_unit.so), against the oracle's restatement of the Java 
   huf    HuffmanCompressionTable.initialize (buildTree + setMaxHeight + the values): code lengths, values, table height
   norm   FiniteStateEntropy.normalizeCounts, and normalizeCounts2 alone (forced) with its three endings
   write  FiniteStateEntropy.writeNormalizedCounts: bytes and size, tight capacities included
-    python tools/hostemu/check_entropy_unit.py [cases]          (build lines: the two sources' headers)"""
+    python tools/hostemu/check_entropy_unit.py [cases]          (the two libraries: emulib.py's targets entropy_unit and unit_oracle_enc)"""
 import ctypes, os, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_entropy_unit.so"))
-ref = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libunit_oracle_enc.so"))
-P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib
+from emu_harness import P
+emu = emulib.load("entropy_unit")
+ref = emulib.load("unit_oracle_enc", env=False)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
 rng = np.random.default_rng(11)
 bad = 0

@@ -2,38 +2,24 @@
 through the two-pass decoders with an arena asked for after the chunk count is known, fold, the serial kernel for everything else --
 against the oracle, on the streams every writer produces.  (Variant 1 runs the chunks through the ring decoders at 4 / 16 lanes per chunk,
 which lean on the hardware's in-order memory pipeline and do not run here.)"""
-import ctypes, os, sys
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib
+from emu_harness import Layout
 from tests import common, oracle_lib
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu.so"))
+emu = emulib.load("emu")
 o = oracle_lib.load()
-P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
 
 def run(snappy, buffer_size, variant, streams, caps):
-    n = len(streams)
-    src_off = np.zeros(n, dtype=np.int64); src_len = np.zeros(n, dtype=np.int32)
-    dst_off = np.zeros(n, dtype=np.int64); dst_cap = np.array(caps, dtype=np.int32)
-    pos = 64
-    for i, f in enumerate(streams):
-        src_off[i] = pos; src_len[i] = len(f); pos += len(f) + 7
-    src = np.full(pos + 64, 0x5A, dtype=np.uint8)
-    for i, f in enumerate(streams):
-        src[src_off[i]:src_off[i] + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    pos = 64
-    for i, c in enumerate(caps):
-        dst_off[i] = pos; pos += c + 64
-    dst = np.full(pos + 64, 0xA5, dtype=np.uint8)
-    out_len = np.zeros(n, dtype=np.int32); status = np.full(n, -999, dtype=np.int32); err = np.zeros(n, dtype=np.int64)
-    emu.emu_hadoop(0, 1 if snappy else 0, buffer_size, variant, P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(dst_cap), P(out_len), P(status), P(err), n)
-    outs = [dst[dst_off[i]:dst_off[i] + max(int(out_len[i]), 0)].tobytes() for i in range(n)]
-    for i in range(n):
-        hi = dst_off[i + 1] if i + 1 < n else len(dst)
-        assert (dst[dst_off[i] + caps[i]:hi] == 0xA5).all(), "stream %d: wrote beyond its capacity" % i
-    return outs, [int(x) for x in status], [int(x) for x in err]
+    lay = Layout(streams, caps, lambda i, n: 7, lambda i, c: 64, fresh=(0, -999, 0))
+    emu.emu_hadoop(0, 1 if snappy else 0, buffer_size, variant, *lay.args())
+    lay.check_guards("stream")
+    return lay.outputs(), lay.status.tolist(), lay.err.tolist()
 
 
 def main():

@@ -5,7 +5,6 @@ and the frame writer.  The correctness argument for the masked replay (lz4_compr
 
   check_lz4_accel.py [--quick]     --quick: accelerations 2, 7 and 64 and a few KiB of text (seconds); without it every acceleration of the GPU test and that test's
                                    own 64 KiB blocks (a fiber switch per memory access and lane: about twenty minutes)"""
-import ctypes
 import os
 import sys
 import time
@@ -14,10 +13,11 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from emu_harness import EmuBatch, P  # noqa: E402
+import emulib  # noqa: E402
+from emu_harness import EmuBatch  # noqa: E402
 from tests import lz4_accel_cases as cases, lz4_accel_ref as ref  # noqa: E402
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", os.environ.get("HOSTEMU_LIB", "libemu_lz4_accel.so")))
+emu = emulib.load("lz4_accel")
 quick = "--quick" in sys.argv
 BAD_HINT = -(3 + 16 * 102)  # INVALID_ARGUMENT / ACHIP_D_BAD_ARGUMENT
 
@@ -28,8 +28,8 @@ class AccelBatch(EmuBatch):
         self.args = (variant, mem_waves, hint, acceleration)
         self.frame = frame
 
-    def _call(self, op, src, src_off, src_len, dst, dst_off, caps, out_len, status, err, n):
-        return emu.emu_lz4_accel(self.frame, P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(caps), P(out_len), P(status), P(err), n, *self.args)
+    def _call(self, op, *batch):
+        return emu.emu_lz4_accel(self.frame, *batch, *self.args)
 
 
 def inputs():

@@ -2,15 +2,17 @@
 block decoder with an arena asked for after the block count is known, fold -- against the plaintext, on frames as writers produce them
 (the oracle's restatement of the Java writer: 4 MiB blocks, stored when not smaller; hand-built frames with content size / content checksum
 and smaller block sizes).  Irregular items go to the wavefront-per-item kernel, which does not run here (tests/test_gpu_lz4_frame.py)."""
-import ctypes, os, struct, sys
+import os, struct, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib
+from emu_harness import Layout
 from tests import common, oracle_lib
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu.so"))
+emu = emulib.load("emu")
 o = oracle_lib.load()
-P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
 
 def frame(content, size_id=7, content_size=False, content_checksum=False, stored=()):
@@ -33,26 +35,10 @@ def frame(content, size_id=7, content_size=False, content_checksum=False, stored
 
 
 def run(variant, frames, caps):
-    n = len(frames)
-    src_off = np.zeros(n, dtype=np.int64); src_len = np.zeros(n, dtype=np.int32)
-    dst_off = np.zeros(n, dtype=np.int64); dst_cap = np.array(caps, dtype=np.int32)
-    pos = 64
-    for i, f in enumerate(frames):
-        src_off[i] = pos; src_len[i] = len(f); pos += len(f) + 3
-    src = np.full(pos + 64, 0x5A, dtype=np.uint8)
-    for i, f in enumerate(frames):
-        src[src_off[i]:src_off[i] + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    pos = 64
-    for i, c in enumerate(caps):
-        dst_off[i] = pos; pos += c + 64
-    dst = np.full(pos + 64, 0xA5, dtype=np.uint8)
-    out_len = np.zeros(n, dtype=np.int32); status = np.full(n, -999, dtype=np.int32); err = np.zeros(n, dtype=np.int64)
-    emu.emu_lz4frame(variant, P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(dst_cap), P(out_len), P(status), P(err), n)
-    outs = [dst[dst_off[i]:dst_off[i] + max(int(out_len[i]), 0)].tobytes() for i in range(n)]
-    for i in range(n):
-        hi = dst_off[i + 1] if i + 1 < n else len(dst)
-        assert (dst[dst_off[i] + caps[i]:hi] == 0xA5).all(), "frame %d: wrote beyond its capacity" % i
-    return outs, [int(x) for x in status]
+    lay = Layout(frames, caps, lambda i, n: 3, lambda i, c: 64, fresh=(0, -999, 0))
+    emu.emu_lz4frame(variant, *lay.args())
+    lay.check_guards("frame")
+    return lay.outputs(), lay.status.tolist()
 
 
 def main():

@@ -11,9 +11,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib  # noqa: E402
 from tests import pack_cases as cases  # noqa: E402
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", os.environ.get("HOSTEMU_LIB", "libemu_pack.so")))
+emu = emulib.load("pack")
 _vp, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 emu.emu_pack_tile_bytes.restype = ctypes.c_longlong
 emu.emu_compress_bound.argtypes = [_i32, _vp, _vp, _vp, _i32, _i32]

@@ -6,11 +6,13 @@ import ctypes, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib
+from emu_harness import P
 from tests import common, oracle_lib
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu.so"))
+emu = emulib.load("emu")
 o = oracle_lib.load()
-P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
 
 def sequences(c):

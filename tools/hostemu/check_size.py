@@ -10,9 +10,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib  # noqa: E402
 from tests import decoded_size_cases as cases, oracle_lib  # noqa: E402
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_size.so"))
+emu = emulib.load("size")
 _vp, _i32 = ctypes.c_void_p, ctypes.c_int32
 emu.emu_decoded_size.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]
 emu.emu_lz4_size_shape.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]

@@ -14,17 +14,15 @@ import os
 import sys
 import time
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from emu_harness import EmuBatch, P  # noqa: E402
+import emulib  # noqa: E402
+from emu_harness import EmuBatch, run_windows  # noqa: E402
 from tests import snf_params_cases as cases, snf_params_ref as ref, window_cases  # noqa: E402
 
-HERE = os.path.join(ROOT, "tools", "hostemu")
-W = ctypes.CDLL(os.path.join(HERE, "libemu_snf_params_w.so"))
-R = ctypes.CDLL(os.path.join(HERE, "libemu_snf_params_r.so"))
+W = emulib.load("snf_params_w")  # (HOSTEMU_LIB: another build of the writers' unit)
+R = emulib.load("snf_params_r", env=False)
 _vp, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 for lib in (W, R):
     lib.emu_snf_write.argtypes = [_i32, _i32, _i32, _i32, _i64] + [_vp] * 9 + [_i32]
@@ -39,8 +37,8 @@ class Writer(EmuBatch):
         self.options = {}
         self.args = (variant, list_entries, int(params[0]), params[1], ref.ratio_bits(params[2]))
 
-    def _call(self, op, *a):
-        return W.emu_snf_write(*self.args, *[P(x) for x in a[:-1]], a[-1])
+    def _call(self, op, *batch):
+        return W.emu_snf_write(*self.args, *batch)
 
 
 class Reader(EmuBatch):
@@ -48,43 +46,14 @@ class Reader(EmuBatch):
         self.options = {}
         self.args = (variant, int(verify))
 
-    def _call(self, op, *a):
-        return R.emu_snf_read(*self.args, *[P(x) for x in a[:-1]], a[-1])
+    def _call(self, op, *batch):
+        return R.emu_snf_read(*self.args, *batch)
 
 
 def window_run(lib, compress, variant, params, verify):
     """-> run(fmt, compress, buffer_size, windows, flags, caps) as tests/window_cases.py's loops want it"""
-    def run(fmt, _compress, _buffer_size, windows, flags, caps):
-        n = len(windows)
-        src_len = np.array([len(w) for w in windows], dtype=np.int32)
-        src_off = np.zeros(n, dtype=np.int64)
-        dst_off = np.zeros(n, dtype=np.int64)
-        dst_cap = np.array(caps, dtype=np.int32)
-        pos = 64
-        for i, w in enumerate(windows):
-            src_off[i] = pos
-            pos += len(w) + 3
-        src = np.full(pos + 64, 0x5A, dtype=np.uint8)
-        for i, w in enumerate(windows):
-            src[src_off[i]:src_off[i] + len(w)] = np.frombuffer(bytes(w), dtype=np.uint8)
-        pos = 64
-        for i, c in enumerate(caps):
-            dst_off[i] = pos
-            pos += int(c) + 16
-        dst = np.full(pos + 64, 0xA5, dtype=np.uint8)
-        fl = np.array(flags, dtype=np.int32)
-        out_len, status, stop = (np.full(n, -7, dtype=np.int32) for _ in range(3))
-        err, consumed, need = (np.full(n, -7, dtype=np.int64) for _ in range(3))
-        D = lambda a: a.ctypes.data  # noqa: E731
-        r = lib.emu_snf_window(int(compress), variant, int(params[0]), params[1], ref.ratio_bits(params[2]), int(verify), D(fl), D(src), D(src_off), D(src_len), D(dst), D(dst_off),
-                               D(dst_cap), D(out_len), D(status), D(err), n, D(consumed), D(stop), D(need))
-        assert r == 0, r
-        for i in range(n):
-            hi = dst_off[i + 1] if i + 1 < n else len(dst)
-            assert (dst[dst_off[i] + caps[i]:hi] == 0xA5).all(), "window %d: wrote beyond its capacity" % i
-        return [{"consumed": int(consumed[i]), "out": dst[dst_off[i]:dst_off[i] + max(int(out_len[i]), 0)].tobytes(), "stop": int(stop[i]), "need": int(need[i]),
-                 "status": int(status[i]), "err": int(err[i])} for i in range(n)]
-    return run
+    head = (int(compress), variant, int(params[0]), params[1], ref.ratio_bits(params[2]), int(verify))
+    return lambda fmt, _compress, _buffer_size, windows, flags, caps: run_windows(lambda *a: lib.emu_snf_window(*head, *a), windows, flags, caps)
 
 
 def emulator_parameter_sets():

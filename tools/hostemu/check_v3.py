@@ -3,46 +3,28 @@ with the oracle: plaintext, status, error offset, and no write outside the block
 --part edges [--ops ...]: the catalog of constructed streams of tests/decoder_edge_cases.py instead -- every ring instantiation of the launch tables (lane
 widths 1 .. 64, both ring classes, the latency class) on the cases built for its own ring sizes, the two-pass decoders on the 4-lane cases, at four
 (source, destination) misalignments."""
-import ctypes, os, sys
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib
+from emu_harness import Layout
 from tests import common, oracle_lib
 from tests.oracle_lib import OracleError
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", os.environ.get("HOSTEMU_LIB", "libemu.so")))  # (HOSTEMU_LIB=libemu_lockstep.so: emu_lockstep.cpp)
+emu = emulib.load("emu")  # (HOSTEMU_LIB=libemu_lockstep.so: emu_lockstep.cpp, emulib's target `lockstep`)
 o = oracle_lib.load()
 
 
 def run(op, blocks, caps, misalign=0, dst_misalign=None):
-    n = len(blocks)
     GUARD = 64
-    src_off, dst_off = [], []
-    pos = misalign
-    for b in blocks:
-        src_off.append(pos)
-        pos += len(b) + 7 + (len(b) % 5)
-    src = np.zeros(pos + 64, dtype=np.uint8)
-    for b, so in zip(blocks, src_off):
-        src[so:so + len(b)] = np.frombuffer(b, dtype=np.uint8)
-    pos = GUARD + (misalign if dst_misalign is None else dst_misalign)
-    for c in caps:
-        dst_off.append(pos)
-        pos += c + GUARD + (c % 3)
-    dst = np.full(pos + 64, 0xA5, dtype=np.uint8)
-    so = np.array(src_off, dtype=np.int64); sl = np.array([len(b) for b in blocks], dtype=np.int32)
-    do = np.array(dst_off, dtype=np.int64); dc = np.array(caps, dtype=np.int32)
-    ol = np.zeros(n, dtype=np.int32); st = np.zeros(n, dtype=np.int32); eo = np.zeros(n, dtype=np.int64)
-    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    r = emu.emu_batch(op, P(src), P(so), P(sl), P(dst), P(do), P(dc), P(ol), P(st), P(eo), n)
+    lay = Layout(blocks, caps, lambda i, n: 7 + n % 5, lambda i, c: GUARD + c % 3, src_lead=misalign, dst_lead=GUARD + (misalign if dst_misalign is None else dst_misalign),
+                 filler=0, fresh=(0, 0, 0))
+    r = emu.emu_batch(op, *lay.args())
     assert r == 0
-    outs = []
-    for i in range(n):
-        outs.append(dst[dst_off[i]:dst_off[i] + ol[i]].tobytes())
-        lo = dst_off[i] + caps[i]
-        assert (dst[lo:lo + GUARD] == 0xA5).all(), "block %d wrote past its output" % i
-        assert (dst[dst_off[i] - GUARD:dst_off[i]] == 0xA5).all() or i > 0, "block %d wrote before its output" % i
-    return outs, st.tolist(), eo.tolist()
+    lay.check_guards("block")
+    return lay.outputs(), lay.status.tolist(), lay.err.tolist()
 
 
 def expect(codec, data, cap):

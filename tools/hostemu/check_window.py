@@ -9,52 +9,21 @@ import ctypes
 import os
 import sys
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib  # noqa: E402
+from emu_harness import run_windows  # noqa: E402
 from tests import oracle_lib, window_cases as cases  # noqa: E402
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", os.environ.get("HOSTEMU_LIB", "libemu_window.so")))
+emu = emulib.load("window")
 _vp, _i32 = ctypes.c_void_p, ctypes.c_int32
 emu.emu_window.argtypes = [_i32, _i32, _i32] + [_vp] * 10 + [_i32] + [_vp] * 3
-PREFILL = 0xA5
 
 
 def run(fmt, compress, buffer_size, windows, flags, caps):
-    n = len(windows)
-    src_len = np.array([len(w) for w in windows], dtype=np.int32)
-    src_off = np.zeros(n, dtype=np.int64)
-    dst_off = np.zeros(n, dtype=np.int64)
-    dst_cap = np.array(caps, dtype=np.int32)
-    pos = 64
-    for i, w in enumerate(windows):
-        src_off[i] = pos
-        pos += len(w) + 3
-    src = np.full(pos + 64, 0x5A, dtype=np.uint8)
-    for i, w in enumerate(windows):
-        src[src_off[i]:src_off[i] + len(w)] = np.frombuffer(bytes(w), dtype=np.uint8)
-    pos = 64
-    for i, c in enumerate(caps):
-        dst_off[i] = pos
-        pos += c + 16
-    dst = np.full(pos + 64, PREFILL, dtype=np.uint8)
-    fl = np.array(flags, dtype=np.int32)
-    out_len = np.full(n, -7, dtype=np.int32)
-    status = np.full(n, -7, dtype=np.int32)
-    stop = np.full(n, -7, dtype=np.int32)
-    err = np.full(n, -7, dtype=np.int64)
-    consumed = np.full(n, -7, dtype=np.int64)
-    need = np.full(n, -7, dtype=np.int64)
     op = (cases.COMPRESS_OP if compress else cases.DECOMPRESS_OP)[fmt]
-    P = lambda a: a.ctypes.data
-    r = emu.emu_window(op, buffer_size, 2, P(fl), P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(dst_cap), P(out_len), P(status), P(err), n, P(consumed), P(stop), P(need))
-    assert r == 0, r
-    for i in range(n):
-        hi = dst_off[i + 1] if i + 1 < n else len(dst)
-        assert (dst[dst_off[i] + caps[i]:hi] == PREFILL).all(), "window %d: wrote beyond its capacity" % i
-    return [{"consumed": int(consumed[i]), "out": dst[dst_off[i]:dst_off[i] + max(int(out_len[i]), 0)].tobytes(), "stop": int(stop[i]), "need": int(need[i]),
-             "status": int(status[i]), "err": int(err[i])} for i in range(n)]
+    return run_windows(lambda *a: emu.emu_window(op, buffer_size, 2, *a), windows, flags, caps)
 
 
 def main():

@@ -9,9 +9,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib  # noqa: E402
 from tests import xxh3_ref  # noqa: E402
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_xxh3.so"))
+emu = emulib.load("xxh3")
 emu.emu_xxh3_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p]
 M64 = (1 << 64) - 1
 

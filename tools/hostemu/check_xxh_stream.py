@@ -12,9 +12,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib  # noqa: E402
 from tests import xxh_stream_cases as C  # noqa: E402
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_xxh_stream.so"))
+emu = emulib.load("xxh_stream")
 _vp, _i32 = ctypes.c_void_p, ctypes.c_int32
 emu.emu_hash_state_size.restype = ctypes.c_longlong
 emu.emu_hash_state_size.argtypes = [_i32]

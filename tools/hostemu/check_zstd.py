@@ -5,6 +5,9 @@ import ctypes, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emulib
+from emu_harness import Layout, P
 from tests import common, oracle_lib, native_libs
 
 try:
@@ -17,38 +20,19 @@ except ImportError:
     libzstd = native_libs.zstd_compress
     HAVE_LIBZSTD = native_libs.available()
 
-emu = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_zstd.so"))
+emu = emulib.load("zstd")
 o = oracle_lib.load()
-P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
 
 def run(frames, caps, tile=0, exec_mode=1, pass_blocks=0, mb_max_bytes=0):
-    n = len(frames)
-    src_off = np.zeros(n, dtype=np.int64); src_len = np.zeros(n, dtype=np.int32)
-    dst_off = np.zeros(n, dtype=np.int64); dst_cap = np.array(caps, dtype=np.int32)
-    pos = 64
-    for i, f in enumerate(frames):
-        src_off[i] = pos; src_len[i] = len(f); pos += len(f) + 3  # (unaligned on purpose)
-    src = np.full(pos + 64, 0x5A, dtype=np.uint8)
-    for i, f in enumerate(frames):
-        src[src_off[i]:src_off[i] + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    pos = 64
-    for i, c in enumerate(caps):
-        dst_off[i] = pos; pos += c + 64 + (i % 5)
-    dst = np.full(pos + 64, 0xA5, dtype=np.uint8)
-    out_len = np.zeros(n, dtype=np.int32); status = np.zeros(n, dtype=np.int32); err = np.zeros(n, dtype=np.int64)
-    fb = np.zeros(n + 1, dtype=np.int32)
+    lay = Layout(frames, caps, lambda i, n: 3, lambda i, c: 64 + i % 5, fresh=(0, 0, 0))  # (unaligned on purpose)
+    fb = np.zeros(lay.n + 1, dtype=np.int32)
     counters = np.zeros(64, dtype=np.int32)
-    k = emu.emu_zstd_pipe(P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(dst_cap), P(out_len), P(status), P(err), n, tile, exec_mode, P(fb), pass_blocks, P(counters), ctypes.c_int64(mb_max_bytes))
+    k = emu.emu_zstd_pipe(*lay.args(), tile, exec_mode, P(fb), pass_blocks, P(counters), ctypes.c_int64(mb_max_bytes))
     run.counters = counters
-    outs = []
-    for i in range(n):
-        outs.append(dst[dst_off[i]:dst_off[i] + max(int(out_len[i]), 0)].tobytes() if status[i] == 0 else None)
-        lo = dst_off[i] + caps[i]
-        hi = dst_off[i + 1] if i + 1 < n else len(dst)
-        # (a few bytes beyond the capacity may be scribbled by whole-vector stores only where the product allows it: nowhere)
-        assert (dst[lo:hi] == 0xA5).all(), "item %d: wrote beyond its capacity" % i
-    return outs, status, sorted(int(x) for x in fb[:k])
+    # (a few bytes beyond the capacity may be scribbled by whole-vector stores only where the product allows it: nowhere)
+    lay.check_guards()
+    return [out if st == 0 else None for out, st in zip(lay.outputs(), lay.status)], lay.status, sorted(int(x) for x in fb[:k])
 
 
 def frame_blocks(f):

@@ -3,9 +3,7 @@
 #if !defined(HOSTEMU_NO_RINGS_LOCKSTEP)
 #define HOSTEMU_RINGS_LOCKSTEP 1  // achip_rings.h: the lanes of a group meet where the device's lockstep makes them meet
 #endif
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }  // development counters of kernels under emulation (ACHIP_EMU_COUNT)
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/lz4_decompress_v2.hip"
 #include "../../aircompressor_amd/csrc/snappy_decompress_v2.hip"
 #include "../../aircompressor_amd/csrc/lz4_decompress_v7.hip"
@@ -14,31 +12,6 @@ extern "C" { long long achip_emu_counters[16]; }  // development counters of ker
 #include "../../aircompressor_amd/csrc/lz4_frame.hip"
 #include "../../aircompressor_amd/csrc/snappy_frame.hip"
 #include "../../aircompressor_amd/csrc/block_decode.cpp"
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-// A scratch of exactly the size a *_scratch_bytes function names, filled with 0xCD, and a guard tail behind it: a kernel that writes beyond the
-// named size changes the tail, and check() ends the process (loud in every caller, whatever it does with a return value).
-struct GuardedScratch {
-    static constexpr size_t TAIL = 4096;
-    std::vector<uint8_t> v;
-    uint8_t* assign(int64_t bytes)
-    {
-        v.assign((size_t)bytes + TAIL, 0xCD);
-        return v.data();
-    }
-    int64_t size() const { return (int64_t)(v.size() - TAIL); }
-    int check(const char* what, int r) const
-    {
-        for (size_t i = v.size() - TAIL; i < v.size(); i++) {
-            if (v[i] != 0xCD) {
-                fprintf(stderr, "hostemu: %s wrote %zu bytes beyond its scratch of %lld bytes\n", what, i - (v.size() - TAIL), (long long)size());
-                abort();
-            }
-        }
-        return r;
-    }
-};
 // the probes of the decoders' auto mode are not built here: the probe statistics stay
 // zero, which picks the ring decoders
 hipError_t achip::launch_snappy_element_sample(const BatchArgs&, hipStream_t, int32_t*, int32_t, int32_t) { return hipSuccess; }

@@ -3,13 +3,10 @@
 // tools/hostemu/check_entropy_unit.py can hold each against the oracle's restatement of the Java method on hundreds of thousands of count sets
 // -- including the rare paths (the height limiter's repayment, normalizeCounts2's three endings) that whole-frame inputs seldom reach.
 // Built like emu_enc.cpp (every memory access a soft order point: the untouched serial parts around these helpers run the same code on all lanes):
-//   clang++ -O2 -std=c++17 -fPIC -shared -fno-omit-frame-pointer -fsanitize-coverage=inline-8bit-counters,trace-loads,trace-stores -I tools/hostemu -I include \
-//           -I aircompressor_amd/csrc -o tools/hostemu/libemu_entropy_unit.so tools/hostemu/emu_entropy_unit.cpp
+// target entropy_unit in the table of emulib.py.
 #define HOSTEMU_ACCESS_LOCKSTEP 1
 #define HOSTEMU_ORDER_IS_RENDEZVOUS 1
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/zstd_compress.hip"
 
 namespace achip {

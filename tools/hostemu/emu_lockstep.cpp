@@ -10,6 +10,7 @@
 // access-granular lockstep a group only has to meet once in a while, the fine order comes from the model.  So this unit makes order()
 // the group's rendezvous (HOSTEMU_RINGS_ORDER_ONLY) and nothing else: a ring kernel needs no emulator-only annotation beyond the barriers
 // its device code has anyway.  Lane-private decoders (ops 16, 18) and the two-pass decoders (op 24) pass with no points at all.
+// Built as an access-lockstep unit like emu_enc.cpp: target lockstep in the table of emulib.py.
 #define HOSTEMU_RINGS_ORDER_ONLY 1
 #define HOSTEMU_ACCESS_LOCKSTEP 1
 #define HOSTEMU_NO_RINGS_LOCKSTEP 1

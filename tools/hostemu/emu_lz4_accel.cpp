@@ -2,9 +2,7 @@
 // the CPU, every memory access a soft order point like emu_enc.cpp (the same build flags: tools/hostemu/build.sh lz4_accel).  Driven by check_lz4_accel.py.
 #define HOSTEMU_ACCESS_LOCKSTEP 1
 #define HOSTEMU_ORDER_IS_RENDEZVOUS 1
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/lz4_compress.hip"
 #include <vector>
 // frame: 0 = block encoder (variant 0 / 1 / 4; memWaves 0 = a wavefront per block, 1 / 2 = the two-tier kernel with a grid of two workgroups), 1 = the frame writer

@@ -1,8 +1,6 @@
 // tools/hostemu/emu_pack.cpp -- the bound kernel, the pack scan and the dense copy (pack_outputs.hip) under the fiber emulator: the scan's workgroup barriers,
 // the copy's 64-way search (a ballot: a rendezvous of the wave here) and its per-lane chunk work.  Driven by check_pack.py.
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/pack_outputs.hip"
 #include <vector>
 extern "C" long long emu_pack_tile_bytes() { return achip::PACK_TILE_BYTES; }

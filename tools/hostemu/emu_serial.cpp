@@ -5,9 +5,7 @@
 // to stay what it is on the device.
 #define HOSTEMU_RINGS_LOCKSTEP 1
 #define HOSTEMU_ORDER_IS_RENDEZVOUS 1
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/lz4_frame.hip"
 #include "../../aircompressor_amd/csrc/snappy_frame.hip"
 #include "../../aircompressor_amd/csrc/hadoop_streams.hip"

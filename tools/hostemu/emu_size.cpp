@@ -1,9 +1,7 @@
 // tools/hostemu/emu_size.cpp -- the sizing kernels and the output planner (decoded_size.hip) under the fiber emulator: the lane-per-block and wavefront-per-block
 // LZ4 walks (the window chain's lane reads, scans and ballots are rendezvous of the wave here), the Snappy preamble, the Zstd walk (its table builds meet at
 // workgroup barriers), the containers' list / size / fold, the planner's workgroup scans.  Driven by check_size.py.
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/decoded_size.hip"
 #include <vector>
 extern "C" int emu_decoded_size(int32_t op, const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t* outSize, int32_t* status, int64_t* errOffset, int32_t n)

@@ -1,8 +1,6 @@
 // tools/hostemu/emu_xxh3.cpp -- the XXH3 kernels (xxhash3.hip) under the fiber emulator: the lane-per-buffer short kernel and the
 // wavefront-per-buffer long kernel, whose cross-lane sums (__shfl_xor) and ballot are rendezvous of the wave here.  Driven by check_xxh3.py.
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/xxhash3.hip"
 extern "C" int emu_xxh3_batch(const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, int32_t n, uint64_t seed, int32_t wide, int64_t* out)
 {

@@ -4,9 +4,7 @@
 // bytes between lanes in hardware order and is NOT emulated: items on the fallback list are reported to the caller instead.
 // The ring executor (zstd_pipe_execute_kernel: four lanes an item over achip_rings.h) needs the rings' group rendezvous, as tools/hostemu/emu.cpp has them.
 #define HOSTEMU_RINGS_LOCKSTEP 1  // achip_rings.h: the lanes of a group meet where the device's lockstep makes them meet
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long achip_emu_counters[16]; }
+#include "emu_preamble.h"
 #include "../../aircompressor_amd/csrc/zstd_decompress_pipe.hip"
 #include "../../aircompressor_amd/csrc/zstd_default_tables.h"
 #include "../../aircompressor_amd/csrc/achip_zstd_frame.h"

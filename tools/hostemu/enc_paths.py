@@ -1,19 +1,20 @@
 """Which way the sequences of the LZ4 and Snappy window encoders go (lz4_compress_mw.h / snappy_compress_mw.h, variant 4), and which way the Zstd encoder goes
 (zstd_compress_body.h, zstd_dfast_mw.h; --option is its variant, 3 by default): a counting build of the emulator library (-DACHIP_HOST_STATS:
-libemu_enc_stats.so, built here), the counters per input or summed, the bytes against the oracle's.
+emulib.py's target enc_stats, rebuilt here when stale), the counters per input or summed, the bytes against the oracle's.
 
     enc_paths.py [lz4|snappy] [corpus|catalog]      corpus: the 64 KiB slices of tests/golden, a line each;  catalog: tests/encoder_edge_cases.py (the entries an
                                                     emulator run takes), a line per counter with the case that raised it first
 
     enc_paths.py zstd catalog [--option N]          tests/zstd_encoder_cases.py (emulator_cases()), the same table
 
-    enc_paths.py lz4|snappy|zstd catalog --json [--option N]      the same as one JSON line [[case, identical, {counter: count}], ...], the library as it lies there
-                                                    (tests/test_encoder_edge_cases.py builds it once and starts one of these per variant, side by side)"""
-import ctypes, json, os, subprocess, sys
+    enc_paths.py lz4|snappy|zstd catalog --json [--option N]      the same as one JSON line [[case, identical, {counter: count}], ...]
+                                                    (tests/test_encoder_edge_cases.py builds the library once and starts one of these per variant, side by side)"""
+import ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from emu_harness import EmuBatch, P
+import emulib
+from emu_harness import EmuBatch
 
 OPS = {"lz4": 1, "snappy": 3, "zstd": 5}
 DEFAULT_OPTION = {"lz4": 4, "snappy": 4, "zstd": 3}
@@ -46,29 +47,25 @@ COUNTERS = {
              121: "full group of 64", 122: "literal length >= 65536 (code 35)", 123: "match length >= 65539 (code 52)", 124: "block dropped by the gain test",
              125: "block committed", 126: "window base moves", 127: "new table: the previous one is not valid"},
 }
-SO = os.path.join(ROOT, "tools", "hostemu", "libemu_enc_stats.so")
 
 
 def build(clang=None):
-    """the emulator's encoder unit with the counters compiled in (what zc_stats.py builds for the Zstd match finder)"""
-    emu = os.path.join(ROOT, "tools", "hostemu")
-    subprocess.run([clang or "/opt/rocm/lib/llvm/bin/clang++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fno-omit-frame-pointer", "-DACHIP_HOST_STATS",
-                    "-fsanitize-coverage=inline-8bit-counters,trace-loads,trace-stores", "-I", emu, "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "aircompressor_amd", "csrc"), "-o", SO, os.path.join(emu, "emu_enc.cpp")], check=True)
-    return SO
+    """the emulator's encoder unit with the counters compiled in, rebuilt whatever lies there (emulib.py's target enc_stats; the compiler is emulib's)"""
+    emulib.build("enc_stats")
+    return emulib.path("enc_stats")
 
 
 class StatsBatch(EmuBatch):
     def __init__(self, lib, option):
         self.lib, self.options, self.option = lib, {}, option
 
-    def _call(self, op, src, src_off, src_len, dst, dst_off, caps, out_len, status, err, n):
-        return self.lib.emu_encode(op, P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(caps), P(out_len), P(status), P(err), n, self.option, 262144)
+    def _call(self, op, *batch):
+        return self.lib.emu_encode(op, *batch, self.option, 262144)
 
 
 def count(codec, inputs, oracle, option=None, lib=None):
     """every input on its own through the counting build: [(output == the oracle's, {counter: count})]"""
-    lib = lib or ctypes.CDLL(SO)
+    lib = lib or emulib.load("enc_stats")
     stats = (ctypes.c_longlong * 128).in_dll(lib, "g_zc_stats")
     option = DEFAULT_OPTION[codec] if option is None else option
     out = []
@@ -96,7 +93,6 @@ def main():
         entries = catalog(codecs[0])
         print(json.dumps([[e[0], ok, c] for e, (ok, c) in zip(entries, count(codecs[0], [d for _, d, _ in entries], o, option))]))
         return
-    build()
     for codec in codecs:
         names = COUNTERS[codec]
         if "catalog" in sys.argv[1:]:

@@ -2,18 +2,19 @@
 Structured inputs -- short and long incompressible stretches (the skip schedule grows, batches leave the LDS window and come back), near and
 far copies of 4..1500 bytes, byte runs, small alphabets -- of 13 bytes to 40 KB, plus, for seed 0, the sizes around the window's chunk
 boundaries and around 64 KiB (Snappy sub-blocks, LZ4's wide table)."""
-import sys, os, time, ctypes
+import sys, os, time
 ROOT_ = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT_); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
-from emu_harness import EmuBatch, P, ROOT
+import emulib
+from emu_harness import EmuBatch
 from tests import oracle_lib, common
 o = oracle_lib.load()
-lib = ctypes.CDLL(os.path.join(ROOT, "tools", "hostemu", "libemu_enc.so"))
+lib = emulib.load("enc")
 class EncBatch(EmuBatch):
     def __init__(self, option): self.lib = lib; self.options = {}; self.option = option
-    def _call(self, op, src, src_off, src_len, dst, dst_off, caps, out_len, status, err, n):
-        return self.lib.emu_encode(op, P(src), P(src_off), P(src_len), P(dst), P(dst_off), P(caps), P(out_len), P(status), P(err), n, self.option, 262144)
+    def _call(self, op, *batch):
+        return self.lib.emu_encode(op, *batch, self.option, 262144)
 seed = int(sys.argv[1]); count = int(sys.argv[2]); codec = sys.argv[3] if len(sys.argv) > 3 else "lz4"; opnum = {"lz4": 1, "snappy": 3, "zstd": 5}[codec]; variant = int(sys.argv[4]) if len(sys.argv) > 4 else 3
 rng = np.random.default_rng(seed)
 def gen(n):

@@ -14,7 +14,7 @@
 // untouched -- where the hardware's lockstep makes the lanes of a group meet: before anybody writes what somebody may still read, and
 // before anybody reads what somebody may still write (within one copy step too: all loads, then all stores).
 //
-// HOSTEMU_ACCESS_LOCKSTEP (tools/hostemu/emu_enc.cpp: the encoders): the unit is built with clang's -fsanitize-coverage=trace-loads,trace-stores,
+// HOSTEMU_ACCESS_LOCKSTEP (tools/hostemu/emu_enc.cpp: the encoders): the unit is built with clang's load / store tracing (emulib.py: LOCKSTEP),
 // whose callbacks make EVERY load and store of the kernel source a soft order point (below): a lane pauses before each memory access until
 // no lane of its wave can run further, so all lanes perform access k before any performs access k+1 -- the lockstep of a wavefront at
 // the granularity of memory operations.  That is what kernels need that run the same serial code on every lane and change shared state in

@@ -1,6 +1,6 @@
 /* tools/hostemu/unit_oracle_enc.c -- the oracle's restatements of the Java entropy helpers, exported one by one for
- * tools/hostemu/check_entropy_unit.py (test infrastructure: the oracle is the checker here, as everywhere).
- *   gcc -O2 -fPIC -std=gnu11 -fno-strict-aliasing -pthread -w -shared -o tools/hostemu/libunit_oracle_enc.so tools/hostemu/unit_oracle_enc.c $(ls oracle/*.c | grep -v zstd_enc.c) */
+ * tools/hostemu/check_entropy_unit.py (test infrastructure: the oracle is the checker here, as everywhere).  Built with gcc over the other oracle/*.c files:
+ * target unit_oracle_enc in the table of tools/hostemu/emulib.py. */
 #include "../../oracle/zstd_enc.c"
 
 /* HuffmanCompressionTable.initialize: code lengths and values per symbol, the table's maxNumberOfBits */
