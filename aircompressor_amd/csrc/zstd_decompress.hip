@@ -173,18 +173,12 @@ __device__ int32_t decode_literals(Ctx& c, Shared& sh, FrameState& fs, const Fse
             myStreamStart = sStart[s];
         }
     }
-    if (!singleStream) {
-        // the lock-step loop's post-condition (:273) can only fail if the last segment is over-long
-        ZVERIFY(c, oStart[3] <= uncompressedSize || uncompressedSize < 0, ACHIP_D_ZSTD_CORRUPTED, input);
-    }
+    // (The lock-step loop's post-condition, Huffman.java:282, never fails: no segment is longer than the first three.  Where those three cover more than the
+    // literals -- 1, 2 or 5 of them in four streams -- the Java code decodes them all the same, up to two bytes beyond the literals and inside its buffer, as this
+    // slab has room for; the fourth stream then has nothing to decode and must be at its end: decodeTail :291-317, which huf_decode_stream restates.)
     int32_t myDetail = 0;
     if (c.lane < nStreams) {
-        if (myOutStart <= myOutEnd) {
-            myDetail = huf_decode_stream(c, sh.huf, tableLog, mine, c.lit, myOutStart, myOutEnd);
-        }
-        else {
-            myDetail = ACHIP_D_ZSTD_CORRUPTED;
-        }
+        myDetail = huf_decode_stream(c, sh.huf, tableLog, mine, c.lit, myOutStart, myOutEnd);
     }
     const unsigned long long bad = __ballot(myDetail != 0);
     if (bad != 0) {

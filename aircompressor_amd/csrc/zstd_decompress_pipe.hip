@@ -707,7 +707,9 @@ __global__ __launch_bounds__(64) void zstd_pipe_literals_kernel(BatchArgs a, zp:
 #pragma unroll
                         for (int j = 0; j < 8; j++) {
                             const uint32_t sy = ((j < 4 ? symLo : symHi) >> (8 * (j & 3))) & 0xFFu;
-                            t[HUF_SLOT + sy] = (uint8_t)((lens >> (4 * j)) & 15u);
+                            if (i + j < (1 << useHuf)) {  // (a table of 2 or 4 entries: what lies behind it in the slot is not a symbol's length)
+                                t[HUF_SLOT + sy] = (uint8_t)((lens >> (4 * j)) & 15u);
+                            }
                         }
                     }
                 }

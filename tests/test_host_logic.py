@@ -160,13 +160,16 @@ def test_zstd_pipeline_kernels_on_the_cpu():
     oracle's encoder and of libzstd, single-block and multi-block, at two pass sizes, must decode to the plaintext on the fast path; damaged
     multi-block frames must either leave the fast path or decode to exactly what the oracle's decoder returns.  The case catalog of
     tests/zstd_frame_cases.py (hand-built frames at the execute stage's edges, valid and malformed, and encoders' frames) runs under BOTH execute
-    stages: the ring executor (exec mode 0, with and without its staging area for far matches) and the record executor (mode 1)."""
-    jobs = list(common.emulator_checks(["zstd"], {part: ("check_zstd.py", "--quick", "--part", part) for part in ("single", "multi", "damaged", "catalog")}).values())  # (side by side)
+    stages: the ring executor (exec mode 0, with and without its staging area for far matches) and the record executor (mode 1).  The entropy-stage catalog of
+    tests/zstd_entropy_cases.py (hand-built FSE tables, Huffman tables and streams, treeless literals and repeat-mode tables across blocks) runs through the one-kernel
+    decoder -- status, offset and bytes as the oracle has them -- and through the pipeline under each of the literal stage's three table layouts."""
+    jobs = list(common.emulator_checks(["zstd", "serial"], {part: ("check_zstd.py", "--quick", "--part", part) for part in ("single", "multi", "damaged", "catalog", "entropy")}).values())  # (side by side)
     outs = [j.stdout for j in jobs]
     assert all(j.returncode == 0 for j in jobs), "\n".join(outs)
     out = "\n".join(outs)
     lines = [l for l in out.splitlines() if "mismatches" in l]
-    assert len(lines) == 5 and all(" 0 mismatches" in l for l in lines), out
+    assert len(lines) == 6 and all(" 0 mismatches" in l for l in lines), out
+    assert out.count("entropy catalog, one-kernel decoder") == 2 and out.count("entropy catalog, pipeline") == 3 and out.count(" 0 wrong") >= 5, out
     assert out.count("catalog, ring executor") == 4 and out.count("catalog, record executor") == 2, out  # (two capacities each)
     assert "fast 18, fallback list []" in out and "fast 17, fallback list [17]" in out, out  # (the smallest passes: the frame of ~260 short blocks has no room)
 

@@ -1,6 +1,7 @@
 """Runs the Zstd decode pipeline (zstd_decompress_pipe.hip) on the CPU (tools/hostemu/libemu_zstd.so) over frames of the oracle's encoder
 (the Java compressor restated) and of libzstd, and compares with the plaintext.  Items the pipeline hands to its fallback list (the
-one-kernel decoder, which the emulator does not run) are counted; `--expect-fast` makes any of them a failure."""
+one-kernel decoder, which these parts do not run) are counted; `--expect-fast` makes any of them a failure.  `--part entropy` runs the catalog of
+tests/zstd_entropy_cases.py through both: the one-kernel decoder on libemu_serial.so, and the pipeline."""
 import ctypes, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -246,18 +247,86 @@ def catalog(expect_fast):
     return bad
 
 
+def entropy(expect_fast):
+    """--part entropy: the catalog of tests/zstd_entropy_cases.py (hand-built FSE tables, Huffman tables and streams, treeless literals and repeat-mode tables across
+    blocks) through the one-kernel decoder (libemu_serial.so) -- status, error offset and bytes as the oracle has them -- and through the pipeline: the literal stage with
+    split tables (13 items), plain entries (16) and lengths by symbol (16), the sequence stage on 1 and 4 wavefronts, exact capacities and 64 bytes of slack, catalog order and a seeded shuffle.
+    Every malformed case and every case the parse stage hands over by design must be on the fallback list; every other valid one must come back from the fast path."""
+    from emu_harness import EmuBatch
+    from tests import zstd_entropy_cases as ze
+    cases = ze.entropy_catalog()
+    quick = "--quick" in sys.argv
+    bad = 0
+
+    def expect(c, cap):
+        try:
+            return 0, 0, o.decompress("zstd", c.frame, cap)
+        except oracle_lib.OracleError as e:
+            return e.status, e.offset, None
+    expected = {pad: [expect(c, c.capacity(pad)) for c in cases] for pad in (0, 64)}
+    for pad in (0, 64):
+        for c, (est, _, eout) in zip(cases, expected[pad]):
+            if (est != 0) != c.malformed or (est == 0 and eout != c.plain):
+                bad += 1
+                print("MISMATCH entropy catalog %s: the oracle %s" % (c.name, "refuses" if est else "decodes %d bytes" % len(eout)))
+    one = EmuBatch()
+    for pad in (0, 64):
+        outs, status, err = one.run(4, [c.frame for c in cases], [c.capacity(pad) for c in cases], unaligned=(pad == 0))
+        wrong = 0
+        for i, (c, (est, eoff, eout)) in enumerate(zip(cases, expected[pad])):
+            if status[i] != est or (est == 0 and outs[i] != eout) or (est != 0 and err[i] != eoff):
+                wrong += 1
+                print("MISMATCH one-kernel decoder, pad %d, %s: status %d offset %d, the oracle's %d offset %d" % (pad, c.name, status[i], err[i], est, eoff))
+        print("entropy catalog, one-kernel decoder, pad %d: %d frames, %d wrong" % (pad, len(cases), wrong), flush=True)
+        bad += wrong
+    LIT = {3 << 2: "split tables (13 items)", 0: "plain entries (16 items)", 1 << 7: "lengths by symbol (16 items)"}
+    runs = [(3 << 2, 1, 0, False), (0, 4, 64, True), (1 << 7, 1, 0, True)] if quick else [(lit, waves, pad, shuffled) for lit in LIT for waves in (1, 4) for pad in (0, 64) for shuffled in (False, True)]
+    for lit, waves, pad, shuffled in runs:
+        order = np.random.default_rng(77).permutation(len(cases)) if shuffled else np.arange(len(cases))
+        sub = [cases[i] for i in order]
+        outs, status, fb = run([c.frame for c in sub], [c.capacity(pad) for c in sub], exec_mode=1 | lit | (waves << 4), pass_blocks=2048)
+        wrong = 0
+        for i, c in enumerate(sub):
+            est, eoff, eout = expected[pad][order[i]]
+            if c.malformed or c.fallback:
+                if i not in fb:
+                    wrong += 1
+                    print("MISMATCH pipeline, %s: %s, but not on the fallback list (status %d)" % (c.name, "malformed" if c.malformed else c.fallback, status[i]))
+            elif i in fb or status[i] != 0 or outs[i] != eout:
+                wrong += 1
+                first = -1
+                if outs[i] is not None:
+                    m = min(len(outs[i]), len(eout))
+                    d = np.nonzero(np.frombuffer(outs[i][:m], dtype=np.uint8) != np.frombuffer(eout[:m], dtype=np.uint8))[0]
+                    first = int(d[0]) if len(d) else m
+                print("MISMATCH pipeline, %s: %s, status %d, %s bytes of %d, first difference at %d" % (
+                    c.name, "on the fallback list" if i in fb else "fast path", status[i], None if outs[i] is None else len(outs[i]), len(eout), first))
+        stages = [int(x) for x in run.counters[33:39]]
+        want = sum(1 for c in cases if c.malformed or c.fallback)
+        if sum(stages) != want or len(fb) != want:
+            wrong += 1
+            print("MISMATCH pipeline: %d on the fallback list, by stage %s, expected %d" % (len(fb), stages, want))
+        print("entropy catalog, pipeline, literal stage %s, sequence stage on %d wavefronts, pad %d, %s: %d frames, fallback list by stage %s, %d wrong" % (
+            LIT[lit], waves, pad, "shuffled" if shuffled else "catalog order", len(cases), stages, wrong), flush=True)
+        bad += wrong
+    print("zstd entropy catalog on the one-kernel decoder and the pipeline: %d mismatches" % bad)
+    return bad
+
+
 def main():
     if "--fuzz" in sys.argv:
         k = sys.argv.index("--fuzz")
         sys.exit(1 if fuzz(int(sys.argv[k + 1]), int(sys.argv[k + 2]) if len(sys.argv) > k + 2 else 1) else 0)
     expect_fast = "--expect-fast" in sys.argv
-    part = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else "all"  # single | multi | damaged | catalog | all
+    part = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else "all"  # single | multi | damaged | catalog | entropy | all
     if part == "multi":
         sys.exit(1 if multi_block(expect_fast) else 0)
     if part == "damaged":
         sys.exit(1 if mutations(expect_fast) else 0)
     if part == "catalog":
         sys.exit(1 if catalog(expect_fast) else 0)
+    if part == "entropy":
+        sys.exit(1 if entropy(expect_fast) else 0)
     plains = [d for _, d in common.HAND_CASES if len(d) > 0] + [d[:131072] for _, d, _ in common.corpus_sample()[:8]] + common.synthetic_blocks(5, 6)
     plains = [p for p in plains if len(p) <= 131072]
     bad = 0; slow = 0; total = 0
@@ -285,6 +354,7 @@ def main():
         bad += multi_block(expect_fast)
         bad += mutations(expect_fast)
         bad += catalog(expect_fast)
+        bad += entropy(expect_fast)
     if bad or (expect_fast and slow):
         sys.exit(1)
 
