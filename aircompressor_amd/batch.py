@@ -126,6 +126,11 @@ class HipBatchCodec:
     def synchronize(self):
         self.native.synchronize()
 
+    def set_lz4frame_linked_blocks(self, accept):
+        """achip_ctx_set_lz4frame_linked_blocks for this codec's context: True = OP_LZ4FRAME_DECOMPRESS items (of launch, launch_mixed, run_host, run_host_mixed,
+        decoded_sizes, decompress_unsized) may be frames of linked blocks; False (the default) = they fail as the Java reader's do"""
+        self.native.set_lz4frame_linked_blocks(accept)
+
     def decoded_sizes(self, op, src, src_off, src_len, out_size, status, err_off, n_blocks):
         """achip_decoded_size_batch: out_size[i] (int64) = what item i decodes to under decode op `op`, found on the device without decoding; status[i] /
         err_off[i] report a structural fault (out_size[i] is then 0).  Asynchronous on the context stream; all arguments device-accessible."""

@@ -173,8 +173,19 @@ class Lz4FrameHipCompressor(_Lz4AcceleratedCompressor):
 
 class Lz4FrameHipDecompressor(_HipDecompressor):
     """Drop-in for Lz4FrameJavaDecompressor (M/lz4/Lz4FrameJavaDecompressor.java:26-44 -> Lz4FrameCompression.decompress):
-    concatenated and skippable frames, header / block / content checksums, the reference's exception for every malformed input."""
+    concatenated and skippable frames, header / block / content checksums, the reference's exception for every malformed input.
+    accept_linked_blocks=True goes a step beyond the Java reader: frames whose block-independence bit is clear (liblz4's frame API at its defaults, `lz4 -BD`,
+    python-lz4's lz4.frame.compress()) are decoded instead of refused, a block's matches reaching up to 65 535 bytes into the same frame's content in front
+    of it.  A property of the object, handed to its context before every call -- two readers that share a context keep their own values."""
     _codec = "lz4frame"
+
+    def __init__(self, device=0, native_ctx=None, accept_linked_blocks=False):
+        super().__init__(device, native_ctx)
+        self.accept_linked_blocks = bool(accept_linked_blocks)
+
+    def _decompress(self, src, dst):
+        self._native.set_lz4frame_linked_blocks(self.accept_linked_blocks)
+        return super()._decompress(src, dst)
 
 
 def _check_snappyframed_writer(block_size, min_compression_ratio):

@@ -366,6 +366,21 @@ int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx)
     return ctx->kernel.lz4Acceleration;
 }
 
+// Frames of linked blocks (nothing in the reference: its reader refuses them, M/lz4/Lz4FrameCompression.java:213-216)
+int32_t achip_ctx_set_lz4frame_linked_blocks(achip_ctx* ctx, int32_t accept)
+{
+    if (accept != 0 && accept != 1) return bad_argument("accept must be 0 or 1");
+    if (!ctx) return bad_argument("ctx is null");
+    achip::set_lz4f_linked_blocks(ctx->kernel, accept);
+    return 0;
+}
+
+int32_t achip_ctx_get_lz4frame_linked_blocks(achip_ctx* ctx)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    return ctx->kernel.lz4fLinkedBlocks;
+}
+
 // Double.toString(v), which the reference's "%1s" prints: the shortest digits -- two at least -- that read back as v (Double.MIN_VALUE is 4.9E-324), d.d in
 // [1e-3, 1e7) and d.dE±n outside.  aircompressor_amd/native.py has the same function for the Python classes' own check (tests/test_snf_params_abi.py compares).
 static std::string java_double_text(double v)

@@ -530,6 +530,7 @@ int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* sr
     HIP_TRY(hipSetDevice(ctx->device));
     if (const int32_t r = sizing_scratch(ctx, achip::decoded_size_scratch_bytes(codecOp, nBlocks)); r < 0) return r;
     achip::SizeArgs s{(const uint8_t*)srcBase, srcOff, srcLen, outSize, status, errOffset, nBlocks};
+    s.lz4fLinked = ctx->kernel.lz4fLinkedBlocks;
     HIP_TRY(achip::launch_decoded_size(codecOp, s, ctx->stream.get(), ctx->scratch.get()));
     return 0;
 }

@@ -133,6 +133,7 @@ struct SizeArgs {
     int32_t* __restrict__ status;
     int64_t* __restrict__ errOffset;
     int32_t nBlocks;
+    int32_t lz4fLinked = 0;               // ACHIP_OP_LZ4FRAME_DECOMPRESS: KernelSettings::lz4fLinkedBlocks of the context (1: frames of linked blocks are sized, not refused)
     const int32_t* nBlocksDev = nullptr;  // when set: the number of items is this device word (<= nBlocks): the LZ4 blocks a container's streams listed
 };
 // `op`: one of the seven ACHIP_OP_*_DECOMPRESS (anything else is an error); scratch: decoded_size_scratch_bytes(op, nBlocks) bytes

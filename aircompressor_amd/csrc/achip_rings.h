@@ -266,6 +266,43 @@ struct Rings {
     }
 
     // ---- output side ----
+    // A block that continues a history (lz4_block_decode<..., HISTORY>): `history` bytes in front of out[0] are content the same wavefront wrote to memory
+    // before init().  The ring takes the nearest min(history, LDS_REACH) of them at their virtual positions (negative ones: the index is the position
+    // & (OUT_RING - 1) as everywhere), which is the state it would be in had the group produced them itself: from here on a back-reference of up to
+    // LDS_REACH bytes is served from the ring whether its source lies in front of the block, behind its start or across it, and a farther one reads
+    // memory that was flushed -- by this block at least CHUNK bytes ago, or by whoever wrote the history.  Whole 16-byte granules are loaded where
+    // they lie inside the history; the granule that holds out[0] and the one that holds the history's first byte are put together from bytes
+    // (nothing in front of out - history is read, nothing is written to memory).  The caller keeps the history's stores in front of these loads
+    // (wave_mem_order(): a wavefront's memory operations are performed in order).
+    __device__ __forceinline__ void prime_history(int32_t history)
+    {
+        if (history <= 0) {  // (uniform: a frame's first block, a frame of independent blocks)
+            return;
+        }
+        enter();
+        const int32_t lowV = outBase - history;                                  // the history's first byte
+        const int32_t fromV = outBase - (history < LDS_REACH ? history : LDS_REACH);  // the first byte a match can ask the ring for
+        for (int32_t v = (fromV & ~15) + 16 * g; v < outBase; v += 16 * GS) {
+            u32x4 d;
+            if (v >= lowV && v + 16 <= outBase) {
+                d = ld16_global(outAligned + v);
+            }
+            else {
+                uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll 1
+                for (int i = 0; i < 16; i++) {
+                    const int32_t p = v + i;
+                    if (p >= lowV && p < outBase) {
+                        w[i >> 2] |= (uint32_t)outAligned[p] << (8 * (i & 3));
+                    }
+                }
+                d = u32x4{w[0], w[1], w[2], w[3]};
+            }
+            *(u32x4*)(outRing + (v & (OUT_RING - 1))) = d;
+        }
+        order();
+    }
+
     __device__ __forceinline__ void out_put(int32_t pos, uint32_t byte) { outRing[(pos + outBase) & (OUT_RING - 1)] = (uint8_t)byte; }
     __device__ __forceinline__ uint32_t out_get(int32_t pos) const { return outRing[(pos + outBase) & (OUT_RING - 1)]; }
 

@@ -22,6 +22,10 @@ struct KernelSettings {
     // Lz4Compressor.create(acceleration), 1 .. 65537 (no option: achip_ctx_set_lz4_acceleration -- a property of the compressor object, not a tuning knob): the LZ4
     // block and LZ4 frame encoders' search advances by this many positions per probe from its second probe on.  Above 1 the launchers take the `_accel` kernels.
     int lz4Acceleration = 1;
+    // LZ4 frames whose block-independence bit is clear (what liblz4's frame API writes at its defaults), 0 or 1 (no option: achip_ctx_set_lz4frame_linked_blocks --
+    // a property of the reader object; nothing in the reference, whose reader refuses them): 1 = every LZ4 frame decode and the LZ4FRAME line of the size query
+    // read such frames, a block's matches reaching up to 65 535 bytes into the frame's content in front of it; 0 = ACHIP_D_LZ4F_LINKED_BLOCKS, as the Java reader.
+    int lz4fLinkedBlocks = 0;
     // snappy.compress.mem_waves: wavefronts of a workgroup whose table lies in memory (0 .. 3).  Their tables are what the kernel's HBM traffic is made of -- 431 GB
     // a launch on the corpus batch, 100 x the input: 1 280 workgroups x 3 slabs x 32 KiB = 120 MB of tables, 15 MB per XCD against 4 MB of L2.
     int snappyMemWaves = 3;
@@ -66,6 +70,13 @@ inline SnfRefusal set_snf_writer(KernelSettings& ks, int32_t writeChecksums, int
         ks.snfMinRatioBits = minRatioBits;
     }
     return r;
+}
+// achip_ctx_set_lz4frame_linked_blocks: 0 or 1; a refused value leaves `ks` as it was
+inline bool set_lz4f_linked_blocks(KernelSettings& ks, int32_t accept)
+{
+    if (accept != 0 && accept != 1) return false;
+    ks.lz4fLinkedBlocks = accept;
+    return true;
 }
 inline SnfRefusal set_snf_verify(KernelSettings& ks, int32_t verify)
 {

@@ -52,7 +52,9 @@ struct Lz4Walk {
 
 // One sequence of the Java loop (w.ip < inLimit on entry); true: the walk is over (w.st says how).  A block that ends behind a match -- the decoder takes it with
 // room to spare and refuses it with exact room, :168-171 -- ends the walk with status 0: R2 holds, R1 does not speak of it.
-__device__ __forceinline__ bool lz4_size_step(const uint8_t* __restrict__ in, int32_t inLimit, Lz4Walk& w)
+// HISTORY: a block of an LZ4 frame with linked blocks (lz4frame_size_item): `history` bytes of the frame's content lie in front of it and an offset may reach them.
+template <bool HISTORY = false>
+__device__ __forceinline__ bool lz4_size_step(const uint8_t* __restrict__ in, int32_t inLimit, Lz4Walk& w, int64_t history = 0)
 {
     int32_t ip = w.ip;
     uint64_t x = 0;  // the token and the bytes behind it
@@ -90,7 +92,7 @@ __device__ __forceinline__ bool lz4_size_step(const uint8_t* __restrict__ in, in
     const uint32_t y = ld4(in + ip);  // the offset and the byte behind it (litEnd <= inLimit - 8)
     const int32_t offset = (int32_t)(y & 0xFFFF);  // :113-119
     ip += 2;
-    if (offset == 0 || (int64_t)offset > w.op) DS_LZ4_FAIL(ACHIP_D_LZ4_OFFSET_OUTSIDE, ip);
+    if (offset == 0 || (int64_t)offset > (HISTORY ? w.op + history : w.op)) DS_LZ4_FAIL(ACHIP_D_LZ4_OFFSET_OUTSIDE, ip);
     int32_t ml = token & 0xF;  // :122-138
     if (ml == 0xF) {
         if (ip > inLimit - 5) DS_LZ4_FAIL(ACHIP_D_LZ4_MALFORMED, ip);
@@ -112,7 +114,8 @@ __device__ __forceinline__ bool lz4_size_step(const uint8_t* __restrict__ in, in
 #undef DS_LZ4_FAIL
 
 // a whole block by one lane
-__device__ __forceinline__ void lz4_size_serial(const uint8_t* __restrict__ in, int32_t inLimit, int64_t& size, int32_t& st, int32_t& eo)
+template <bool HISTORY = false>
+__device__ __forceinline__ void lz4_size_serial(const uint8_t* __restrict__ in, int32_t inLimit, int64_t& size, int32_t& st, int32_t& eo, int64_t history = 0)
 {
     Lz4Walk w;
     w.ip = 0;
@@ -123,7 +126,7 @@ __device__ __forceinline__ void lz4_size_serial(const uint8_t* __restrict__ in, 
         w.st = mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_LZ4_INPUT_EMPTY);
     }
     else {
-        while (!lz4_size_step(in, inLimit, w)) {
+        while (!lz4_size_step<HISTORY>(in, inLimit, w, history)) {
         }
     }
     st = w.st;
@@ -596,6 +599,7 @@ struct ListingSizer {
         eo = 0;
         return assume;
     }
+    __device__ int64_t lz4_linked(const uint8_t* srcBase, int64_t off, int32_t len, int64_t assume, int64_t, int32_t& st, int32_t& eo) { return lz4(srcBase, off, len, assume, st, eo); }
 };
 // The fold: the stream's k-th request is its k-th entry if the listing saw the same block there; else the lane walks the block.
 struct FoldSizer {
@@ -613,6 +617,17 @@ struct FoldSizer {
         lz4_size_serial(srcBase + off, len, size, st, eo);
         return size;
     }
+    // A block of a linked frame, `history` bytes of the frame's content in front of it.  The list's walk knows no history: a block it sized passed the stricter
+    // check at every offset, so the size stands; what it refused for an offset (the first thing it met: everything in front passed) the lane walks again with the
+    // history -- which is most blocks of a real linked frame, so such frames are sized at a lane's pace (a parallel walk with histories: when their decode has one).
+    __device__ int64_t lz4_linked(const uint8_t* srcBase, int64_t off, int32_t len, int64_t assume, int64_t history, int32_t& st, int32_t& eo)
+    {
+        int64_t size = lz4(srcBase, off, len, assume, st, eo);
+        if (st == mk_status(ACHIP_CLASS_MALFORMED, ACHIP_D_LZ4_OFFSET_OUTSIDE)) {
+            lz4_size_serial<true>(srcBase + off, len, size, st, eo, history);
+        }
+        return size;
+    }
 };
 struct NoSizer {  // (the Snappy containers: the preamble is read in the loop)
     __device__ int64_t lz4(const uint8_t*, int64_t, int32_t, int64_t assume, int32_t& st, int32_t& eo)
@@ -621,6 +636,7 @@ struct NoSizer {  // (the Snappy containers: the preamble is read in the loop)
         eo = 0;
         return assume;
     }
+    __device__ int64_t lz4_linked(const uint8_t* srcBase, int64_t off, int32_t len, int64_t assume, int64_t, int32_t& st, int32_t& eo) { return lz4(srcBase, off, len, assume, st, eo); }
 };
 
 #define DS_FAIL(detail, off)                             \
@@ -631,9 +647,12 @@ struct NoSizer {  // (the Snappy containers: the preamble is read in the loop)
 
 // ---- LZ4 frames: Lz4FrameCompression.decompress / decompressFrame / skipFrame, M/lz4/Lz4FrameCompression.java:145-343, without the blocks' bodies.  A frame that
 // announces its content size decodes to that or fails (:318); any other frame is the sum of its blocks: a stored block's length, a compressed block's walk.
+// acceptLinked (SizeArgs::lz4fLinked, the context's achip_ctx_set_lz4frame_linked_blocks): frames of linked blocks are sized like any other.  The token walk reads
+// no match source, but it does compare every offset with the bytes produced so far, as the decoder does -- so a block of a linked frame is walked with the
+// frame's content in front of it as its history (FoldSizer::lz4_linked), the decoder's own bound.
 
 template <class Z>
-__device__ int32_t lz4frame_size_item(const uint8_t* __restrict__ srcBase, int64_t srcOff, int32_t inLen, Z& z, int64_t& total, int64_t& eo)
+__device__ int32_t lz4frame_size_item(const uint8_t* __restrict__ srcBase, int64_t srcOff, int32_t inLen, bool acceptLinked, Z& z, int64_t& total, int64_t& eo)
 {
     using namespace lz4f;
     const uint8_t* __restrict__ in = srcBase + srcOff;
@@ -655,7 +674,7 @@ __device__ int32_t lz4frame_size_item(const uint8_t* __restrict__ srcBase, int64
         if (magic != MAGIC) DS_FAIL(ACHIP_D_LZ4F_BAD_MAGIC, pos);
         // decompressFrame :184-322
         FrameHeader h;
-        const int32_t hst = read_frame_header(in, inLen, (int32_t)pos, h, eo);
+        const int32_t hst = read_frame_header(in, inLen, (int32_t)pos, acceptLinked, h, eo);
         if (hst != 0) {
             return hst;
         }
@@ -677,7 +696,8 @@ __device__ int32_t lz4frame_size_item(const uint8_t* __restrict__ srcBase, int64
             }
             else if (!contentSize) {
                 int32_t bst = 0, beo = 0;
-                const int64_t size = z.lz4(srcBase, srcOff + p, (int32_t)blockLen, blockMax, bst, beo);
+                const int64_t size = h.linked ? z.lz4_linked(srcBase, srcOff + p, (int32_t)blockLen, blockMax, o < 65535 ? o : 65535, bst, beo)
+                                              : z.lz4(srcBase, srcOff + p, (int32_t)blockLen, blockMax, bst, beo);
                 if (bst != 0) {  // the block codec's exception, its offset relative to the block
                     eo = (int64_t)beo;
                     return bst;
@@ -835,7 +855,7 @@ __device__ __forceinline__ int32_t container_size_item(const SizeArgs& s, int64_
 {
     const int32_t inLen = s.srcLen[stream] > 0 ? s.srcLen[stream] : 0;
     if constexpr (KIND == KIND_LZ4FRAME) {
-        return lz4frame_size_item(s.srcBase, s.srcOff[stream], inLen, z, total, eo);
+        return lz4frame_size_item(s.srcBase, s.srcOff[stream], inLen, s.lz4fLinked != 0, z, total, eo);
     }
     else if constexpr (KIND == KIND_SNAPPYFRAMED) {
         return snappyframed_size_item(s.srcBase, s.srcOff[stream], inLen, z, total, eo);

@@ -8,9 +8,16 @@ namespace achip {
 
 // `R` is initialised on (in, inLimit, out); on return st / eo hold the status and error offset, op the bytes produced
 // (the output is flushed).  All lanes of the group return the same values.
-template <int GS, int IN_RING, int OUT_RING, int GPL, int PHASED = 0>
+//
+// HISTORY (the LZ4 frame reader's blocks of a linked frame, lz4_frame.hip; every other caller has the form without): `history` bytes of the
+// same frame's content lie in memory in front of out[0], flushed by the blocks before this one, and a match may begin in them.  Two things
+// differ: the output ring starts with the nearest of those bytes in it (Rings::prime_history) instead of empty, so a near match is served
+// from LDS wherever its source lies and copy_match stays as it is -- a far one reads out[op - offset] from memory as it always did, the
+// address now possibly in front of `out`; and the bound of the offset check (:118) is op + history.  No other check moves: status, detail
+// and the block-relative offset of every failure are the plain form's.
+template <int GS, int IN_RING, int OUT_RING, int GPL, int PHASED = 0, bool HISTORY = false>
 __device__ __forceinline__ void lz4_block_decode(Rings<GS, IN_RING, OUT_RING, GPL, PHASED>& R, const uint8_t* __restrict__ in, int32_t inLimit, int32_t outLimit, int32_t& stOut,
-                                                 int32_t& eoOut, int32_t& opOut)
+                                                 int32_t& eoOut, int32_t& opOut, int32_t history = 0)
 {
     int32_t st = 0;
     int32_t eo = 0;  // 32-bit on purpose (see lz4_decompress.hip)
@@ -34,6 +41,9 @@ __device__ __forceinline__ void lz4_block_decode(Rings<GS, IN_RING, OUT_RING, GP
     }
     else {
         const int32_t fastOutLimit = outLimit - 8;
+        if constexpr (HISTORY) {
+            R.prime_history(history);
+        }
         // The 4-byte windows at the token and at the offset are read one phase early (the next token's before the match
         // copy, the offset's before the literal copy) so that they travel with that copy's own LDS reads: two dependent
         // LDS round trips fewer per sequence.
@@ -85,7 +95,7 @@ __device__ __forceinline__ void lz4_block_decode(Rings<GS, IN_RING, OUT_RING, GP
             }
             const int32_t offset = (int32_t)(o4 & 0xFFFF);  // :113-119
             ip += 2;
-            if (offset == 0 || offset > op) LZ4_FAIL(ACHIP_D_LZ4_OFFSET_OUTSIDE, ip);
+            if (offset == 0 || offset > (HISTORY ? op + history : op)) LZ4_FAIL(ACHIP_D_LZ4_OFFSET_OUTSIDE, ip);
 
             int32_t ml = token & 0xF;  // :122-138
             if (ml == 0xF) {

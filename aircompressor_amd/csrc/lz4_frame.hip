@@ -25,11 +25,19 @@ using FR = Rings<64, IN_RING, OUT_RING, 1>;
     }
 
 // decompressFrame :184-322 ; wave-uniform.  Returns 0 or the status; pos / op advance.
-__device__ int32_t decompress_frame(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* lds, int lane, int32_t& pos, int32_t& op, int64_t& eo)
+//
+// acceptLinked (achip_ctx_set_lz4frame_linked_blocks; a step beyond the Java reader, which refuses such frames): the blocks of a frame whose block-independence
+// bit is clear may look back into this frame's content, out[outStart, o) -- compressed and stored blocks alike, never a frame before it or anything in front of
+// the item.  A compressed block is told how much of it there is (at most the format's 65 535); the decoder reads it from memory (far matches, and once per
+// block into its ring: Rings::prime_history).  Those bytes were stored by this wavefront -- the ring flushes of the block before, group_copy for a stored
+// block -- and the wave_mem_order() behind either keeps the compiler from moving the next block's loads in front of them; the hardware performs a wavefront's
+// vector memory operations in the order they were issued, which is all the far matches inside one block have ever relied on.  Nothing waits for another wavefront.
+__device__ int32_t decompress_frame(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* lds, int lane, bool acceptLinked, int32_t& pos, int32_t& op,
+                                    int64_t& eo)
 {
     const int32_t outStart = op;
     FrameHeader h;
-    const int32_t hst = read_frame_header(in, inLen, pos, h, eo);
+    const int32_t hst = read_frame_header(in, inLen, pos, acceptLinked, h, eo);
     if (hst != 0) {
         return hst;
     }
@@ -60,7 +68,8 @@ __device__ int32_t decompress_frame(const uint8_t* __restrict__ in, int32_t inLe
             FR R;
             R.init(lds, lds + IN_RING, in + p, (int32_t)blockLen, out + o, lane);
             int32_t bst = 0, beo = 0, bop = 0;
-            lz4_block_decode<64, IN_RING, OUT_RING, 1>(R, in + p, (int32_t)blockLen, outCap - o, bst, beo, bop);
+            const int32_t history = !h.linked ? 0 : (o - outStart < 65535 ? o - outStart : 65535);
+            lz4_block_decode<64, IN_RING, OUT_RING, 1, 0, true>(R, in + p, (int32_t)blockLen, outCap - o, bst, beo, bop, history);
             wave_mem_order();
             if (bst != 0) {
                 if (bst == mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_LZ4_EMPTY_OUTPUT)) {
@@ -97,7 +106,7 @@ __device__ int32_t decompress_frame(const uint8_t* __restrict__ in, int32_t inLe
 }
 
 // decompress :145-177
-__device__ int32_t decompress_item(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* lds, int lane, int32_t& opOut, int64_t& eo)
+__device__ int32_t decompress_item(const uint8_t* __restrict__ in, int32_t inLen, uint8_t* out, int32_t outCap, uint8_t* lds, int lane, bool acceptLinked, int32_t& opOut, int64_t& eo)
 {
     eo = 0;
     opOut = 0;
@@ -107,7 +116,7 @@ __device__ int32_t decompress_item(const uint8_t* __restrict__ in, int32_t inLen
         if ((int64_t)pos + 4 > inLen) LZ4F_FAIL(ACHIP_D_LZ4F_TRUNC_MAGIC, pos);
         const uint32_t magic = ld4(in + pos);
         if (magic == MAGIC) {
-            const int32_t r = decompress_frame(in, inLen, out, outCap, lds, lane, pos, op, eo);
+            const int32_t r = decompress_frame(in, inLen, out, outCap, lds, lane, acceptLinked, pos, op, eo);
             if (r != 0) {
                 return r;
             }
@@ -139,7 +148,8 @@ __device__ int32_t decompress_item(const uint8_t* __restrict__ in, int32_t inLen
 //          has read back the number of blocks and their room;
 //   fold   a wavefront per item walks the frame again: compressed blocks must have decoded, all but the last to a full block; stored blocks
 //          are copied now; content checksum and content size are checked; anything else flags the item;
-//   then the kernel above runs the flagged items, and every item of any other shape, from scratch (the Java loop: same status / offset).
+//   then the kernel above runs the flagged items, and every item of any other shape, from scratch (the Java loop: same status / offset).  A frame of linked blocks
+//   is of another shape whatever the context accepts (frame_shape): its blocks are no batch of independent ones.
 namespace lz4f {
 struct BlockList : lists::ChunkBatch {  // (counters [2..3]: the entries' room, 64 bits; [8..11]: probe statistics)
     int32_t* sFirst;     // per item: first entry, -1 = not on this path
@@ -350,9 +360,9 @@ __global__ __launch_bounds__(64) void lz4frame_fold_kernel(BatchArgs a, lz4f::Bl
     }
 }
 
-// LISTED: only the items `list` flags (the list path's leftovers)
+// LISTED: only the items `list` flags (the list path's leftovers).  acceptLinked: KernelSettings::lz4fLinkedBlocks
 template <bool LISTED>
-__global__ __launch_bounds__(64) void lz4frame_decompress_kernel(BatchArgs a, int32_t* nextItem, const int32_t* __restrict__ list)
+__global__ __launch_bounds__(64) void lz4frame_decompress_kernel(BatchArgs a, int32_t* nextItem, const int32_t* __restrict__ list, int32_t acceptLinked)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[lz4f::IN_RING + lz4f::OUT_RING];
     __shared__ int32_t item;
@@ -372,7 +382,7 @@ __global__ __launch_bounds__(64) void lz4frame_decompress_kernel(BatchArgs a, in
         }
         int32_t op = 0;
         int64_t eo = 0;
-        const int32_t st = lz4f::decompress_item(a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], a.dstCap[block], lds, lane, op, eo);
+        const int32_t st = lz4f::decompress_item(a.srcBase + a.srcOff[block], a.srcLen[block], a.dstBase + a.dstOff[block], a.dstCap[block], lds, lane, acceptLinked != 0, op, eo);
         if (lane == 0) {
             a.outLen[block] = st == 0 ? op : 0;
             a.status[block] = st;
@@ -407,7 +417,7 @@ hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, vo
     const int32_t maxWaves = 256 * 16;
     const unsigned grid = (unsigned)(a.nBlocks < maxWaves ? a.nBlocks : maxWaves);
     if (!listed) {
-        hipLaunchKernelGGL(lz4frame_decompress_kernel<false>, dim3(grid), dim3(64), 0, stream, a, L.cursor, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(lz4frame_decompress_kernel<false>, dim3(grid), dim3(64), 0, stream, a, L.cursor, (const int32_t*)nullptr, (int32_t)ks.lz4fLinkedBlocks);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(lz4frame_walk_kernel, dim3((unsigned)((a.nBlocks + 63) / 64)), dim3(64), 0, stream, a, L);
@@ -418,7 +428,7 @@ hipError_t launch_lz4frame_decompress(const BatchArgs& a, hipStream_t stream, vo
     e = launch_listed_decode(L.as_batch(a, lists::CAPACITY), 0, stream, L.counters, L.counters + 8, aux, ks, want, &decoded);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lz4frame_fold_kernel, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, L, decoded ? 1 : 0);
-    hipLaunchKernelGGL(lz4frame_decompress_kernel<true>, dim3(grid), dim3(64), 0, stream, a, L.cursor, (const int32_t*)L.sSerial);
+    hipLaunchKernelGGL(lz4frame_decompress_kernel<true>, dim3(grid), dim3(64), 0, stream, a, L.cursor, (const int32_t*)L.sSerial, (int32_t)ks.lz4fLinkedBlocks);
     return hipGetLastError();
 }
 

@@ -14,12 +14,14 @@ constexpr uint32_t UNCOMPRESSED_FLAG = 0x80000000u;
 struct FrameHeader {
     int32_t blockMax;  // 64 KiB, 256 KiB, 1 MiB, 4 MiB (Lz4FrameFormat.java:58-67)
     bool blockChecksum, contentSize, contentChecksum;
+    bool linked;           // the block-independence bit is clear: a block's matches may reach into the frame's content in front of it (acceptLinked readers only)
     int64_t expectedSize;  // -1: the frame does not announce its content size
     int32_t firstBlock;    // position of the first block's length
 };
 
 // The header of the frame whose magic stands at frameStart (the caller has read it): 0, or the status of the reader's exception with its offset in eo.
-__device__ __forceinline__ int32_t read_frame_header(const uint8_t* __restrict__ in, int32_t inLen, int32_t frameStart, FrameHeader& h, int64_t& eo)
+// acceptLinked (achip_ctx_set_lz4frame_linked_blocks; nothing in the reference): a clear block-independence bit is recorded in h.linked where the Java reader throws.
+__device__ __forceinline__ int32_t read_frame_header(const uint8_t* __restrict__ in, int32_t inLen, int32_t frameStart, bool acceptLinked, FrameHeader& h, int64_t& eo)
 {
 #define LZ4F_HEAD_FAIL(detail, off)                      \
     {                                                    \
@@ -35,7 +37,8 @@ __device__ __forceinline__ int32_t read_frame_header(const uint8_t* __restrict__
     h.blockChecksum = (flg & FLG_BLOCK_CHECKSUM) != 0;
     h.contentSize = (flg & FLG_CONTENT_SIZE) != 0;
     h.contentChecksum = (flg & FLG_CONTENT_CHECKSUM) != 0;
-    if ((flg & FLG_BLOCK_INDEPENDENCE) == 0) LZ4F_HEAD_FAIL(ACHIP_D_LZ4F_LINKED_BLOCKS, dstart);
+    h.linked = (flg & FLG_BLOCK_INDEPENDENCE) == 0;
+    if (h.linked && !acceptLinked) LZ4F_HEAD_FAIL(ACHIP_D_LZ4F_LINKED_BLOCKS, dstart);
     if ((flg & FLG_DICTIONARY_ID) != 0) LZ4F_HEAD_FAIL(ACHIP_D_LZ4F_DICTIONARY, dstart);
     const int sizeId = (bd >> 4) & 7;
     if (sizeId < 4) LZ4F_HEAD_FAIL(ACHIP_D_LZ4F_BLOCK_MAX_SIZE, dstart + 1);

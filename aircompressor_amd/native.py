@@ -43,6 +43,8 @@ SIGNATURES = {
     "achip_ctx_get_stat": (_i64, [_vp, ctypes.c_char_p]),
     "achip_ctx_set_lz4_acceleration": (_i32, [_vp, _i32]),
     "achip_ctx_get_lz4_acceleration": (_i32, [_vp]),
+    "achip_ctx_set_lz4frame_linked_blocks": (_i32, [_vp, _i32]),
+    "achip_ctx_get_lz4frame_linked_blocks": (_i32, [_vp]),
     "achip_snappyframed_max_compressed_length": (_i32, [_i32]),
     "achip_snappyframed_max_compressed_length_for": (_i32, [_i32, _i32]),
     "achip_ctx_set_snappyframed_writer": (_i32, [_vp, _i32, _i32, _i64]),
@@ -258,6 +260,19 @@ class HipNative:
         if r < 0:
             raise_for_status(r)
         return r
+
+    def set_lz4frame_linked_blocks(self, accept):
+        """1: this context's LZ4 frame decodes and its LZ4FRAME size queries read frames of linked blocks (liblz4's default frames; the Java reader refuses them);
+        0 (the default): they fail with DETAIL_LZ4F_LINKED_BLOCKS.  The library checks the value: anything but 0 / 1 (or a bool) is refused"""
+        r = self.lib.achip_ctx_set_lz4frame_linked_blocks(self.ctx, int(accept))
+        if r < 0:
+            raise IllegalArgumentException(self.lib.achip_last_error().decode(), r)
+
+    def get_lz4frame_linked_blocks(self):
+        r = int(self.lib.achip_ctx_get_lz4frame_linked_blocks(self.ctx))
+        if r < 0:
+            raise_for_status(r)
+        return bool(r)
 
     def set_snappyframed_writer(self, write_checksums=True, block_size=SNF_DEFAULT_BLOCK_SIZE, min_compression_ratio=SNF_DEFAULT_MIN_RATIO):
         """SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio) for this context's x-snappy-framed encodes; the ratio

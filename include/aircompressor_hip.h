@@ -205,6 +205,26 @@ int32_t achip_ctx_set_option(achip_ctx* ctx, const char* name, int64_t value);
 #define ACHIP_LZ4_MAX_ACCELERATION 65537
 int32_t achip_ctx_set_lz4_acceleration(achip_ctx* ctx, int32_t acceleration);
 int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx);
+/* replaces nothing in the reference: Lz4FrameCompression.decompressFrame refuses a frame whose block-independence bit is clear ("LZ4 frames with linked
+ * blocks are not supported", M/lz4/Lz4FrameCompression.java:213-216) because it "cannot decode block by block".  This reader decodes a frame's blocks in
+ * order into one contiguous output, so it can: with accept = 1 such frames -- what liblz4's frame API writes at its defaults (LZ4F_blockLinked), `lz4 -BD`,
+ * python-lz4's lz4.frame.compress() -- are decoded.  A deliberate step beyond the Java reader, hence OFF by default; a property of the
+ * context, as accepting them would be of a reader object; a mixed batch's helper contexts take a copy of it.
+ * With accept = 1 a match of a linked frame's block may begin up to 65 535 bytes in front of the position being written, in the decoded content of the SAME
+ * frame (stored blocks' bytes included; never a previous frame of the item, never anything in front of the item's dstOff).  The only check that changes is
+ * the block decoder's ACHIP_D_LZ4_OFFSET_OUTSIDE (M/lz4/Lz4RawDecompressor.java:118): the offset is compared with the bytes of this frame produced so far
+ * instead of the bytes of this block; status, detail and the block-relative errOffset of that failure are the block decoder's.  Every other check of
+ * decompressFrame keeps its order, detail and offset; a frame with a dictionary ID is still ACHIP_D_LZ4F_DICTIONARY.
+ * It applies to every LZ4 frame decode the context launches: achip_lz4frame_decompress_batch, achip_lz4frame_decompress, ACHIP_OP_LZ4FRAME_DECOMPRESS inside
+ * achip_batch_host, achip_mixed_batch, achip_mixed_batch_host and achip_multi_batch_host, and that op's line of achip_decoded_size_batch (linked frames are
+ * sized instead of reported).
+ * It does NOT change: any encoder (no writer here writes linked blocks), any bound, any other reader, the Hadoop LZ4 streams (they have no frames), frames of
+ * independent blocks (same bytes, same path), or anything at all with accept = 0: every byte, status, detail and offset is then what it was without this call.
+ * set: 0, or for a value other than 0 or 1 a status of class INVALID_ARGUMENT with detail ACHIP_D_BAD_ARGUMENT -- the context keeps its value (checked
+ * before the context is looked at).
+ * get: 0 or 1, or a status for a null context. */
+int32_t achip_ctx_set_lz4frame_linked_blocks(achip_ctx* ctx, int32_t accept);
+int32_t achip_ctx_get_lz4frame_linked_blocks(achip_ctx* ctx);
 /* replaces the arguments of SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio)
  * M/snappy/SnappyFramedOutputStream.java:77-91 (newChecksumFreeBenchmarkOutputStream :65-69 is writeChecksums = 0 at the defaults) and of
  * SnappyFramedInputStream(decompressor, in, verifyChecksums)  M/snappy/SnappyFramedInputStream.java:74-79.  Properties of the context, as they are of the

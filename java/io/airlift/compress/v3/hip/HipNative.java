@@ -296,6 +296,10 @@ public final class HipNative
             MethodHandle ctxSetLz4Acceleration,
             @NativeSignature(name = "achip_ctx_get_lz4_acceleration", returnType = int.class, argumentTypes = MemorySegment.class)
             MethodHandle ctxGetLz4Acceleration,
+            @NativeSignature(name = "achip_ctx_set_lz4frame_linked_blocks", returnType = int.class, argumentTypes = {MemorySegment.class, int.class})
+            MethodHandle ctxSetLz4FrameLinkedBlocks,
+            @NativeSignature(name = "achip_ctx_get_lz4frame_linked_blocks", returnType = int.class, argumentTypes = MemorySegment.class)
+            MethodHandle ctxGetLz4FrameLinkedBlocks,
             @NativeSignature(name = "achip_ctx_set_snappyframed_writer", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, long.class})
             MethodHandle ctxSetSnappyFramedWriter,
             @NativeSignature(name = "achip_ctx_get_snappyframed_writer", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
@@ -1063,6 +1067,42 @@ public final class HipNative
             }
             throwIfError(result, 0);
             return result;
+        }
+
+        /**
+         * achip_ctx_set_lz4frame_linked_blocks: true = this context's LZ4 frame decodes (and its LZ4FRAME size queries) read frames whose block-independence
+         * bit is clear, which Lz4FrameCompression.decompressFrame refuses; false (the default) = they fail as the Java reader's do.
+         */
+        public void setLz4FrameLinkedBlocks(boolean accept)
+        {
+            int result;
+            try {
+                result = (int) HANDLES.ctxSetLz4FrameLinkedBlocks().invokeExact(handle(), accept ? 1 : 0);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /** achip_ctx_get_lz4frame_linked_blocks */
+        public boolean getLz4FrameLinkedBlocks()
+        {
+            int result;
+            try {
+                result = (int) HANDLES.ctxGetLz4FrameLinkedBlocks().invokeExact(handle());
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+            return result != 0;
         }
 
         /**

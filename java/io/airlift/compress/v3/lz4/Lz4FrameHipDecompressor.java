@@ -30,6 +30,9 @@ import static java.util.Objects.requireNonNull;
  * the same {@link MalformedInputException} (reason and offset), including those of the block decoder underneath.
  * Binding: {@code achip_lz4frame_decompress} (include/aircompressor_hip.h).
  * <p>
+ * {@code new Lz4FrameHipDecompressor(true)} goes a step beyond the Java reader: frames whose block-independence bit is clear (what liblz4's frame
+ * API writes at its defaults) are decoded instead of refused ({@code achip_ctx_set_lz4frame_linked_blocks}).
+ * <p>
  * Not thread-safe (owns one HIP stream).  For throughput use {@link io.airlift.compress.v3.hip.HipBatchCodec}.
  */
 public final class Lz4FrameHipDecompressor
@@ -44,8 +47,23 @@ public final class Lz4FrameHipDecompressor
 
     public Lz4FrameHipDecompressor(int device)
     {
+        this(device, false);
+    }
+
+    /**
+     * @param acceptLinkedBlocks true: frames of linked blocks are decoded, a block's matches reaching up to 65 535 bytes into the same frame's content
+     * in front of it; false: they raise the Java reader's "LZ4 frames with linked blocks are not supported"
+     */
+    public Lz4FrameHipDecompressor(boolean acceptLinkedBlocks)
+    {
+        this(0, acceptLinkedBlocks);
+    }
+
+    public Lz4FrameHipDecompressor(int device, boolean acceptLinkedBlocks)
+    {
         HipNative.verifyEnabled();
         this.context = new HipNative.Context(device);
+        this.context.setLz4FrameLinkedBlocks(acceptLinkedBlocks);
     }
 
     public static boolean isEnabled()

@@ -27,6 +27,18 @@ extern "C" int emu_lz4frame_serial(const uint8_t* srcBase, const int64_t* srcOff
     return achip::launch_lz4frame_decompress(a, nullptr, scratch.data(), 0, nullptr, achip::KernelSettings());
 }
 
+// the same with achip_ctx_set_lz4frame_linked_blocks(accept) (check_lz4_linked.py)
+extern "C" int emu_lz4frame_serial_linked(const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, uint8_t* dstBase, const int64_t* dstOff, const int32_t* dstCap,
+                                          int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n, int32_t accept)
+{
+    achip::BatchArgs a{srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, n, 16};
+    static std::vector<uint8_t> scratch;
+    scratch.assign(4096, 0);
+    achip::KernelSettings ks;
+    if (!achip::set_lz4f_linked_blocks(ks, accept)) return -1;
+    return achip::launch_lz4frame_decompress(a, nullptr, scratch.data(), 0, nullptr, ks);
+}
+
 // op 8: x-snappy-framed streams, 10 / 12: Hadoop LZ4 / Snappy block streams, 4: Zstd frames -- each through its wavefront-per-item kernel
 extern "C" int emu_serial(int op, int bufferSize, const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, uint8_t* dstBase, const int64_t* dstOff,
                           const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t n)

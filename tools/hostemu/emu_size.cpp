@@ -10,6 +10,14 @@ extern "C" int emu_decoded_size(int32_t op, const uint8_t* srcBase, const int64_
     const achip::SizeArgs s{srcBase, srcOff, srcLen, outSize, status, errOffset, n};
     return (int)achip::launch_decoded_size(op, s, nullptr, scratch.data());
 }
+// LZ4 frames with achip_ctx_set_lz4frame_linked_blocks(accept) (check_lz4_linked.py)
+extern "C" int emu_lz4frame_size_linked(const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t* outSize, int32_t* status, int64_t* errOffset, int32_t n, int32_t accept)
+{
+    std::vector<uint8_t> scratch((size_t)achip::decoded_size_scratch_bytes(ACHIP_OP_LZ4FRAME_DECOMPRESS, n) + 16, 0xCD);
+    achip::SizeArgs s{srcBase, srcOff, srcLen, outSize, status, errOffset, n};
+    s.lz4fLinked = accept;
+    return (int)achip::launch_decoded_size(ACHIP_OP_LZ4FRAME_DECOMPRESS, s, nullptr, scratch.data());
+}
 // the LZ4 walk in the shape the launcher would not pick for this count: shape 1 a lane per block, 2 a wavefront per block
 extern "C" int emu_lz4_size_shape(int32_t shape, const uint8_t* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t* outSize, int32_t* status, int64_t* errOffset, int32_t n)
 {
