@@ -62,6 +62,20 @@ int64_t lz4frame_compress_scratch_bytes(int32_t items, bool least)
     return 4096 + waves * lz4f::SLAB_BYTES;
 }
 
+// A kernel of either set (lz4_compress_kernels.h): the `_accel` twin with the acceleration behind the other arguments for an acceleration above 1, else the kernel
+// as it was.  LZ4K_BOTH(name, <T>) names the two.
+#define LZ4K_BOTH(name, ...) name __VA_ARGS__, name##_accel __VA_ARGS__
+template <typename Plain, typename Accel, typename... Args>
+static void launch_lz4k(Plain plain, Accel twin, int32_t acceleration, dim3 grid, dim3 block, hipStream_t stream, Args... args)
+{
+    if (acceleration > 1) {
+        hipLaunchKernelGGL(twin, grid, block, 0, stream, args..., acceleration);
+    }
+    else {
+        hipLaunchKernelGGL(plain, grid, block, 0, stream, args...);
+    }
+}
+
 hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int32_t acceleration)
 {
     if (a.nBlocks <= 0) {
@@ -74,55 +88,12 @@ hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void
     if (waves < 1) return hipErrorUnknown;  // (the caller sizes the scratch: never)
     if (waves > lz4f::MAX_WAVES) waves = lz4f::MAX_WAVES;
     const unsigned grid = (unsigned)(a.nBlocks < waves ? a.nBlocks : waves);
-    if (acceleration > 1) {
-        hipLaunchKernelGGL(lz4frame_compress_kernel_accel, dim3(grid), dim3(64), 0, stream, a, (uint8_t*)scratch + 4096, counter, acceleration);
-    }
-    else {
-        hipLaunchKernelGGL(lz4frame_compress_kernel, dim3(grid), dim3(64), 0, stream, a, (uint8_t*)scratch + 4096, counter);
-    }
+    launch_lz4k(LZ4K_BOTH(lz4frame_compress_kernel), acceleration, dim3(grid), dim3(64), stream, a, (uint8_t*)scratch + 4096, counter);
     return hipGetLastError();
 }
 
 // the two-tier kernel: from batches that fill the LDS tier on (fewer blocks: a wavefront per block, all tables in LDS); ks.lz4MemWaves, ks.lz4TierMinBlocks
 int64_t lz4_compress_scratch_bytes() { return 4096 + (int64_t)lz4t::WORKGROUPS * lz4t::MEM_WAVES_MAX * lz4c::MAX_TABLE_SIZE * 2; }
-
-// The same choices as launch_lz4_compress below, over the `_accel` kernels (ks.lz4Acceleration > 1)
-static hipError_t launch_lz4_compress_accel(const BatchArgs& a, hipStream_t stream, int variant, int32_t both, void* scratch, int64_t scratchBytes, const KernelSettings& ks)
-{
-    const int32_t accel = ks.lz4Acceleration;
-    const dim3 grid((unsigned)a.nBlocks), wave(64);
-    if (variant == 4 && ks.lz4MemWaves > 0 && a.nBlocks >= ks.lz4TierMinBlocks && scratch != nullptr && scratchBytes >= lz4_compress_scratch_bytes()) {
-        int32_t* counter = (int32_t*)scratch;
-        const hipError_t e = hipMemsetAsync(counter, 0, 64, stream);
-        if (e != hipSuccess) return e;
-        const unsigned perGroup = (unsigned)(lz4t::LDS_WAVES + ks.lz4MemWaves);
-        unsigned groups = ks.lz4TierWorkgroups > 0 ? (unsigned)ks.lz4TierWorkgroups : (unsigned)lz4t::WORKGROUPS;
-        groups = groups > (unsigned)lz4t::WORKGROUPS ? (unsigned)lz4t::WORKGROUPS : groups;
-        const unsigned need = ((unsigned)a.nBlocks + perGroup - 1) / perGroup;
-        hipLaunchKernelGGL(lz4_compress_tiers_kernel_accel, dim3(need < groups ? need : groups), dim3(64 * perGroup), 0, stream, a, both, (uint16_t*)((uint8_t*)scratch + 4096), counter, accel);
-    }
-    else if (variant == 4) {
-        hipLaunchKernelGGL(lz4_compress_mw_kernel_accel<uint16_t>, grid, wave, 0, stream, a, both, accel);
-    }
-    else if (variant == 0) {
-        hipLaunchKernelGGL(lz4_compress_kernel_accel<uint16_t>, grid, wave, 0, stream, a, both, accel);
-    }
-    else {
-        hipLaunchKernelGGL(lz4_compress_batch_kernel_accel<uint16_t>, grid, wave, 0, stream, a, both, accel);
-    }
-    if (both) {  // blocks beyond 64 KiB: the wide table
-        if (variant == 4) {
-            hipLaunchKernelGGL(lz4_compress_mw_kernel_accel<int32_t>, grid, wave, 0, stream, a, both, accel);
-        }
-        else if (variant == 0) {
-            hipLaunchKernelGGL(lz4_compress_kernel_accel<int32_t>, grid, wave, 0, stream, a, both, accel);
-        }
-        else {
-            hipLaunchKernelGGL(lz4_compress_batch_kernel_accel<int32_t>, grid, wave, 0, stream, a, both, accel);
-        }
-    }
-    return hipGetLastError();
-}
 
 hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int variant, int maxSrcLenHint, void* scratch, int64_t scratchBytes, const KernelSettings& ks)
 {
@@ -132,9 +103,9 @@ hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int varia
     // maxSrcLenHint: 0 = unknown, else the caller's promise about the largest srcLen in the batch: when it is <= 64 KiB the launch of
     // the wide-table kernel is skipped (a block that breaks the promise gets an INVALID_ARGUMENT status, not silence)
     const int32_t both = maxSrcLenHint == 0 || maxSrcLenHint > 65536;
-    if (ks.lz4Acceleration > 1) {
-        return launch_lz4_compress_accel(a, stream, variant, both, scratch, scratchBytes, ks);
-    }
+    const int32_t accel = ks.lz4Acceleration;
+    const dim3 grid((unsigned)a.nBlocks), wave(64);
+    // blocks up to 64 KiB: the narrow table
     if (variant == 4 && ks.lz4MemWaves > 0 && a.nBlocks >= ks.lz4TierMinBlocks && scratch != nullptr && scratchBytes >= lz4_compress_scratch_bytes()) {
         int32_t* counter = (int32_t*)scratch;
         const hipError_t e = hipMemsetAsync(counter, 0, 64, stream);
@@ -143,31 +114,26 @@ hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int varia
         unsigned groups = ks.lz4TierWorkgroups > 0 ? (unsigned)ks.lz4TierWorkgroups : (unsigned)lz4t::WORKGROUPS;
         groups = groups > (unsigned)lz4t::WORKGROUPS ? (unsigned)lz4t::WORKGROUPS : groups;
         const unsigned need = ((unsigned)a.nBlocks + perGroup - 1) / perGroup;
-        hipLaunchKernelGGL(lz4_compress_tiers_kernel, dim3(need < groups ? need : groups), dim3(64 * perGroup), 0, stream, a, both, (uint16_t*)((uint8_t*)scratch + 4096), counter);
-        if (both) {
-            hipLaunchKernelGGL(lz4_compress_mw_kernel<int32_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
-        }
-        return hipGetLastError();
+        launch_lz4k(LZ4K_BOTH(lz4_compress_tiers_kernel), accel, dim3(need < groups ? need : groups), dim3(64 * perGroup), stream, a, both, (uint16_t*)((uint8_t*)scratch + 4096), counter);
     }
-    if (variant == 4) {
-        hipLaunchKernelGGL(lz4_compress_mw_kernel<uint16_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
-        if (both) {
-            hipLaunchKernelGGL(lz4_compress_mw_kernel<int32_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
-        }
-        return hipGetLastError();
+    else if (variant == 4) {
+        launch_lz4k(LZ4K_BOTH(lz4_compress_mw_kernel, <uint16_t>), accel, grid, wave, stream, a, both);
     }
-    if (variant == 0) {
-        hipLaunchKernelGGL(lz4_compress_kernel<uint16_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
+    else if (variant == 0) {
+        launch_lz4k(LZ4K_BOTH(lz4_compress_kernel, <uint16_t>), accel, grid, wave, stream, a, both);
     }
     else {
-        hipLaunchKernelGGL(lz4_compress_batch_kernel<uint16_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
+        launch_lz4k(LZ4K_BOTH(lz4_compress_batch_kernel, <uint16_t>), accel, grid, wave, stream, a, both);
     }
-    if (both) {
-        if (variant == 0) {
-            hipLaunchKernelGGL(lz4_compress_kernel<int32_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
+    if (both) {  // blocks beyond 64 KiB: the wide table
+        if (variant == 4) {
+            launch_lz4k(LZ4K_BOTH(lz4_compress_mw_kernel, <int32_t>), accel, grid, wave, stream, a, both);
+        }
+        else if (variant == 0) {
+            launch_lz4k(LZ4K_BOTH(lz4_compress_kernel, <int32_t>), accel, grid, wave, stream, a, both);
         }
         else {
-            hipLaunchKernelGGL(lz4_compress_batch_kernel<int32_t>, dim3((unsigned)a.nBlocks), dim3(64), 0, stream, a, both);
+            launch_lz4k(LZ4K_BOTH(lz4_compress_batch_kernel, <int32_t>), accel, grid, wave, stream, a, both);
         }
     }
     return hipGetLastError();

@@ -28,23 +28,10 @@ __global__ __launch_bounds__(64) void LZ4K(lz4_compress_kernel)(BatchArgs a, int
     uint8_t* __restrict__ out = a.dstBase + a.dstOff[block];
     const int32_t outCap = a.dstCap[block];
 
-    int32_t st = 0;
     int32_t output = 0;
-
-    const int64_t bound = (int64_t)inLen + inLen / 255 + 16;  // :64-67
-    if ((uint32_t)inLen > 0x7E000000u) {                     // :83-85
-        st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_LZ4_MAX_INPUT);
-    }
-    else if ((int64_t)outCap < bound) {  // :87-89
-        st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_LZ4_MAX_OUTPUT);
-    }
-    else {
-        // computeTableSize :304-311
-        int32_t tableSize = inLen <= 1 ? 0 : (int32_t)((0x80000000u >> __builtin_clz((uint32_t)(inLen - 1))) << 1);
-        tableSize = tableSize < MIN_TABLE_SIZE ? MIN_TABLE_SIZE : (tableSize > MAX_TABLE_SIZE ? MAX_TABLE_SIZE : tableSize);
-        for (int i = lane; i < tableSize; i += 64) {
-            table[i] = 0;
-        }
+    const int32_t st = lz4_block_status(inLen, outCap);
+    if (st == 0) {
+        const int32_t tableSize = lz4_table_init(inLen, table, lane);
         __syncthreads();
         const int32_t mask = tableSize - 1;
 
@@ -101,31 +88,7 @@ __global__ __launch_bounds__(64) void LZ4K(lz4_compress_kernel)(BatchArgs a, int
 
                 for (;;) {  // :147-184
                     const int32_t matchLength = wave_count(in, input + MIN_MATCH, matchIndex + MIN_MATCH, matchLimit, lane);
-                    // emitMatch :209-235
-                    if (lane == 0) {
-                        lz4_write_run_length(out, tokenPos, literalLength, matchLength >= ML_MASK ? ML_MASK : (uint32_t)matchLength);
-                        const uint32_t off = (uint32_t)(input - matchIndex);
-                        out[output] = (uint8_t)off;
-                        out[output + 1] = (uint8_t)(off >> 8);
-                        if (matchLength >= ML_MASK) {
-                            int32_t o = output + 2;
-                            int32_t remaining = matchLength - ML_MASK;
-                            while (remaining >= 510) {
-                                out[o++] = 255;
-                                out[o++] = 255;
-                                remaining -= 510;
-                            }
-                            if (remaining >= 255) {
-                                out[o++] = 255;
-                                remaining -= 255;
-                            }
-                            out[o++] = (uint8_t)remaining;
-                        }
-                    }
-                    output += 2;
-                    if (matchLength >= ML_MASK) {
-                        output += 1 + (matchLength - ML_MASK) / 255;
-                    }
+                    output = lz4_emit_match(out, tokenPos, literalLength, input - matchIndex, matchLength, output, lane);
 
                     input += matchLength + MIN_MATCH;
                     anchor = input;
@@ -151,15 +114,7 @@ __global__ __launch_bounds__(64) void LZ4K(lz4_compress_kernel)(BatchArgs a, int
                 }
             } while (!done);
         }
-        {  // emitLastLiteral :269-280 (all three exits of the Java method end here)
-            const int32_t length = inputLimit - anchor;
-            if (lane == 0) {
-                lz4_write_run_length(out, output, length, 0);
-            }
-            output += lz4_run_length_size(length);
-            group_copy<64>(out + output, in + anchor, length, lane);
-            output += length;
-        }
+        output = lz4_emit_last_literals(in, out, output, anchor, inputLimit, lane);  // (all three exits of the Java method end here)
     }
 
     if (lane == 0) {

@@ -23,7 +23,7 @@
 //   * at the end of the window the table takes the latest inserted lane of every hash.
 // A window therefore costs two memory round trips (its own bytes, the candidates' surroundings) plus one LDS round trip, whatever the
 // number of sequences in it -- about five on text.  A search that runs through a whole window without a match (incompressible data:
-// the skip schedule takes over after 64 probes) is handed to the batch-probe loop below, which comes back here after its match.
+// the skip schedule takes over after 64 probes) goes on in lz4_probe_step (lz4_compress_body.h) with every lane probing, and comes back here after its match.
 #pragma once
 #include "lz4_compress_body.h"
 
@@ -33,34 +33,14 @@
 // 31 / 32 the block ends at a probe beyond matchFindLimit / behind a match, 33 a match ends beyond its window, 35 mode 2 runs off the end
 extern "C" long long g_zc_stats[128];
 #define MWC(k) do { if (lane == 0) g_zc_stats[k]++; } while (0)
+#define MWC_TRIPS(k, trips) do { const int32_t t_ = (trips); if (lane == 0 && t_ > 1) g_zc_stats[k] += t_ - 1; } while (0)  // (lz4_catch_up_mem: every trip behind the first)
 #else
 #define MWC(k)
+#define MWC_TRIPS(k, trips) (void)(trips)
 #endif
 namespace achip {
 
 namespace lz4mw {
-__device__ __forceinline__ uint32_t rl32(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t rl64(uint64_t v, int src) { return ((uint64_t)rl32((uint32_t)(v >> 32), src) << 32) | rl32((uint32_t)v, src); }
-// bits [lo, hi) of a 64-bit mask (0 <= lo, hi <= 64)
-__device__ __forceinline__ uint64_t bits(int lo, int hi)
-{
-    const uint64_t upTo = hi >= 64 ? ~0ull : ((1ull << hi) - 1ull);
-    const uint64_t below = lo >= 64 ? ~0ull : ((1ull << lo) - 1ull);
-    return upTo & ~below;
-}
-// The same for WAVE-UNIFORM lo <= hi with hi - lo <= 63 (every call site below: the masks of the replay), in one scalar instruction: `bits` compiles to a
-// dozen (two 64-bit shifts with their >= 64 cases, subtractions, selects), twice per sequence, in a kernel whose time IS its scalar instructions -- 6.0e10
-// of them against 2.1e10 vector instructions per launch on the corpus batch, one scalar unit per CU (profiles/r06_counters_lz4_compress_corpus.txt).
-__device__ __forceinline__ uint64_t sbits(int lo, int hi)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint64_t m;
-    asm("s_bfm_b64 %0, %1, %2" : "=s"(m) : "s"(hi - lo), "s"(lo));
-    return m;
-#else
-    return bits(lo, hi);
-#endif
-}
 // 8 bytes starting at byte `off` (0 .. 8) of the 16 bytes (lo, hi)
 __device__ __forceinline__ uint64_t ext64(uint64_t lo, uint64_t hi, int off)
 {
@@ -82,6 +62,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
     outCap = uni(outCap);
     int32_t st = 0;
     int32_t output = 0;
+    // (lz4_block_status' two tests, written out: through the function the two-tier kernel spilled more -- profiles/encoder_refactor_isa.txt)
     const int64_t bound = (int64_t)inLen + inLen / 255 + 16;
     if ((uint32_t)inLen > 0x7E000000u) {
         st = mk_status(ACHIP_CLASS_INVALID_ARGUMENT, ACHIP_D_LZ4_MAX_INPUT);
@@ -90,11 +71,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
         st = mk_status(ACHIP_CLASS_OUTPUT_TOO_SMALL, ACHIP_D_LZ4_MAX_OUTPUT);
     }
     else {
-        int32_t tableSize = inLen <= 1 ? 0 : (int32_t)((0x80000000u >> __builtin_clz((uint32_t)(inLen - 1))) << 1);
-        tableSize = tableSize < MIN_TABLE_SIZE ? MIN_TABLE_SIZE : (tableSize > MAX_TABLE_SIZE ? MAX_TABLE_SIZE : tableSize);
-        for (int i = lane; i < tableSize; i += 64) {
-            table[i] = 0;
-        }
+        const int32_t tableSize = lz4_table_init(inLen, table, lane);
         wave_sync();  // (the accesses of this wavefront to its table, in order; it may share its workgroup with others: lz4_compress_tiers_kernel)
         const int32_t mask = tableSize - 1;
         const int hashBits = 32 - __builtin_clz((uint32_t)mask | 1u);
@@ -108,57 +85,6 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
             pattern = lz4_probe_pattern(accel);
         }
 
-        // emitMatch :209-235 behind a literal run already in place; returns the new output position
-        auto emit_match = [&](int32_t tokenPos, int32_t literalLength, int32_t offset, int32_t matchLength) {
-            if (lane == 0) {
-                lz4_write_run_length(out, tokenPos, literalLength, matchLength >= ML_MASK ? ML_MASK : (uint32_t)matchLength);
-                out[output] = (uint8_t)offset;
-                out[output + 1] = (uint8_t)((uint32_t)offset >> 8);
-                if (matchLength >= ML_MASK) {
-                    int32_t o = output + 2;
-                    int32_t remaining = matchLength - ML_MASK;
-                    while (remaining >= 510) {
-                        out[o++] = 255;
-                        out[o++] = 255;
-                        remaining -= 510;
-                    }
-                    if (remaining >= 255) {
-                        out[o++] = 255;
-                        remaining -= 255;
-                    }
-                    out[o++] = (uint8_t)remaining;
-                }
-            }
-            output += 2;
-            if (matchLength >= ML_MASK) {
-                output += 1 + (matchLength - ML_MASK) / 255;
-            }
-        };
-
-        // the same with every argument in a vector register (see vec(), achip_device.h): returns the output position behind the match
-        auto emit_match_v = [&](int32_t tokenPos, int32_t literalLength, int32_t offset, int32_t matchLength, int32_t at) -> int32_t {
-            if (lane == 0) {
-                lz4_write_run_length(out, tokenPos, literalLength, matchLength >= ML_MASK ? ML_MASK : (uint32_t)matchLength);
-                out[at] = (uint8_t)offset;
-                out[at + 1] = (uint8_t)((uint32_t)offset >> 8);
-                if (matchLength >= ML_MASK) {
-                    int32_t o = at + 2;
-                    int32_t remaining = matchLength - ML_MASK;
-                    while (remaining >= 510) {
-                        out[o++] = 255;
-                        out[o++] = 255;
-                        remaining -= 510;
-                    }
-                    if (remaining >= 255) {
-                        out[o++] = 255;
-                        remaining -= 255;
-                    }
-                    out[o++] = (uint8_t)remaining;
-                }
-            }
-            return at + 2 + (matchLength >= ML_MASK ? 1 + (int32_t)((uint32_t)(matchLength - ML_MASK) / 255u) : 0);
-        };
-
         if (inLen >= MIN_LENGTH) {
             // mode 0: block start (position 0 is inserted, the search starts at 1); mode 1: after a match that ended at `input`;
             // mode 2: a search that has run through a window goes on (probe k0 of the search that began at scanStart comes next)
@@ -168,48 +94,12 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
             int32_t k0 = 0;
             for (;;) {
                 if (mode == 2) {
-                    // ---- the batch-probe step of lz4_compress_body.h for a search in progress: 64 probes at the positions of the skip schedule ----
-                    const int32_t k = k0 + lane;
-                    const int32_t pos = scanStart + (ACCEL ? lz4_scan_offset(k, accel) : lz4_scan_offset(k));
-                    const bool valid = pos + (ACCEL ? lz4_scan_advance(k, accel) : lz4_scan_advance(k)) <= matchFindLimit;
-                    const unsigned long long invalidMask = __ballot(!valid);
-                    const int firstInvalid = invalidMask ? __builtin_ctzll(invalidMask) : 64;
-                    const bool active = lane < firstInvalid;
-                    const unsigned long long activeMask = __ballot(active);
-                    uint64_t x = 0;
-                    int32_t h = 0;
-                    int32_t cand = 0;
-                    if (active) {
-                        x = ld8(in + pos);
-                        h = lz4_hash(x, mask);
-                        cand = (int32_t)table[h];
-                    }
-                    const unsigned long long same = wave_match_any((uint32_t)h, hashBits, activeMask);
-                    const unsigned long long earlier = same & ((1ull << lane) - 1ull);
-                    {
-                        const bool fromBatch = active && earlier != 0;
-                        const int32_t latest = __shfl(pos, fromBatch ? 63 - __builtin_clzll(earlier) : lane);
-                        if (fromBatch) {
-                            cand = latest;
-                        }
-                    }
-                    bool hit = false;
-                    if (active) {
-                        hit = ld4(in + cand) == (uint32_t)x && cand + MAX_DISTANCE >= pos;
-                    }
-                    const unsigned long long hitMask = __ballot(hit);
-                    const int winner = hitMask ? __builtin_ctzll(hitMask) : -1;
-                    const int lastWriter = winner >= 0 ? winner : firstInvalid - 1;
-                    {
-                        const unsigned long long upTo = lastWriter >= 63 ? ~0ull : ((1ull << (lastWriter + 1)) - 1ull);
-                        const unsigned long long later = same & upTo & ~((2ull << lane) - 1ull);
-                        if (active && lane <= lastWriter && later == 0) {
-                            table[h] = (TableT)pos;
-                        }
-                    }
+                    // ---- lz4_probe_step (lz4_compress_body.h) for a search in progress: every lane probes, at the skip schedule's positions from probe k0 on ----
+                    __builtin_assume(k0 >= 0);  // (a count of probes, which the compiler cannot know: without it every lane's `k >= 0` is tested)
+                    const Lz4ProbeStep s = lz4_probe_step<TableT, ACCEL>(in, table, mask, hashBits, matchFindLimit, scanStart, accel, 2, 0, k0 + lane, lane);
                     wave_sync();  // (the accesses of this wavefront to its table, in order; it may share its workgroup with others: lz4_compress_tiers_kernel)
-                    if (winner < 0) {
-                        if (firstInvalid < 64) {
+                    if (s.winner < 0) {
+                        if (s.firstInvalid < 64) {
                             MWC(35);
                             break;  // the search ran off the end: last literals from anchor
                         }
@@ -217,28 +107,15 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                         continue;
                     }
                     MWC(25);
-                    input = (int32_t)rl32((uint32_t)pos, winner);
-                    int32_t matchIndex = (int32_t)rl32((uint32_t)cand, winner);
-                    int32_t room = input - anchor < matchIndex ? input - anchor : matchIndex;  // catch up :141-144
-                    while (room > 0) {
-                        const bool eq = lane < room && in[input - 1 - lane] == in[matchIndex - 1 - lane];
-                        const unsigned long long ne = ~__ballot(eq);
-                        const int run = ne ? __builtin_ctzll(ne) : 64;
-                        input -= run;
-                        matchIndex -= run;
-                        room -= run;
-                        if (run < 64) {
-                            break;
-                        }
-                        if (room > 0) MWC(34);
-                    }
+                    input = (int32_t)rl32((uint32_t)s.pos, s.winner);
+                    int32_t matchIndex = (int32_t)rl32((uint32_t)s.cand, s.winner);
+                    MWC_TRIPS(34, lz4_catch_up_mem(in, input, matchIndex, input - anchor < matchIndex ? input - anchor : matchIndex, lane));
                     const int32_t literalLength = input - anchor;
                     const int32_t tokenPos = output;
                     const int32_t litPos = tokenPos + lz4_run_length_size(literalLength);
                     group_copy<64>(out + litPos, in + anchor, literalLength, lane);
-                    output = litPos + literalLength;
                     const int32_t matchLength = wave_count(in, input + MIN_MATCH, matchIndex + MIN_MATCH, matchLimit, lane);
-                    emit_match(tokenPos, literalLength, input - matchIndex, matchLength);
+                    output = lz4_emit_match(out, tokenPos, literalLength, input - matchIndex, matchLength, litPos + literalLength, lane);
                     input += matchLength + MIN_MATCH;
                     anchor = input;
                     if (input > matchFindLimit) {
@@ -252,21 +129,11 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                 MWC(26);
                 const int32_t base = mode == 0 ? 0 : input - 2;
                 const int32_t pos = base + lane;
-                const bool canLoad = pos + 8 <= inLen;
                 const bool canProbe = pos + 1 <= matchFindLimit;  // a search probe needs its successor inside the limit (:127-129)
                 // (ACCEL: the successor is one position on for a search's first probe and `accel` positions on behind it -- compared per step, below: two vector
                 // instructions there instead of two more lane masks held in scalar registers across the replay, which has none to spare)
-                uint64_t x = 0;
-                int32_t h = 0;
-                int32_t tc = 0;
-                if (canLoad) {
-                    x = ld8(in + pos);
-                    h = lz4_hash(x, mask);
-                    tc = (int32_t)table[h];
-                }
+                const auto [x, h, tc, same, canLoad] = window_load(in, pos, inLen, table, hashBits, [&](uint64_t v) { return lz4_hash(v, mask); });
                 const uint32_t x4 = (uint32_t)x;
-                const unsigned long long loadMask = __ballot(canLoad);
-                const unsigned long long same = wave_match_any((uint32_t)h, hashBits, loadMask) & loadMask;
                 // the 16 bytes around the table entry: [tc - 4, tc + 12) where there is room for them, else only the entry's own 4 bytes
                 // (fast == false: such a lane's match, if it wins, is measured from memory like the batch-probe encoder does)
                 const int32_t tcLo = tc >= 4 ? tc - 4 : 0;
@@ -322,6 +189,23 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                 int r = mode == 0 ? -1 : 2;     // lane of a pending re-probe (the position right behind a match), -1: none
                 bool blockDone = false;          // the search ran off the end, or a match ended beyond matchFindLimit
                 bool searchGoesOn = false;       // the window is used up in the middle of a search
+                // after a sequence that ended at `input`: the block is done (:152-155), or the replay goes on in this window -- the `input - 2` insert :157-159 and the
+                // re-probe at `input` are pending: true --, or the match ended beyond the window and the next one starts at input - 2
+                auto after_sequence = [&]() -> bool {
+                    if (input > matchFindLimit) {
+                        MWC(32);
+                        blockDone = true;
+                        return false;
+                    }
+                    const int rr = input - base;
+                    if (rr < 64) {
+                        M |= 1ull << (rr - 2);
+                        r = rr;
+                        return true;
+                    }
+                    MWC(33);
+                    return false;
+                };
                 for (;;) {
                     // ONE step finds the next match (round 6): the immediate re-probe :171-176 at lane r -- the position right behind a match, the table as the
                     // replay has left it -- is the first probing lane of the search :113-138 over the lanes behind it; its test is the search lanes' test (the
@@ -412,25 +296,14 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                             const int32_t vLit = vInput - vAnchor;  // (0 behind a re-probe's hit: the zero-literal token :181-183 is the token of an empty run)
                             const int32_t vTok = vOutput;
                             const int32_t vLitPos = vTok + (vLit >= RUN_MASK ? 2 + (int32_t)((uint32_t)(vLit - RUN_MASK) / 255u) : 1);
-                            if (pos >= vAnchor && pos < vInput) {
-                                out[vLitPos + (pos - vAnchor)] = (uint8_t)x4;
-                            }
-                            vOutput = emit_match_v(vTok, vLit, vInput - vCand, vMl, vLitPos + vLit);
+                            window_store_literals(out, vLitPos, vAnchor, vInput, pos, x4);
+                            vOutput = lz4_emit_match(out, vTok, vLit, vInput - vCand, vMl, vLitPos + vLit, lane);
                             vAnchor = vInput + vMl + MIN_MATCH;
                             input = uni(vAnchor);
-                            if (input > matchFindLimit) {  // :152-155
-                                MWC(32);
-                                blockDone = true;
-                                break;
-                            }
-                            const int rr = input - base;
-                            if (rr < 64) {
-                                M |= 1ull << (rr - 2);  // :157-159 the `input - 2` insert
-                                r = rr;
+                            if (after_sequence()) {
                                 continue;
                             }
-                            MWC(33);
-                            break;  // the match ends beyond the window: the next one starts at input - 2
+                            break;
                         }
                     }
                     // ---- every other sequence: scalar code, as before round 6 ----
@@ -506,19 +379,8 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                             }
                         }
                         if (slow && room > 0) {
-                            int32_t i2 = input - back, m2 = cand - back, room2 = room - back;
-                            while (room2 > 0) {
-                                const bool eq = lane < room2 && in[i2 - 1 - lane] == in[m2 - 1 - lane];
-                                const unsigned long long ne = ~__ballot(eq);
-                                const int run = ne ? __builtin_ctzll(ne) : 64;
-                                i2 -= run;
-                                m2 -= run;
-                                room2 -= run;
-                                if (run < 64) {
-                                    break;
-                                }
-                                if (room2 > 0) MWC(30);
-                            }
+                            int32_t i2 = input - back, m2 = cand - back;
+                            MWC_TRIPS(30, lz4_catch_up_mem(in, i2, m2, room - back, lane));
                             back = input - i2;
                         }
                         input -= back;
@@ -534,15 +396,12 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                         literalLength = input - anchor;
                         tokenPos = output;
                         const int32_t litPos = tokenPos + lz4_run_length_size(literalLength);
-                        if (pos >= anchor && pos < input) {
-                            out[litPos + (pos - anchor)] = (uint8_t)x4;
-                        }
+                        window_store_literals(out, litPos, anchor, input, pos, x4);
                         output = litPos + literalLength;
                     }
                     // count :240-267 from input + 4 against cand + 4: the first 8 bytes from registers
                     if (general) {
                         const int32_t a0 = input + MIN_MATCH, b0 = cand + MIN_MATCH;
-                        const int32_t limitLen = matchLimit - a0;  // (>= 4: input <= matchFindLimit - 1)
                         const int la = a0 - base;
                         const int lb = b0 - base;
                         // (a catch-up that went to memory may have moved both positions out of what the registers hold)
@@ -553,46 +412,25 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                         if (okA && okB) {
                             const uint64_t a8 = rl64(x, la);
                             const uint64_t b8 = jl >= 0 ? rl64(x, lb) : ext64(rLoW, rHiW, shiftW + 4 - back);
-                            const uint64_t d = a8 ^ b8;
-                            int32_t eq = d == 0 ? 8 : (int32_t)(__builtin_ctzll(d) >> 3);
-                            eq = eq < limitLen ? eq : limitLen;
-                            matchLength = eq;
-                            if (eq == 8 && limitLen > 8) {
-                                matchLength = 8 + wave_count(in, a0 + 8, b0 + 8, matchLimit, lane);
-                            }
+                            matchLength = window_count8(in, a8, b8, a0, b0, matchLimit, lane);  // (its limit is >= 4 bytes away: input <= matchFindLimit - 1)
                         }
                         else {
                             matchLength = wave_count(in, a0, b0, matchLimit, lane);
                         }
                     }
-                    emit_match(tokenPos, literalLength, input - cand, matchLength);
+                    output = lz4_emit_match(out, tokenPos, literalLength, input - cand, matchLength, output, lane);
                     input += matchLength + MIN_MATCH;
                     anchor = input;
                     vAnchor = vec(anchor);
                     vOutput = vec(output);
-                    if (input > matchFindLimit) {  // :152-155
-                        MWC(32);
-                        blockDone = true;
-                        break;
-                    }
-                    const int rr = input - base;
-                    if (rr < 64) {
-                        M |= 1ull << (rr - 2);  // :157-159 the `input - 2` insert
-                        r = rr;
+                    if (after_sequence()) {
                         continue;
                     }
-                    MWC(33);
-                    break;  // the match ends beyond the window: the next one starts at input - 2
+                    break;
                 }
                 anchor = uni(vAnchor);
                 output = uni(vOutput);
-                // the table takes the latest inserted lane of every hash
-                {
-                    const unsigned long long later = same & M & ~((2ull << lane) - 1ull);
-                    if (canLoad && ((M >> lane) & 1ull) != 0 && later == 0) {
-                        table[h] = (TableT)pos;
-                    }
-                }
+                window_commit_table(table, h, pos, canLoad, same, M, lane);  // the table takes the latest inserted lane of every hash
                 wave_sync();  // (the accesses of this wavefront to its table, in order; it may share its workgroup with others: lz4_compress_tiers_kernel)
                 if (blockDone) {
                     break;
@@ -606,15 +444,7 @@ __device__ int32_t lz4_compress_block_mw(const uint8_t* __restrict__ in, int32_t
                 mode = 1;
             }
         }
-        {  // emitLastLiteral :269-280
-            const int32_t length = inputLimit - anchor;
-            if (lane == 0) {
-                lz4_write_run_length(out, output, length, 0);
-            }
-            output += lz4_run_length_size(length);
-            group_copy<64>(out + output, in + anchor, length, lane);
-            output += length;
-        }
+        output = lz4_emit_last_literals(in, out, output, anchor, inputLimit, lane);
     }
     stOut = st;
     return output;

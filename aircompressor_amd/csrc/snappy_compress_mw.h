@@ -5,7 +5,7 @@
 // search are consecutive positions, then every second one), the copy (:186-198), the `input - 1` insert and the re-probe behind it
 // (:199-219) -- lane reads of registers; the table is only read at the start of a window and written at its end, which matters most for the
 // wavefronts whose table lives in global memory (snappy_compress.hip, two tiers): one round of table loads per window, not per sequence.
-// A search that runs through a whole window goes on in the batch-probe step (snappy_compress_body.h's, in its mode 2 form).
+// A search that runs through a whole window goes on in snappy_probe_step (snappy_compress_body.h) with every lane probing.
 #pragma once
 #include "snappy_compress_body.h"
 
@@ -24,25 +24,6 @@ extern "C" long long g_zc_stats[128];
 namespace achip {
 
 namespace snmw {
-__device__ __forceinline__ uint32_t rl32(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t rl64(uint64_t v, int src) { return ((uint64_t)rl32((uint32_t)(v >> 32), src) << 32) | rl32((uint32_t)v, src); }
-__device__ __forceinline__ uint64_t bits(int lo, int hi)
-{
-    const uint64_t upTo = hi >= 64 ? ~0ull : ((1ull << hi) - 1ull);
-    const uint64_t below = lo >= 64 ? ~0ull : ((1ull << lo) - 1ull);
-    return upTo & ~below;
-}
-// bits [lo, hi) for WAVE-UNIFORM lo <= hi with hi - lo <= 63, in one scalar instruction (lz4_compress_mw.h: these encoders' time is their scalar instructions)
-__device__ __forceinline__ uint64_t sbits(int lo, int hi)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint64_t m;
-    asm("s_bfm_b64 %0, %1, %2" : "=s"(m) : "s"(hi - lo), "s"(lo));
-    return m;
-#else
-    return bits(lo, hi);
-#endif
-}
 // the lanes of a window that a search starting at lane c probes: c .. c + 32 (its first 33 probes advance by one), then every second lane
 __device__ __forceinline__ uint64_t probe_lanes(int c)  // (wave-uniform c in 1 .. 64)
 {
@@ -91,13 +72,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
         for (int64_t blockAddress = (int64_t)subFirst * BLOCK_SIZE; blockAddress < endAddress; blockAddress += BLOCK_SIZE) {
             const uint8_t* __restrict__ in = in0 + blockAddress;
             const int32_t blockLimit = (int32_t)((inLen - blockAddress) < BLOCK_SIZE ? (inLen - blockAddress) : BLOCK_SIZE);
-            int32_t tableSize = blockLimit <= 1 ? 0 : (int32_t)((0x80000000u >> __builtin_clz((uint32_t)(blockLimit - 1))) << 1);
-            tableSize = tableSize < 256 ? 256 : (tableSize > MAX_HASH_TABLE_SIZE ? MAX_HASH_TABLE_SIZE : tableSize);
-            wave_mem_order();
-            for (int i = lane; i < tableSize; i += 64) {
-                table[i] = 0;
-            }
-            wave_mem_order();
+            const int32_t tableSize = snappy_table_init(table, blockLimit, lane);
             const int hashBits = 31 - __builtin_clz((uint32_t)tableSize);
             const int32_t shift = 32 - hashBits;
             const int32_t fastInputLimit = blockLimit - INPUT_MARGIN_BYTES;
@@ -110,56 +85,20 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                 int32_t k0 = 0;         // (mode 2) its next probe
                 for (;;) {
                     if (mode == 2) {
-                        // ---- the batch-probe step of snappy_compress_body.h for a search in progress ----
-                        const int32_t k = k0 + lane;
-                        const int32_t pos = scanStart + snappy_scan_offset(k);
-                        const bool valid = pos + ((32 + k) >> 5) <= fastInputLimit;  // the loop condition of :141
-                        const unsigned long long invalidMask = __ballot(!valid);
-                        const int firstInvalid = invalidMask ? __builtin_ctzll(invalidMask) : 64;
-                        const bool active = lane < firstInvalid;
-                        const unsigned long long activeMask = __ballot(active);
-                        uint32_t x = 0;
-                        int32_t h = 0;
-                        int32_t cand = 0;
-                        if (active) {
-                            x = ld4(in + pos);
-                            h = snappy_hash(x, shift);
-                            cand = (int32_t)table[h];
-                        }
-                        const unsigned long long same = wave_match_any14((uint32_t)h, hashBits, activeMask);
-                        const unsigned long long earlier = same & ((1ull << lane) - 1ull);
-                        {
-                            const bool fromBatch = active && earlier != 0;
-                            const int32_t latest = __shfl(pos, fromBatch ? 63 - __builtin_clzll(earlier) : lane);
-                            if (fromBatch) {
-                                cand = latest;
-                            }
-                        }
-                        bool hit = false;
-                        if (active) {
-                            hit = ld4(in + cand) == x;
-                        }
-                        const unsigned long long hitMask = __ballot(hit);
-                        const int winner = hitMask ? __builtin_ctzll(hitMask) : -1;
-                        const int lastWriter = winner >= 0 ? winner : firstInvalid - 1;
-                        {
-                            const unsigned long long upTo = lastWriter >= 63 ? ~0ull : ((1ull << (lastWriter + 1)) - 1ull);
-                            const unsigned long long later = same & upTo & ~((2ull << lane) - 1ull);
-                            if (active && lane <= lastWriter && later == 0) {
-                                table[h] = (uint16_t)pos;
-                            }
-                        }
+                        // ---- snappy_probe_step (snappy_compress_body.h) for a search in progress: every lane probes, from probe k0 of the search on ----
+                        __builtin_assume(k0 >= 0);  // (a count of probes, which the compiler cannot know: without it every lane's `k >= 0` is tested)
+                        const SnappyProbeStep s = snappy_probe_step(in, table, hashBits, shift, fastInputLimit, scanStart, 2, 0, k0 + lane, lane);
                         wave_mem_order();
-                        if (winner < 0) {
-                            if (firstInvalid < 64) {
+                        if (s.winner < 0) {
+                            if (s.firstInvalid < 64) {
                                 SNWC(49);
                                 break;  // the search ran off the end: what is left is a literal (:160-162)
                             }
                             k0 += 64;
                             continue;
                         }
-                        input = uni(__shfl(pos, winner));
-                        const int32_t candidate = uni(__shfl(cand, winner));
+                        input = uni(__shfl(s.pos, s.winner));
+                        const int32_t candidate = uni(__shfl(s.cand, s.winner));
                         const int32_t literalLength = input - nextEmit;  // :169-175
                         output += snappy_literal_header(out, output, literalLength, lane);
                         group_copy<64>(out + output, in + nextEmit, literalLength, lane);
@@ -182,18 +121,8 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                     SNWC(47);
                     const int32_t base = mode == 0 ? 0 : input - 1;
                     const int32_t pos = base + lane;
-                    const bool canLoad = pos + 8 <= blockLimit;
-                    uint64_t x = 0;
-                    int32_t h = 0;
-                    int32_t tc = 0;
-                    if (canLoad) {
-                        x = ld8(in + pos);
-                        h = snappy_hash((uint32_t)x, shift);
-                        tc = (int32_t)table[h];
-                    }
+                    const auto [x, h, tc, same, canLoad] = window_load(in, pos, blockLimit, table, hashBits, [&](uint64_t v) { return snappy_hash((uint32_t)v, shift); });
                     const uint32_t x4 = (uint32_t)x;
-                    const unsigned long long loadMask = __ballot(canLoad);
-                    const unsigned long long same = wave_match_any14((uint32_t)h, hashBits, loadMask) & loadMask;
                     // the 16 bytes at the table entry's position where the block has them (the candidate's own 4 and 12 behind them), else its 4
                     const bool fast = canLoad && tc + 16 <= blockLimit;
                     uint32_t c4 = 0;
@@ -227,6 +156,22 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                     int r = mode == 0 ? -1 : 1;                     // lane of a pending re-probe, -1: none
                     bool blockDone = false, searchGoesOn = false;
                     int32_t probesDone = 0;
+                    // after a copy that ended at `input`: the block is done (:194-196), or the replay goes on in this window -- the `input - 1` insert :203-205 and the
+                    // re-probe at `input` are pending: true --, or the copy ended beyond the window and the next one starts at input - 1
+                    auto after_copy = [&]() -> bool {
+                        if (input >= fastInputLimit) {
+                            blockDone = true;
+                            return false;
+                        }
+                        const int rr = input - base;
+                        if (rr < 64) {
+                            M |= 1ull << (rr - 1);
+                            r = rr;
+                            return true;
+                        }
+                        SNWC(51);
+                        return false;
+                    };
                     for (;;) {
                         int wl = -1;
                         int32_t cand = 0;
@@ -305,9 +250,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             if (!viaReprobe) {  // the literal before it :169-175: bytes of this window, stored from the lanes' registers
                                 const int32_t vLit = vIn - vNextEmit;
                                 vOutput += snappy_literal_header(out, vOutput, vLit, lane);
-                                if (pos >= vNextEmit && pos < vIn) {
-                                    out[vOutput + (pos - vNextEmit)] = (uint8_t)x4;
-                                }
+                                window_store_literals(out, vOutput, vNextEmit, vIn, pos, x4);
                                 vOutput += vLit;
                             }
                             const int32_t vLimitLen = blockLimit - (vIn + 4);
@@ -321,18 +264,10 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             vOutput = snappy_emit_copy(out, vOutput, vIn - vCand, vMatched, lane);
                             vNextEmit = vIn + vMatched;
                             input = uni(vNextEmit);
-                            if (input >= fastInputLimit) {  // :194-196
-                                blockDone = true;
-                                break;
-                            }
-                            const int rr = input - base;
-                            if (rr < 64) {
-                                M |= 1ull << (rr - 1);  // :203-205 the `input - 1` insert
-                                r = rr;
+                            if (after_copy()) {
                                 continue;
                             }
-                            SNWC(51);
-                            break;  // the copy ends beyond the window: the next one starts at input - 1
+                            break;
                         }
                         // ---- every other copy: scalar code, as before round 6 ----
                         nextEmit = uni(vNextEmit);
@@ -340,15 +275,12 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                         if (!viaReprobe) {  // the literal before it :169-175: bytes of this window, stored from the lanes' registers
                             const int32_t literalLength = input - nextEmit;
                             output += snappy_literal_header(out, output, literalLength, lane);
-                            if (pos >= nextEmit && pos < input) {
-                                out[output + (pos - nextEmit)] = (uint8_t)x4;
-                            }
+                            window_store_literals(out, output, nextEmit, input, pos, x4);
                             output += literalLength;
                         }
                         int32_t matched;
                         {
                             const int32_t a0 = input + 4, b0 = cand + 4;
-                            const int32_t limitLen = blockLimit - a0;
                             const int la = a0 - base, lb = b0 - base;
                             const bool okA = la < 64 && a0 + 8 <= blockLimit;
                             const bool okB = jl >= 0 ? (lb < 64 && b0 + 8 <= blockLimit) : rl32((uint32_t)fast, wl) != 0;
@@ -357,13 +289,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                             if (okA && okB) {
                                 const uint64_t a8 = rl64(x, la);
                                 const uint64_t b8 = jl >= 0 ? rl64(x, lb) : rl64(after8, wl);
-                                const uint64_t dd = a8 ^ b8;
-                                int32_t eq = dd == 0 ? 8 : (int32_t)(__builtin_ctzll(dd) >> 3);
-                                eq = eq < limitLen ? eq : limitLen;
-                                matched = 4 + eq;
-                                if (eq == 8 && limitLen > 8) {
-                                    matched = 12 + wave_count(in, a0 + 8, b0 + 8, blockLimit, lane);
-                                }
+                                matched = 4 + window_count8(in, a8, b8, a0, b0, blockLimit, lane);
                             }
                             else {
                                 matched = 4 + wave_count(in, a0, b0, blockLimit, lane);
@@ -375,28 +301,14 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                         nextEmit = input;
                         vNextEmit = vec(nextEmit);
                         vOutput = vec(output);
-                        if (input >= fastInputLimit) {  // :194-196
-                            blockDone = true;
-                            break;
-                        }
-                        const int rr = input - base;
-                        if (rr < 64) {
-                            M |= 1ull << (rr - 1);  // :203-205 the `input - 1` insert
-                            r = rr;
+                        if (after_copy()) {
                             continue;
                         }
-                        SNWC(51);
-                        break;  // the copy ends beyond the window: the next one starts at input - 1
+                        break;
                     }
                     nextEmit = uni(vNextEmit);
                     output = uni(vOutput);
-                    // the table takes the latest inserted lane of every hash
-                    {
-                        const unsigned long long later = same & M & ~((2ull << lane) - 1ull);
-                        if (canLoad && ((M >> lane) & 1ull) != 0 && later == 0) {
-                            table[h] = (uint16_t)pos;
-                        }
-                    }
+                    window_commit_table(table, h, pos, canLoad, same, M, lane);  // the table takes the latest inserted lane of every hash
                     wave_mem_order();
                     if (blockDone) {
                         break;
@@ -410,12 +322,7 @@ __device__ __forceinline__ void snappy_compress_buffer_mw(uint16_t* table, const
                     mode = 1;
                 }
             }
-            if (nextEmit < blockLimit) {  // :224-229
-                const int32_t literalLength = blockLimit - nextEmit;
-                output += snappy_literal_header(out, output, literalLength, lane);
-                group_copy<64>(out + output, in + nextEmit, literalLength, lane);
-                output += literalLength;
-            }
+            output = snappy_emit_final_literal(in, out, output, nextEmit, blockLimit, lane);
         }
     }
     stOut = st;

@@ -4,6 +4,7 @@
 // description and the reference citations.
 #pragma once
 #include "achip_device.h"
+#include "achip_enc_wave.h"  // wave_match_any, and the lane helpers of zstd_dfast_mw.h
 #include "achip_seqexec.h"  // sx::wave_scan_incl, sx::wave_bcast
 
 #ifdef ACHIP_HOST_STATS  // (CPU emulator only: which way the encoder goes -- tools/hostemu/enc_paths.py, zc_stats.py, tests/test_zstd_encoder_cases.py)
@@ -1644,18 +1645,6 @@ __device__ __forceinline__ void store_sequence(Ctx& c, int32_t literalAddress, i
     c.sequenceCount = i + 1;
 }
 
-// for every lane, the mask of lanes whose `key` (low `bits` bits) equals its own
-__device__ __forceinline__ unsigned long long zc_match_any(uint32_t key, int bits, unsigned long long active)
-{
-    unsigned long long eq = active;
-    for (int b = 0; b < bits; b++) {
-        const bool bit = (key >> b) & 1u;
-        const unsigned long long m = __ballot(bit);
-        eq &= bit ? m : ~m;
-    }
-    return eq;
-}
-
 __device__ int32_t dfast_compress_block(Ctx& c, int32_t inputAddress, int32_t inputSize)
 {
     const uint8_t* __restrict__ in = c.in;
@@ -1706,8 +1695,8 @@ __device__ int32_t dfast_compress_block(Ctx& c, int32_t inputAddress, int32_t in
             int32_t sm = act ? shortTable[sh] : 0;
             int32_t lm = act ? longTable[lh] : 0;
             const unsigned long long below = (1ull << lane) - 1ull;
-            const unsigned long long sameS = zc_match_any((uint32_t)sh, c.chainLog, actMask);
-            const unsigned long long sameL = zc_match_any((uint32_t)lh, longBits, actMask);
+            const unsigned long long sameS = wave_match_any((uint32_t)sh, c.chainLog, actMask);
+            const unsigned long long sameL = wave_match_any((uint32_t)lh, longBits, actMask);
             if (act && (sameS & below) != 0) {
                 sm = input + (63 - __builtin_clzll(sameS & below));
             }

@@ -8,7 +8,7 @@
 // consecutive positions -- the 8 bytes at the position, both hashes, both table entries as they were when the window began, 32 bytes
 // around the long table's candidate ([entry - 8, entry + 24)), 16 around the short table's ([entry - 4, entry + 12)), and the 4 bytes at
 // position + 1 - offset for both repeat offsets -- and the Java loop is replayed over those registers by wave-uniform code:
-//   * what a table says at a lane = the latest lane of the window with the same hash that the replay has inserted so far (zc_match_any
+//   * what a table says at a lane = the latest lane of the window with the same hash that the replay has inserted so far (wave_match_any
 //     masks intersected with the masks of inserted lanes, one per table), else the entry read at the window's start;
 //   * the three hit tests (:71-73 repeat offset at position + 1, :83 long, :104 short, and :109-116 the long table at position + 1 behind
 //     a short hit) are evaluated by all remaining lanes at once, the first hit is the match;
@@ -26,19 +26,7 @@
 // (ZC_STAT: zstd_compress_body.h -- CPU emulator only: how often each part of the replay runs, tools/hostemu/zc_stats.py)
 
 namespace dmw {
-__device__ __forceinline__ uint32_t rl32(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t rl64(uint64_t v, int src) { return ((uint64_t)rl32((uint32_t)(v >> 32), src) << 32) | rl32((uint32_t)v, src); }
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
-{
-    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
-}
-// bits [lo, hi) of a 64-bit mask (0 <= lo, hi <= 64; empty when hi <= lo)
-__device__ __forceinline__ uint64_t bits(int lo, int hi)
-{
-    const uint64_t upTo = hi >= 64 ? ~0ull : ((1ull << hi) - 1ull);
-    const uint64_t below = lo >= 64 ? ~0ull : ((1ull << lo) - 1ull);
-    return upTo & ~below;
-}
+// (rl32 / rl64 / shfl64 / bits / wave_match_any: achip_enc_wave.h)
 // 8 bytes from byte k (0 .. 31) of the 32 bytes r0 .. r3 (what lies beyond them reads as 0)
 __device__ __forceinline__ uint64_t ext32(uint64_t r0, uint64_t r1, uint64_t r2, uint64_t r3, int k)
 {
@@ -57,18 +45,18 @@ __device__ __forceinline__ int run_from(uint64_t E, int k, int nv)
     const int r = inv != 0 ? __builtin_ctzll(inv) : 64;
     return r < nv - k ? r : nv - k;
 }
-// zc_match_any with fewer ballots: classes by the low 9 bits of the key, then one check that every class is pure (all of its lanes have the full
+// wave_match_any with fewer ballots: classes by the low 9 bits of the key, then one check that every class is pure (all of its lanes have the full
 // key of its first lane) -- which it is unless two different hashes of a window share their low bits: then the full loop
 __device__ __forceinline__ unsigned long long match_any_fast(uint32_t key, int keyBits, unsigned long long active, bool isActive)
 {
     if (keyBits <= 9) {
-        return zc_match_any(key, keyBits, active);
+        return wave_match_any(key, keyBits, active);
     }
-    const unsigned long long eq = zc_match_any(key, 9, active);
+    const unsigned long long eq = wave_match_any(key, 9, active);
     const int leader = eq != 0 ? __builtin_ctzll(eq) : 0;
     const uint32_t leaderKey = (uint32_t)__shfl((int)key, leader);
     if (__ballot(isActive && leaderKey != key) != 0) {
-        return zc_match_any(key, keyBits, active);
+        return wave_match_any(key, keyBits, active);
     }
     return eq;
 }
