@@ -157,14 +157,46 @@ class Lz4HipDecompressor(_HipDecompressor):
         return r
 
 
+LZ4F_BLOCK_SIZES = (65536, 262144, 1048576, 4194304)
+
+
+def _check_lz4frame_writer(block_size, block_checksum, content_checksum, content_size):
+    # achip_ctx_set_lz4frame_writer's checks, in its order and with its texts
+    if block_size not in LZ4F_BLOCK_SIZES:
+        raise IllegalArgumentException("blockMaxSize must be 65536, 262144, 1048576 or 4194304")
+    for name, flag in (("blockChecksum", block_checksum), ("contentChecksum", content_checksum), ("contentSize", content_size)):
+        if flag not in (0, 1):  # (True == 1, False == 0)
+            raise IllegalArgumentException("%s must be 0 or 1" % name)
+
+
 class Lz4FrameHipCompressor(_Lz4AcceleratedCompressor):
     """Drop-in for Lz4FrameJavaCompressor (M/lz4/Lz4FrameJavaCompressor.java:26-44 -> Lz4FrameCompression.compress): one LZ4
     frame of independent 4 MiB blocks, each through the HIP block encoder, stored uncompressed when that is not smaller; with
-    `acceleration`, for Lz4FrameNativeCompressor(acceleration) (M/lz4/Lz4FrameNativeCompressor.java:37-40)."""
+    `acceleration`, for Lz4FrameNativeCompressor(acceleration) (M/lz4/Lz4FrameNativeCompressor.java:37-40).
+    block_size, block_checksum, content_checksum and content_size go a step beyond the Java writer, which writes that one shape: the frame's block-maximum
+    size (65536, 262144, 1048576 or 4194304) and the three optional fields of the format.  Properties of the object, checked before anything asks for a
+    device and handed to its context before every call -- two compressors that share a context keep their own values.  With anything but the defaults the
+    frame is written by the block-list writer, and max_compressed_length is the capacity THAT writer asks for (its blocks' worst-case places)."""
     _codec = "lz4frame"
 
+    def __init__(self, device=0, native_ctx=None, acceleration=1, block_size=4194304, block_checksum=False, content_checksum=False, content_size=False):
+        _check_lz4frame_writer(block_size, block_checksum, content_checksum, content_size)  # (before anything asks for a device)
+        super().__init__(device, native_ctx, acceleration)
+        self.block_size = int(block_size)
+        self.block_checksum, self.content_checksum, self.content_size = bool(block_checksum), bool(content_checksum), bool(content_size)
+
+    def _frame_settings(self):
+        return self.block_size, self.block_checksum, self.content_checksum, self.content_size
+
+    def _compress(self, src, dst):
+        self._native.set_lz4frame_writer(*self._frame_settings())
+        return super()._compress(src, dst)
+
     def max_compressed_length(self, uncompressed_size):
-        r = self._lib.achip_lz4frame_max_compressed_length(uncompressed_size)
+        if self._frame_settings() == (4194304, False, False, False):
+            r = self._lib.achip_lz4frame_max_compressed_length(uncompressed_size)
+        else:
+            r = self._lib.achip_lz4frame_max_compressed_length_for(uncompressed_size, *(int(v) for v in self._frame_settings()))
         if r < 0:
             raise IllegalArgumentException("uncompressedSize is negative: %d" % uncompressed_size if uncompressed_size < 0 else
                                            "Maximum compressed length exceeds Integer.MAX_VALUE for uncompressedSize: %d" % uncompressed_size)

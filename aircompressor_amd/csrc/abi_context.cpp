@@ -183,6 +183,14 @@ const char* achip_last_error(void) { return g_lastError.c_str(); }
 int32_t achip_lz4_max_compressed_length(int32_t n) { return (int32_t)achip::bound::lz4(n); }
 int32_t achip_snappy_max_compressed_length(int32_t n) { return (int32_t)achip::bound::snappy(n); }
 int32_t achip_lz4frame_max_compressed_length(int32_t n) { return int_bound(n, [&] { return achip::bound::lz4frame(n); }); }
+// what the block-list writer asks (achip_ctx_set_lz4frame_writer): the worst-case places of the frame's blocks
+int32_t achip_lz4frame_max_compressed_length_for(int32_t n, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize)
+{
+    if (n < 0) return bad_argument("uncompressedSize is negative");
+    const achip::Lz4fRefusal r = achip::check_lz4f_writer(blockMaxSize, blockChecksum, contentChecksum, contentSize);
+    if (r != achip::Lz4fRefusal::None) return bad_argument(achip::lz4f_refusal_text(r));
+    return int_bound(n, [&] { return achip::bound::lz4frame_list(n, blockMaxSize, blockChecksum, contentChecksum, contentSize); });
+}
 // stream header + per 64 KiB block a chunk header, the masked CRC and at most the block itself (a compressed chunk is kept
 // only at <= 0.85 of its block: M/snappy/SnappyFramedOutputStream.java:214)
 int32_t achip_snappyframed_max_compressed_length(int32_t n) { return int_bound(n, [&] { return achip::bound::snappyframed(n); }); }
@@ -379,6 +387,27 @@ int32_t achip_ctx_get_lz4frame_linked_blocks(achip_ctx* ctx)
 {
     if (!ctx) return bad_argument("ctx is null");
     return ctx->kernel.lz4fLinkedBlocks;
+}
+
+// The LZ4 frame writer's frame descriptor (nothing in the reference: its writer has one shape, M/lz4/Lz4FrameCompression.java:98-132): checked in the order of
+// the arguments, before the context is looked at
+int32_t achip_ctx_set_lz4frame_writer(achip_ctx* ctx, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize)
+{
+    const achip::Lz4fRefusal r = achip::check_lz4f_writer(blockMaxSize, blockChecksum, contentChecksum, contentSize);
+    if (r != achip::Lz4fRefusal::None) return bad_argument(achip::lz4f_refusal_text(r));
+    if (!ctx) return bad_argument("ctx is null");
+    achip::set_lz4f_writer(ctx->kernel, blockMaxSize, blockChecksum, contentChecksum, contentSize);
+    return 0;
+}
+
+int32_t achip_ctx_get_lz4frame_writer(achip_ctx* ctx, int32_t* blockMaxSize, int32_t* blockChecksum, int32_t* contentChecksum, int32_t* contentSize)
+{
+    if (!ctx) return bad_argument("ctx is null");
+    if (blockMaxSize) *blockMaxSize = ctx->kernel.lz4fBlockMaxSize;
+    if (blockChecksum) *blockChecksum = ctx->kernel.lz4fBlockChecksum;
+    if (contentChecksum) *contentChecksum = ctx->kernel.lz4fContentChecksum;
+    if (contentSize) *contentSize = ctx->kernel.lz4fContentSize;
+    return 0;
 }
 
 // Double.toString(v), which the reference's "%1s" prints: the shortest digits -- two at least -- that read back as v (Double.MIN_VALUE is 4.9E-324), d.d in

@@ -315,6 +315,11 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
             break;
         }
         case ACHIP_OP_LZ4FRAME_COMPRESS: {
+            if (achip::lz4f_list_writer(ctx->kernel)) {  // any frame setting but the Java writer's, or lz4frame.compress.variant 1: the block list
+                if (const int32_t r = ensure_scratch(ctx, achip::lz4frame_list_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
+                e = achip::launch_lz4frame_list_compress(a, ctx->stream.get(), ctx->scratch.get(), ctx->kernel);
+                break;
+            }
             // a slab per resident wavefront; when the device cannot give the full set the launch runs with fewer wavefronts
             if (grow_scratch_keeping_old(ctx, achip::lz4frame_compress_scratch_bytes(a.nBlocks, false)) != 0) {
                 g_lastError.clear();
@@ -557,6 +562,10 @@ int32_t achip_compress_bound_batch(achip_ctx* ctx, int32_t codecOp, const int32_
     if (!ctx) return bad_argument("ctx is null");
     if (!srcLen || !outSize || !status) return bad_argument("null array");
     HIP_TRY(hipSetDevice(ctx->device));
+    if (codecOp == ACHIP_OP_LZ4FRAME_COMPRESS && achip::lz4f_list_writer(ctx->kernel)) {  // the bound of the writer that will run
+        HIP_TRY(achip::launch_lz4frame_list_bound(srcLen, outSize, status, nBlocks, ctx->stream.get(), ctx->kernel));
+        return 0;
+    }
     HIP_TRY(achip::launch_compress_bound(codecOp, srcLen, outSize, status, nBlocks, ctx->hadoopBufferSize, ctx->stream.get(), ctx->kernel.snfBlockSize));
     return 0;
 }

@@ -30,6 +30,15 @@ __host__ __device__ inline int64_t lz4frame(int64_t n)
     const int64_t blocks = (n + (4 << 20) - 1) / (4 << 20);
     return 7 + 4 + n + 4 * blocks;
 }
+// What the block-list LZ4 frame writer (lz4_frame_writer.hip; achip_ctx_set_lz4frame_writer) asks: the worst-case places its blocks are encoded at inside the
+// destination -- header (with the content size), per block of blockMaxSize bytes its size field, the block encoder's bound and the block checksum, the end mark,
+// the content checksum.  The flags are 0 or 1.
+__host__ __device__ inline int64_t lz4frame_list(int64_t n, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize)
+{
+    const int64_t each = 4 + 4 * (int64_t)blockChecksum;
+    const int64_t rest = n % blockMaxSize;
+    return 7 + 8 * (int64_t)contentSize + (n / blockMaxSize) * (each + lz4(blockMaxSize)) + (rest > 0 ? each + lz4(rest) : 0) + 4 + 4 * (int64_t)contentChecksum;
+}
 // stream header + per block of blockSize bytes (1 .. 65536: the writer's constructor argument, M/snappy/SnappyFramedOutputStream.java:77-91) a chunk header, the
 // CRC field and at most the block itself (a compressed chunk is kept only at <= minCompressionRatio <= 1.0 of its block: :213)
 __host__ __device__ inline int64_t snappyframed(int64_t n, int32_t blockSize)

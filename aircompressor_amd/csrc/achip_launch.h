@@ -102,6 +102,11 @@ int64_t lz4frame_decompress_scratch_bytes(int32_t nItems, int variant);
 // acceleration: KernelSettings::lz4Acceleration of the context (1: the kernel as it was)
 hipError_t launch_lz4frame_compress(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int32_t acceleration = 1);
 int64_t lz4frame_compress_scratch_bytes(int32_t items, bool least);
+// the block-list writer (lz4_frame_writer.hip): what every LZ4 frame encode takes when lz4f_list_writer(ks) (achip_settings.h) -- frames by ks.lz4f*, blocks at
+// ks.lz4Acceleration; it asks bound::lz4frame_list of dstCap, which launch_lz4frame_list_bound works out per item for achip_compress_bound_batch
+hipError_t launch_lz4frame_list_compress(const BatchArgs& a, hipStream_t stream, void* scratch, const KernelSettings& ks);
+int64_t lz4frame_list_compress_scratch_bytes(int32_t nStreams);
+hipError_t launch_lz4frame_list_bound(const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks, hipStream_t stream, const KernelSettings& ks);
 hipError_t launch_snappyframed_decompress(const BatchArgs& a, hipStream_t stream, void* scratch, int variant, const AuxScratch* aux, const KernelSettings& ks);
 int64_t snappyframed_decompress_scratch_bytes(int32_t nStreams);
 // ks: the writer's constructor arguments (KernelSettings::snf*; the defaults: the stream as new SnappyFramedOutputStream(compressor, out) writes it); the readers take

@@ -40,7 +40,57 @@ struct KernelSettings {
     int snfVerifyChecksums = 1;
     int snfEncodeWorkgroups = 0;  // the block-list writer's persistent encode grid (no option; 0: 768, tools/hostemu makes it small)
     int snfListEntries = 0;  // entries of the x-snappy-framed writer's block list (no option; 0: lists::CAPACITY, tools/hostemu makes it small: streams beyond it take the serial kernel)
+    // The LZ4 frame writer's frame descriptor (no options: achip_ctx_set_lz4frame_writer -- properties of the writer object; nothing in the reference, whose writer
+    // has one shape, M/lz4/Lz4FrameCompression.java:98-132): the block-maximum size (64 KiB, 256 KiB, 1 MiB, 4 MiB: BD ids 4 .. 7) and whether a frame carries
+    // block checksums, a content checksum, its content size.  At (4 MiB, 0, 0, 0) with lz4frame.compress.variant 0 every LZ4 frame encode is the wavefront-per-frame
+    // kernel as it was; anything else takes the block-list writer (lz4_frame_writer.hip), which asks bound::lz4frame_list of dstCap.
+    int lz4fBlockMaxSize = 4 << 20;
+    int lz4fBlockChecksum = 0;
+    int lz4fContentChecksum = 0;
+    int lz4fContentSize = 0;
+    int lz4fCompressVariant = 0;   // lz4frame.compress.variant: 0 = by the settings above, 1 = the block-list writer at the default settings too
+    int lz4fEncodeWorkgroups = 0;  // the block-list writer's persistent encode grid (no option; 0: 2560, tools/hostemu makes it small)
+    int lz4fListEntries = 0;       // entries of its block list (no option; 0: lists::CAPACITY, tools/hostemu makes it small: a frame beyond it is refused)
 };
+
+// achip_ctx_set_lz4frame_writer's checks, in the order of its arguments: the block-maximum size must be one of the format's four, then each flag 0 or 1.  set_ stores
+// only what passed all four: a refused call leaves `ks` as it was.
+enum class Lz4fRefusal { None, BlockMaxSize, BlockChecksum, ContentChecksum, ContentSize };
+inline Lz4fRefusal check_lz4f_writer(int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize)
+{
+    if (blockMaxSize != 65536 && blockMaxSize != 262144 && blockMaxSize != 1048576 && blockMaxSize != 4194304) return Lz4fRefusal::BlockMaxSize;
+    if (blockChecksum != 0 && blockChecksum != 1) return Lz4fRefusal::BlockChecksum;
+    if (contentChecksum != 0 && contentChecksum != 1) return Lz4fRefusal::ContentChecksum;
+    if (contentSize != 0 && contentSize != 1) return Lz4fRefusal::ContentSize;
+    return Lz4fRefusal::None;
+}
+inline const char* lz4f_refusal_text(Lz4fRefusal r)
+{
+    switch (r) {
+        case Lz4fRefusal::BlockMaxSize: return "blockMaxSize must be 65536, 262144, 1048576 or 4194304";
+        case Lz4fRefusal::BlockChecksum: return "blockChecksum must be 0 or 1";
+        case Lz4fRefusal::ContentChecksum: return "contentChecksum must be 0 or 1";
+        case Lz4fRefusal::ContentSize: return "contentSize must be 0 or 1";
+        case Lz4fRefusal::None: break;
+    }
+    return "";
+}
+inline Lz4fRefusal set_lz4f_writer(KernelSettings& ks, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize)
+{
+    const Lz4fRefusal r = check_lz4f_writer(blockMaxSize, blockChecksum, contentChecksum, contentSize);
+    if (r == Lz4fRefusal::None) {
+        ks.lz4fBlockMaxSize = blockMaxSize;
+        ks.lz4fBlockChecksum = blockChecksum;
+        ks.lz4fContentChecksum = contentChecksum;
+        ks.lz4fContentSize = contentSize;
+    }
+    return r;
+}
+// which LZ4 frame writer a launch takes: the block list unless everything is at its default
+inline bool lz4f_list_writer(const KernelSettings& ks)
+{
+    return ks.lz4fCompressVariant != 0 || ks.lz4fBlockMaxSize != (4 << 20) || ks.lz4fBlockChecksum != 0 || ks.lz4fContentChecksum != 0 || ks.lz4fContentSize != 0;
+}
 
 // achip_ctx_set_snappyframed_writer's checks, in the order of SnappyFramedOutputStream's constructor (M/snappy/SnappyFramedOutputStream.java:83, :90): the ratio
 // (its IEEE-754 bits) must be > 0 and <= 1.0 -- NaN fails --, then the block size must be in (0, 65536], then the flag 0 or 1.  set_ stores only what passed all
@@ -239,22 +289,36 @@ inline const Option kOptions[] = {
     {"host.copy_threads", &Settings::hostCopyThreads, range(0, 64), "host.copy_threads must be in 0..64"},
 };
 
+// Options that came after that table was frozen against the parser it replaced (tests/test_options.py holds kOptions to that parser's names and values); DESIGN.md 8b
+// documents them below its table.
+inline const Option kLaterOptions[] = {
+    {"lz4frame.compress.variant", &KernelSettings::lz4fCompressVariant, range(0, 1), "lz4frame.compress.variant: 0 the writer the context's frame settings ask for (a wavefront per frame at the defaults), 1 the block-list writer at the default settings too"},
+};
+
 enum class Applied { Ok, Unknown, BadValue };
+
+// One option applied to `s`.
+inline Applied apply_option(Settings& s, const Option& o, int64_t value, const char** refusal)
+{
+    if (!o.accepted(value)) {
+        if (refusal) *refusal = o.refusal;
+        return Applied::BadValue;
+    }
+    const int64_t v = o.accepted.kind == Accepted::Flag ? (value != 0 ? 1 : 0) : value;
+    if (o.field.ctx) s.*o.field.ctx = (int)v;
+    if (o.field.wide) s.*o.field.wide = v;
+    if (o.field.kernel) s.kernel.*o.field.kernel = (int)v;
+    return Applied::Ok;
+}
 
 // Sets option `name` of `s` to `value`.  BadValue leaves `s` as it was and points `*refusal` (if given) at the option's error text.
 inline Applied apply(Settings& s, const char* name, int64_t value, const char** refusal = nullptr)
 {
     for (const Option& o : kOptions) {
-        if (strcmp(o.name, name) != 0) continue;
-        if (!o.accepted(value)) {
-            if (refusal) *refusal = o.refusal;
-            return Applied::BadValue;
-        }
-        const int64_t v = o.accepted.kind == Accepted::Flag ? (value != 0 ? 1 : 0) : value;
-        if (o.field.ctx) s.*o.field.ctx = (int)v;
-        if (o.field.wide) s.*o.field.wide = v;
-        if (o.field.kernel) s.kernel.*o.field.kernel = (int)v;
-        return Applied::Ok;
+        if (strcmp(o.name, name) == 0) return apply_option(s, o, value, refusal);
+    }
+    for (const Option& o : kLaterOptions) {
+        if (strcmp(o.name, name) == 0) return apply_option(s, o, value, refusal);
     }
     return Applied::Unknown;
 }

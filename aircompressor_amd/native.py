@@ -47,6 +47,9 @@ SIGNATURES = {
     "achip_ctx_get_lz4frame_linked_blocks": (_i32, [_vp]),
     "achip_snappyframed_max_compressed_length": (_i32, [_i32]),
     "achip_snappyframed_max_compressed_length_for": (_i32, [_i32, _i32]),
+    "achip_ctx_set_lz4frame_writer": (_i32, [_vp, _i32, _i32, _i32, _i32]),
+    "achip_ctx_get_lz4frame_writer": (_i32, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "achip_lz4frame_max_compressed_length_for": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "achip_ctx_set_snappyframed_writer": (_i32, [_vp, _i32, _i32, _i64]),
     "achip_ctx_get_snappyframed_writer": (_i32, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
     "achip_ctx_set_snappyframed_verify_checksums": (_i32, [_vp, _i32]),
@@ -159,6 +162,7 @@ def load_library():
 
 
 SNF_DEFAULT_BLOCK_SIZE = SNF_MAX_BLOCK_SIZE = 65536
+LZ4F_DEFAULT_BLOCK_MAX_SIZE = 4194304
 SNF_DEFAULT_MIN_RATIO = 0.85  # ACHIP_SNF_DEFAULT_MIN_RATIO_BITS
 
 
@@ -273,6 +277,22 @@ class HipNative:
         if r < 0:
             raise_for_status(r)
         return bool(r)
+
+    def set_lz4frame_writer(self, block_size=LZ4F_DEFAULT_BLOCK_MAX_SIZE, block_checksum=False, content_checksum=False, content_size=False):
+        """The frame descriptor of this context's LZ4 frame encodes: the block-maximum size (65536, 262144, 1048576 or 4194304) and whether a frame carries block
+        checksums, a content checksum, its content size.  Anything but (4194304, False, False, False) takes the block-list writer, which asks
+        achip_lz4frame_max_compressed_length_for of the capacity.  The library checks the values: a flag must be 0 / 1 (or a bool)"""
+        r = self.lib.achip_ctx_set_lz4frame_writer(self.ctx, int(block_size), int(block_checksum), int(content_checksum), int(content_size))
+        if r < 0:
+            raise IllegalArgumentException(self.lib.achip_last_error().decode(), r)
+
+    def get_lz4frame_writer(self):
+        """-> (block_size, block_checksum, content_checksum, content_size)"""
+        v = [_i32(0) for _ in range(4)]
+        r = self.lib.achip_ctx_get_lz4frame_writer(self.ctx, *(ctypes.byref(x) for x in v))
+        if r < 0:
+            raise_for_status(r)
+        return v[0].value, bool(v[1].value), bool(v[2].value), bool(v[3].value)
 
     def set_snappyframed_writer(self, write_checksums=True, block_size=SNF_DEFAULT_BLOCK_SIZE, min_compression_ratio=SNF_DEFAULT_MIN_RATIO):
         """SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio) for this context's x-snappy-framed encodes; the ratio

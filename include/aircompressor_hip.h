@@ -225,6 +225,33 @@ int32_t achip_ctx_get_lz4_acceleration(achip_ctx* ctx);
  * get: 0 or 1, or a status for a null context. */
 int32_t achip_ctx_set_lz4frame_linked_blocks(achip_ctx* ctx, int32_t accept);
 int32_t achip_ctx_get_lz4frame_linked_blocks(achip_ctx* ctx);
+/* replaces nothing in the reference: Lz4FrameCompression.compress writes one shape of frame -- FLG 0x60, BD 0x70: independent 4 MiB blocks, no checksum, no
+ * content size (M/lz4/Lz4FrameCompression.java:98-132) -- while its reader, and this library's, accept the whole format.  With these values the writer writes the
+ * rest: blockMaxSize is the frame's block-maximum size, one of 65536, 262144, 1048576, 4194304 (BD ids 4 .. 7); blockChecksum = 1 puts XXH32 (seed 0) of every
+ * block's data as stored behind it, contentChecksum = 1 XXH32 of the frame's content behind the end mark, contentSize = 1 the 8-byte content size into the
+ * header.  FLG = 0x60 | blockChecksum << 4 | contentSize << 3 | contentChecksum << 2; the blocks are independent, each the block encoder's bytes for that block
+ * alone at the context's acceleration, stored raw (high bit of the size field) where that is not smaller (:114-126).  A deliberate step beyond the Java writer,
+ * hence OFF unless asked for; properties of the context, as they would be of a writer object; a mixed batch's helper contexts take a copy.
+ * The defaults are (4194304, 0, 0, 0).  At the defaults -- and context option "lz4frame.compress.variant" 0 -- every byte, bound, status and kernel is what it was
+ * without these calls.  With any other value, or with that option at 1, every LZ4 frame encode of the context takes the block-list writer: a
+ * frame's blocks are encoded side by side at worst-case places INSIDE the item's destination and then moved together, so that writer asks of dstCap
+ *     7 + 8 contentSize + (n / B) (e + lz4(B)) + (n % B ? e + lz4(n % B) : 0) + 4 + 4 contentChecksum,   B = blockMaxSize, e = 4 + 4 blockChecksum,
+ *     lz4(n) = n + n / 255 + 16
+ * -- achip_lz4frame_max_compressed_length_for, and that op's line of achip_compress_bound_batch -- and refuses less with OUTPUT_TOO_SMALL /
+ * ACHIP_D_LZ4F_MAX_OUTPUT before it writes one byte of the item's destination (the Java writer's rule, "fits if the output fits", is the default writer's
+ * only).  A frame of more than 2^20 blocks is INVALID_ARGUMENT / ACHIP_D_UNSUPPORTED, a negative length INVALID_ARGUMENT / ACHIP_D_BAD_ARGUMENT.
+ * They apply to every LZ4 frame encode the context launches: achip_lz4frame_compress_batch, achip_lz4frame_compress, and ACHIP_OP_LZ4FRAME_COMPRESS inside
+ * achip_batch_host, achip_mixed_batch, achip_mixed_batch_host and achip_multi_batch_host (each context its own values).
+ * They do NOT change: the LZ4 block encoder, the Hadoop LZ4 writer, any reader, any other codec, or achip_lz4frame_max_compressed_length (Java's formula).
+ * set: 0, or a status of class INVALID_ARGUMENT with detail ACHIP_D_BAD_ARGUMENT -- the context keeps all of its values.  Checked in the order of the arguments,
+ * before the context is looked at: "blockMaxSize must be 65536, 262144, 1048576 or 4194304", then "<flag> must be 0 or 1" for the three flags.
+ * get: 0 with the values stored through the non-null pointers, or a status for a null context.
+ * achip_lz4frame_max_compressed_length_for: the formula above in 64-bit arithmetic, for every parameter set, (4194304, 0, 0, 0) included; a negative status for
+ * n < 0, for a value the setter refuses, or for a result above INT32_MAX. */
+#define ACHIP_LZ4F_DEFAULT_BLOCK_MAX_SIZE 4194304
+int32_t achip_ctx_set_lz4frame_writer(achip_ctx* ctx, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize);
+int32_t achip_ctx_get_lz4frame_writer(achip_ctx* ctx, int32_t* blockMaxSize, int32_t* blockChecksum, int32_t* contentChecksum, int32_t* contentSize);
+int32_t achip_lz4frame_max_compressed_length_for(int32_t uncompressedSize, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize);
 /* replaces the arguments of SnappyFramedOutputStream(compressor, out, writeChecksums, blockSize, minCompressionRatio)
  * M/snappy/SnappyFramedOutputStream.java:77-91 (newChecksumFreeBenchmarkOutputStream :65-69 is writeChecksums = 0 at the defaults) and of
  * SnappyFramedInputStream(decompressor, in, verifyChecksums)  M/snappy/SnappyFramedInputStream.java:74-79.  Properties of the context, as they are of the
@@ -339,7 +366,7 @@ int32_t achip_zstd_decompress(achip_ctx* ctx, const void* src, void* dst, int32_
  * Replace Lz4FrameCompression.maxCompressedLength / compress / decompress    M/lz4/Lz4FrameCompression.java:70-83, 96-140, 145-343
  * (the methods behind Lz4FrameJavaCompressor / Lz4FrameJavaDecompressor, M/lz4/Lz4FrameJavaCompressor.java:26-44) with the
  * HIP block codec underneath.  An item of the batch is a whole buffer: any number of concatenated and skippable frames on
- * decode, one frame (4 MiB independent blocks, no checksums) on encode.  Same batch arguments, result convention and
+ * decode, one frame (4 MiB independent blocks, no checksums; achip_ctx_set_lz4frame_writer: the rest of the format) on encode.  Same batch arguments, result convention and
  * asynchrony as the block codecs; errOffset carries the MalformedInputException offset. */
 int32_t achip_lz4frame_max_compressed_length(int32_t uncompressedSize);  /* negative: IllegalArgumentException */
 int32_t achip_lz4frame_decompress_batch(ACHIP_BATCH_ARGS);

@@ -140,6 +140,8 @@ public final class HipNative
             MethodHandle snappyFramedMaxCompressedLength,
             @NativeSignature(name = "achip_snappyframed_max_compressed_length_for", returnType = int.class, argumentTypes = {int.class, int.class})
             MethodHandle snappyFramedMaxCompressedLengthFor,
+            @NativeSignature(name = "achip_lz4frame_max_compressed_length_for", returnType = int.class, argumentTypes = {int.class, int.class, int.class, int.class, int.class})
+            MethodHandle lz4FrameMaxCompressedLengthFor,
             // Hadoop block streams (SURVEY 8f row 2, second half)
             @NativeSignature(name = "achip_lz4hadoop_compress", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class})
             MethodHandle lz4HadoopCompress,
@@ -300,6 +302,10 @@ public final class HipNative
             MethodHandle ctxSetLz4FrameLinkedBlocks,
             @NativeSignature(name = "achip_ctx_get_lz4frame_linked_blocks", returnType = int.class, argumentTypes = MemorySegment.class)
             MethodHandle ctxGetLz4FrameLinkedBlocks,
+            @NativeSignature(name = "achip_ctx_set_lz4frame_writer", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, int.class, int.class})
+            MethodHandle ctxSetLz4FrameWriter,
+            @NativeSignature(name = "achip_ctx_get_lz4frame_writer", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
+            MethodHandle ctxGetLz4FrameWriter,
             @NativeSignature(name = "achip_ctx_set_snappyframed_writer", returnType = int.class, argumentTypes = {MemorySegment.class, int.class, int.class, long.class})
             MethodHandle ctxSetSnappyFramedWriter,
             @NativeSignature(name = "achip_ctx_get_snappyframed_writer", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class})
@@ -632,6 +638,35 @@ public final class HipNative
     {
         try {
             int result = (int) HANDLES.snappyFramedMaxCompressedLength().invokeExact(n);
+            if (result < 0) {
+                throw new IllegalArgumentException(n < 0 ? "uncompressedSize is negative: " + n : "Maximum compressed length exceeds Integer.MAX_VALUE for uncompressedSize: " + n);
+            }
+            return result;
+        }
+        catch (RuntimeException e) {
+            throw e;
+        }
+        catch (Throwable e) {
+            throw new AssertionError("should not reach here", e);
+        }
+    }
+
+    public static final int LZ4F_DEFAULT_BLOCK_MAX_SIZE = 4194304;
+
+    /** achip_ctx_set_lz4frame_writer's check of the block-maximum size, with its text */
+    public static void verifyLz4FrameBlockMaxSize(int blockMaxSize)
+    {
+        if (blockMaxSize != 65536 && blockMaxSize != 262144 && blockMaxSize != 1048576 && blockMaxSize != 4194304) {
+            throw new IllegalArgumentException("blockMaxSize must be 65536, 262144, 1048576 or 4194304");
+        }
+    }
+
+    /** what the block-list LZ4 frame writer asks of its destination: its blocks' worst-case places (achip_lz4frame_max_compressed_length_for) */
+    public static int lz4FrameMaxCompressedLength(int n, int blockMaxSize, boolean blockChecksum, boolean contentChecksum, boolean contentSize)
+    {
+        verifyLz4FrameBlockMaxSize(blockMaxSize);
+        try {
+            int result = (int) HANDLES.lz4FrameMaxCompressedLengthFor().invokeExact(n, blockMaxSize, blockChecksum ? 1 : 0, contentChecksum ? 1 : 0, contentSize ? 1 : 0);
             if (result < 0) {
                 throw new IllegalArgumentException(n < 0 ? "uncompressedSize is negative: " + n : "Maximum compressed length exceeds Integer.MAX_VALUE for uncompressedSize: " + n);
             }
@@ -1103,6 +1138,48 @@ public final class HipNative
             }
             throwIfError(result, 0);
             return result != 0;
+        }
+
+        /**
+         * achip_ctx_set_lz4frame_writer: the frame descriptor of this context's LZ4 frame encodes -- the block-maximum size (65536, 262144, 1048576 or 4194304) and
+         * whether a frame carries block checksums, a content checksum, its content size.  Anything but (4194304, false, false, false) takes the block-list writer,
+         * which asks lz4FrameMaxCompressedLength(n, ...) of the capacity.
+         */
+        public void setLz4FrameWriter(int blockMaxSize, boolean blockChecksum, boolean contentChecksum, boolean contentSize)
+        {
+            verifyLz4FrameBlockMaxSize(blockMaxSize);
+            int result;
+            try {
+                result = (int) HANDLES.ctxSetLz4FrameWriter().invokeExact(handle(), blockMaxSize, blockChecksum ? 1 : 0, contentChecksum ? 1 : 0, contentSize ? 1 : 0);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
+            throwIfError(result, 0);
+        }
+
+        /** what achip_ctx_get_lz4frame_writer reports */
+        public record Lz4FrameWriter(int blockMaxSize, boolean blockChecksum, boolean contentChecksum, boolean contentSize) {}
+
+        /** achip_ctx_get_lz4frame_writer */
+        public Lz4FrameWriter getLz4FrameWriter()
+        {
+            try (Arena arena = Arena.ofConfined()) {
+                MemorySegment values = arena.allocate(java.lang.foreign.ValueLayout.JAVA_INT, 4);
+                int result = (int) HANDLES.ctxGetLz4FrameWriter().invokeExact(handle(), values.asSlice(0, 4), values.asSlice(4, 4), values.asSlice(8, 4), values.asSlice(12, 4));
+                throwIfError(result, 0);
+                return new Lz4FrameWriter(values.getAtIndex(java.lang.foreign.ValueLayout.JAVA_INT, 0), values.getAtIndex(java.lang.foreign.ValueLayout.JAVA_INT, 1) != 0,
+                        values.getAtIndex(java.lang.foreign.ValueLayout.JAVA_INT, 2) != 0, values.getAtIndex(java.lang.foreign.ValueLayout.JAVA_INT, 3) != 0);
+            }
+            catch (RuntimeException e) {
+                throw e;
+            }
+            catch (Throwable e) {
+                throw new AssertionError("should not reach here", e);
+            }
         }
 
         /**

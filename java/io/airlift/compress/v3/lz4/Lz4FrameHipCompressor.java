@@ -29,6 +29,10 @@ import static java.util.Objects.requireNonNull;
  * the HIP block encoder, which restates the Java encoder's greedy parse step for step.
  * Binding: {@code achip_lz4frame_compress}, {@code achip_lz4frame_max_compressed_length} (include/aircompressor_hip.h).
  * <p>
+ * The six-argument constructor goes a step beyond the Java writer, which writes that one shape: the frame's block-maximum size and the format's three optional
+ * fields ({@code achip_ctx_set_lz4frame_writer}).  Such frames are written by the block-list writer, and {@link #maxCompressedLength} is then the capacity that
+ * writer asks for ({@code achip_lz4frame_max_compressed_length_for}).
+ * <p>
  * This class is not thread-safe (it owns one HIP stream), like {@code Lz4JavaCompressor}.
  * For throughput use {@link io.airlift.compress.v3.hip.HipBatchCodec}: one call, many blocks, data resident on the device.
  */
@@ -36,6 +40,10 @@ public final class Lz4FrameHipCompressor
         implements Lz4FrameCompressor
 {
     private final HipNative.Context context;
+    private final int blockMaxSize;
+    private final boolean blockChecksum;
+    private final boolean contentChecksum;
+    private final boolean contentSize;
 
     public Lz4FrameHipCompressor()
     {
@@ -53,9 +61,26 @@ public final class Lz4FrameHipCompressor
      */
     public Lz4FrameHipCompressor(int device, int acceleration)
     {
+        this(device, acceleration, HipNative.LZ4F_DEFAULT_BLOCK_MAX_SIZE, false, false, false);
+    }
+
+    /**
+     * @param blockMaxSize the frame's block-maximum size: 65536, 262144, 1048576 or 4194304
+     * @param blockChecksum XXH32 of every block's data behind it
+     * @param contentChecksum XXH32 of the content behind the end mark
+     * @param contentSize the content size in the frame header
+     */
+    public Lz4FrameHipCompressor(int device, int acceleration, int blockMaxSize, boolean blockChecksum, boolean contentChecksum, boolean contentSize)
+    {
+        HipNative.verifyLz4FrameBlockMaxSize(blockMaxSize);  // (before anything asks for a device)
         HipNative.verifyEnabled();
         this.context = new HipNative.Context(device);
         this.context.setLz4Acceleration(acceleration);
+        this.context.setLz4FrameWriter(blockMaxSize, blockChecksum, contentChecksum, contentSize);
+        this.blockMaxSize = blockMaxSize;
+        this.blockChecksum = blockChecksum;
+        this.contentChecksum = contentChecksum;
+        this.contentSize = contentSize;
     }
 
     /** {@code new Lz4FrameNativeCompressor(acceleration)} on device 0 (a one-argument constructor is taken: it names the device) */
@@ -72,7 +97,10 @@ public final class Lz4FrameHipCompressor
     @Override
     public int maxCompressedLength(int uncompressedSize)
     {
-        return HipNative.lz4FrameMaxCompressedLength(uncompressedSize);
+        if (blockMaxSize == HipNative.LZ4F_DEFAULT_BLOCK_MAX_SIZE && !blockChecksum && !contentChecksum && !contentSize) {
+            return HipNative.lz4FrameMaxCompressedLength(uncompressedSize);
+        }
+        return HipNative.lz4FrameMaxCompressedLength(uncompressedSize, blockMaxSize, blockChecksum, contentChecksum, contentSize);
     }
 
     @Override
