@@ -19,6 +19,8 @@ from .codecs import (
     SnappyHadoopHipCompressor,
     SnappyHadoopHipDecompressor,
     SnappyFramedHipDecompressor,
+    LzoHipCompressor,
+    LzoHipDecompressor,
     SnappyHipCompressor,
     SnappyHipDecompressor,
     ZstdHipCompressor,
@@ -30,12 +32,12 @@ from .streams import (HipWindowInputStream, HipWindowOutputStream, SnappyFramedH
                       Lz4HadoopHipOutputStream, SnappyHadoopHipInputStream, SnappyHadoopHipOutputStream)
 from .xxhash import XxHash32HipHasher, XxHash64HipHasher, XxHash3HipHasher, XxHash128, HipStreamHasher, HipHashStates
 from .sharding import shard_for_rank, aggregate_throughput
-from .batch import HipBatchCodec, HipMultiContextCodec, OP_LZ4_DECOMPRESS, OP_LZ4_COMPRESS, OP_SNAPPY_DECOMPRESS, OP_SNAPPY_COMPRESS, OP_ZSTD_DECOMPRESS, OP_ZSTD_COMPRESS, OP_LZ4FRAME_DECOMPRESS, OP_LZ4FRAME_COMPRESS, OP_SNAPPYFRAMED_DECOMPRESS, OP_SNAPPYFRAMED_COMPRESS, OP_LZ4HADOOP_DECOMPRESS, OP_LZ4HADOOP_COMPRESS, OP_SNAPPYHADOOP_DECOMPRESS, OP_SNAPPYHADOOP_COMPRESS, OP_ZSTDSTREAM_COMPRESS, partition_blocks
+from .batch import HipBatchCodec, HipMultiContextCodec, OP_LZ4_DECOMPRESS, OP_LZ4_COMPRESS, OP_SNAPPY_DECOMPRESS, OP_SNAPPY_COMPRESS, OP_ZSTD_DECOMPRESS, OP_ZSTD_COMPRESS, OP_LZ4FRAME_DECOMPRESS, OP_LZ4FRAME_COMPRESS, OP_SNAPPYFRAMED_DECOMPRESS, OP_SNAPPYFRAMED_COMPRESS, OP_LZ4HADOOP_DECOMPRESS, OP_LZ4HADOOP_COMPRESS, OP_SNAPPYHADOOP_DECOMPRESS, OP_SNAPPYHADOOP_COMPRESS, OP_ZSTDSTREAM_COMPRESS, OP_LZO_DECOMPRESS, OP_LZO_COMPRESS, partition_blocks
 
 __all__ = [
     "IllegalArgumentException", "MalformedInputException", "HipUnavailableError", "HipNative", "load_library",
     "Compressor", "Decompressor", "Lz4HipCompressor", "Lz4HipDecompressor", "Lz4FrameHipCompressor", "Lz4FrameHipDecompressor", "SnappyFramedHipCompressor", "SnappyFramedHipDecompressor", "Lz4HadoopHipCompressor", "Lz4HadoopHipDecompressor", "SnappyHadoopHipCompressor", "SnappyHadoopHipDecompressor", "SnappyHipCompressor", "SnappyHipDecompressor",
     "ZstdHipCompressor", "ZstdHipDecompressor", "ZstdHipOutputStream", "ZstdHipInputStream", "HipWindowInputStream", "HipWindowOutputStream", "SnappyFramedHipInputStream",
     "SnappyFramedHipOutputStream", "Lz4HadoopHipInputStream", "Lz4HadoopHipOutputStream", "SnappyHadoopHipInputStream", "SnappyHadoopHipOutputStream", "XxHash32HipHasher", "XxHash64HipHasher", "XxHash3HipHasher", "XxHash128", "HipStreamHasher", "HipHashStates", "HipBatchCodec", "HipMultiContextCodec", "partition_blocks", "shard_for_rank", "aggregate_throughput",
-    "OP_LZ4_DECOMPRESS", "OP_LZ4_COMPRESS", "OP_SNAPPY_DECOMPRESS", "OP_SNAPPY_COMPRESS", "OP_ZSTD_DECOMPRESS", "OP_ZSTD_COMPRESS", "OP_LZ4FRAME_DECOMPRESS", "OP_LZ4FRAME_COMPRESS", "OP_SNAPPYFRAMED_DECOMPRESS", "OP_SNAPPYFRAMED_COMPRESS", "OP_LZ4HADOOP_DECOMPRESS", "OP_LZ4HADOOP_COMPRESS", "OP_SNAPPYHADOOP_DECOMPRESS", "OP_SNAPPYHADOOP_COMPRESS", "OP_ZSTDSTREAM_COMPRESS",
+    "OP_LZ4_DECOMPRESS", "OP_LZ4_COMPRESS", "OP_SNAPPY_DECOMPRESS", "OP_SNAPPY_COMPRESS", "OP_ZSTD_DECOMPRESS", "OP_ZSTD_COMPRESS", "OP_LZ4FRAME_DECOMPRESS", "OP_LZ4FRAME_COMPRESS", "OP_SNAPPYFRAMED_DECOMPRESS", "OP_SNAPPYFRAMED_COMPRESS", "OP_LZ4HADOOP_DECOMPRESS", "OP_LZ4HADOOP_COMPRESS", "OP_SNAPPYHADOOP_DECOMPRESS", "OP_SNAPPYHADOOP_COMPRESS", "OP_ZSTDSTREAM_COMPRESS", "OP_LZO_DECOMPRESS", "OP_LZO_COMPRESS", "LzoHipCompressor", "LzoHipDecompressor",
 ]

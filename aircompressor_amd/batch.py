@@ -13,6 +13,7 @@ from . import native
 from .native import HipNative
 
 OP_LZ4_DECOMPRESS, OP_LZ4_COMPRESS, OP_SNAPPY_DECOMPRESS, OP_SNAPPY_COMPRESS, OP_ZSTD_DECOMPRESS, OP_ZSTD_COMPRESS, OP_LZ4FRAME_DECOMPRESS, OP_LZ4FRAME_COMPRESS, OP_SNAPPYFRAMED_DECOMPRESS, OP_SNAPPYFRAMED_COMPRESS, OP_LZ4HADOOP_DECOMPRESS, OP_LZ4HADOOP_COMPRESS, OP_SNAPPYHADOOP_DECOMPRESS, OP_SNAPPYHADOOP_COMPRESS, OP_ZSTDSTREAM_COMPRESS = range(15)
+OP_LZO_DECOMPRESS, OP_LZO_COMPRESS = 16, 17  # (15 is no op: even ops decode, odd ops encode)
 _FN = {
     OP_LZ4_DECOMPRESS: "achip_lz4_decompress_batch",
     OP_LZ4_COMPRESS: "achip_lz4_compress_batch",
@@ -29,6 +30,8 @@ _FN = {
     OP_SNAPPYHADOOP_DECOMPRESS: "achip_snappyhadoop_decompress_batch",
     OP_SNAPPYHADOOP_COMPRESS: "achip_snappyhadoop_compress_batch",
     OP_ZSTDSTREAM_COMPRESS: "achip_zstdstream_compress_batch",
+    OP_LZO_DECOMPRESS: "achip_lzo_decompress_batch",
+    OP_LZO_COMPRESS: "achip_lzo_compress_batch",
 }
 
 

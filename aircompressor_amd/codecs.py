@@ -350,6 +350,20 @@ class SnappyHipDecompressor(_HipDecompressor):
         return int(r)
 
 
+class LzoHipCompressor(_HipCompressor):
+    """Drop-in for LzoCompressor (M/lzo/LzoCompressor.java:32-91 -> LzoRawCompressor.compress): the same LZO1X bytes."""
+    _codec = "lzo"
+
+    def get_retained_size_in_bytes(self, input_length):
+        return 4096  # MAX_TABLE_SIZE  M/lzo/LzoCompressor.java:76-79
+
+
+class LzoHipDecompressor(_HipDecompressor):
+    """Drop-in for LzoDecompressor (M/lzo/LzoDecompressor.java:29-86 -> LzoRawDecompressor.decompress): any number of concatenated LZO1X blocks; every
+    failure, a destination that is too small included, is a MalformedInputException with the Java offset."""
+    _codec = "lzo"
+
+
 class ZstdHipCompressor(_HipCompressor):
     """Drop-in for ZstdJavaCompressor (always level 3; M/zstd/ZstdJavaCompressor.java:28-90)."""
     _codec = "zstd"

@@ -60,6 +60,9 @@ const DetailText kDetailText[] = {
     {ACHIP_D_LZ4_EMPTY_OUTPUT, "Output buffer too small"},
     {ACHIP_D_LZ4_MAX_INPUT, "Max input length exceeded"},
     {ACHIP_D_LZ4_MAX_OUTPUT, "Max output length must be larger than the LZ4 bound"},
+    {ACHIP_D_LZO_MALFORMED, "Malformed input"},
+    {ACHIP_D_LZO_MAX_INPUT, "Max input length exceeded"},
+    {ACHIP_D_LZO_MAX_OUTPUT, "Max output length must be larger than the LZO bound"},
     {ACHIP_D_LZ4F_TOO_SHORT, "Input is too short to be an LZ4 frame"},
     {ACHIP_D_LZ4F_TRUNC_MAGIC, "Truncated LZ4 frame: incomplete magic number"},
     {ACHIP_D_LZ4F_BAD_MAGIC, "Invalid LZ4 frame magic number"},
@@ -182,6 +185,7 @@ const char* achip_last_error(void) { return g_lastError.c_str(); }
 // ---- size helpers (the formulas: achip_bounds.h, which the bound kernel of achip_compress_bound_batch calls too) ----
 int32_t achip_lz4_max_compressed_length(int32_t n) { return (int32_t)achip::bound::lz4(n); }
 int32_t achip_snappy_max_compressed_length(int32_t n) { return (int32_t)achip::bound::snappy(n); }
+int32_t achip_lzo_max_compressed_length(int32_t n) { return (int32_t)achip::bound::lzo(n); }
 int32_t achip_lz4frame_max_compressed_length(int32_t n) { return int_bound(n, [&] { return achip::bound::lz4frame(n); }); }
 // what the block-list writer asks (achip_ctx_set_lz4frame_writer): the worst-case places of the frame's blocks
 int32_t achip_lz4frame_max_compressed_length_for(int32_t n, int32_t blockMaxSize, int32_t blockChecksum, int32_t contentChecksum, int32_t contentSize)
@@ -527,6 +531,12 @@ int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name)
         if (!ctx->lastTwopass || ctx->scratch.get() == nullptr) return -1;
         int32_t v[3] = {0, 0, 0};
         return read_scratch(ctx, ctx->lastLz4dAuto ? 4096 : 0, v, 3) ? v[2] : -1;
+    }
+    if (k == "lzo.decompress.fallback_blocks") {  // items of the last LZO decode whose records did not fit the arena: the wavefront decoder took them (-1: the last launch was no LZO decode)
+        if (ctx->lastLzod == 0) return -1;
+        if (ctx->lastLzod == 2 || ctx->scratch.get() == nullptr) return 0;
+        int32_t v[3] = {0, 0, 0};
+        return read_scratch(ctx, 0, v, 3) ? v[2] : -1;
     }
     if (k == "zstd.decompress.multiblock_items" || k == "zstd.decompress.multiblock_blocks" || k == "zstd.decompress.multiblock_fast_items") {
         // the last Zstd decode: items K1 handed to the multi-block stages, their blocks, items those stages finished

@@ -249,6 +249,7 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
     ctx->lastLz4dAuto = false;
     ctx->lastTwopass = false;
     ctx->lastRemembered = -1;
+    ctx->lastLzod = 0;
     switch (op) {
         case ACHIP_OP_LZ4_DECOMPRESS: return launch_block_decode(ctx, a, 0, ctx->lz4dVariant, ctx->lz4dGroup);
         case ACHIP_OP_SNAPPY_DECOMPRESS: return launch_block_decode(ctx, a, 1, ctx->snappydVariant, ctx->snappydGroup);
@@ -341,6 +342,25 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
             e = achip::launch_zstd_compress(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes, ctx->zstdcVariant);
             break;
         }
+        case ACHIP_OP_LZO_DECOMPRESS: {
+            // auto: batches below lzo.decompress.auto_min_blocks (and the `only` lists and device-counted batches no caller has for this op) run a wavefront per
+            // item -- nothing hides a lane's serial walk when there are not items for every lane of the chip --, larger ones the two passes.  The line (8 192) is
+            // from profiles/lzo_rate.txt: the two passes cost the same 16 .. 19 ms of a text batch whatever its count, the wavefront decoder 12.5 ms at 4 096 blocks and 34.5 at 16 384
+            const bool twopass = ctx->lzodVariant == 1 || (ctx->lzodVariant == 0 && a.nBlocks >= ctx->lzodAutoMinBlocks);
+            if (twopass) {
+                const int32_t r = ensure_twopass_scratch(ctx, 0, a.nBlocks, achip::LZ4_RECORD_BYTES_PER_BLOCK, achip::LZ4_RECORD_BYTES_PER_BLOCK_MIN);
+                if (r < 0) return r;
+                if (r > 0) {
+                    ctx->lastLzod = 1;
+                    e = achip::launch_lzo_decompress_twopass(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes, ctx->lzodMaxChunks);
+                    break;
+                }
+            }
+            ctx->lastLzod = 2;
+            e = achip::launch_lzo_decompress_wave(a, ctx->stream.get());
+            break;
+        }
+        case ACHIP_OP_LZO_COMPRESS: e = achip::launch_lzo_compress(a, ctx->stream.get()); break;
         default: return bad_argument("unknown codecOp");
     }
     if (e != hipSuccess) {
@@ -375,6 +395,8 @@ ACHIP_DEFINE_BATCH(achip_lz4hadoop_compress_batch, ACHIP_OP_LZ4HADOOP_COMPRESS)
 ACHIP_DEFINE_BATCH(achip_snappyhadoop_decompress_batch, ACHIP_OP_SNAPPYHADOOP_DECOMPRESS)
 ACHIP_DEFINE_BATCH(achip_snappyhadoop_compress_batch, ACHIP_OP_SNAPPYHADOOP_COMPRESS)
 ACHIP_DEFINE_BATCH(achip_zstdstream_compress_batch, ACHIP_OP_ZSTDSTREAM_COMPRESS)
+ACHIP_DEFINE_BATCH(achip_lzo_decompress_batch, ACHIP_OP_LZO_DECOMPRESS)
+ACHIP_DEFINE_BATCH(achip_lzo_compress_batch, ACHIP_OP_LZO_COMPRESS)
 
 // ---- mixed batch: bucket by codec op, run every op over its slice, un-bucket (BASELINE configs[4]) ----
 namespace {
@@ -397,8 +419,8 @@ constexpr int kMixFamilies = 3;
 // LZ4 (block, frame, Hadoop), Snappy (block, framed, Hadoop), Zstd (frame, stream): aircompressor_hip.h's ACHIP_OP_* in pairs
 int op_family(int op)
 {
-    static const int family[8] = {0, 1, 2, 0, 1, 0, 1, 2};  // LZ4, Snappy, Zstd, LZ4 frame, x-snappy-framed, LZ4 Hadoop, Snappy Hadoop, Zstd stream
-    return family[(op >> 1) & 7];
+    static const int family[9] = {0, 1, 2, 0, 1, 0, 1, 2, 0};  // LZ4, Snappy, Zstd, LZ4 frame, x-snappy-framed, LZ4 Hadoop, Snappy Hadoop, Zstd stream, LZO (rides with LZ4's)
+    return family[op >> 1];
 }
 bool op_is_encoder(int op) { return (op & 1) != 0 || op == ACHIP_OP_ZSTDSTREAM_COMPRESS; }  // (aircompressor_hip.h: ACHIP_OP_*_COMPRESS are the odd ops, and the last one)
 // the helper context codec family `op` (1, 2) of a mixed batch runs on: made at first use, this context's options at every use
@@ -427,7 +449,7 @@ int32_t achip_mixed_batch(achip_ctx* ctx, const int32_t* codecOp, const void* sr
     const int64_t n = nBlocks;
     int64_t count[kNumOps + 1] = {0};
     for (int64_t i = 0; i < n; i++) {
-        if (codecOp[i] < 0 || codecOp[i] >= kNumOps) return bad_argument("codecOp out of range");
+        if (!op_known(codecOp[i])) return bad_argument("codecOp out of range");
         count[codecOp[i] + 1]++;
     }
     int32_t r = ensure_mix(ctx, n);
@@ -519,6 +541,7 @@ int32_t sizing_scratch(achip_ctx* ctx, int64_t bytes)
     ctx->lastLz4dAuto = false;
     ctx->lastRemembered = -1;
     ctx->lastZstddBlocks = 0;
+    ctx->lastLzod = 0;
     return ensure_scratch(ctx, bytes);
 }
 }  // namespace
@@ -527,7 +550,7 @@ int32_t sizing_scratch(achip_ctx* ctx, int64_t bytes)
 int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t* outSize, int32_t* status,
                                  int64_t* errOffset, int32_t nBlocks)
 {
-    if (codecOp < 0 || codecOp >= kNumOps || op_is_encoder(codecOp)) return bad_argument("codecOp is not a decode op");
+    if (!op_known(codecOp) || op_is_encoder(codecOp)) return bad_argument("codecOp is not a decode op");
     if (nBlocks < 0) return bad_argument("nBlocks < 0");
     if (nBlocks == 0) return 0;
     if (!ctx) return bad_argument("ctx is null");
@@ -556,7 +579,7 @@ int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t
 // ---- compress bounds and the dense copy of a compressed batch (pack_outputs.hip) ----
 int32_t achip_compress_bound_batch(achip_ctx* ctx, int32_t codecOp, const int32_t* srcLen, int64_t* outSize, int32_t* status, int32_t nBlocks)
 {
-    if (codecOp < 0 || codecOp >= kNumOps || !op_is_encoder(codecOp)) return bad_argument("codecOp is not a compress op");
+    if (!op_known(codecOp) || !op_is_encoder(codecOp)) return bad_argument("codecOp is not a compress op");
     if (nBlocks < 0) return bad_argument("nBlocks < 0");
     if (nBlocks == 0) return 0;
     if (!ctx) return bad_argument("ctx is null");

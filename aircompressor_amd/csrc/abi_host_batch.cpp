@@ -373,7 +373,7 @@ int32_t achip_batch_host(int32_t codecOp, ACHIP_BATCH_ARGS)
     if (!ctx) return bad_argument("ctx is null");
     if (nBlocks < 0) return bad_argument("nBlocks < 0");
     if (nBlocks == 0) return 0;
-    if (codecOp < 0 || codecOp >= kNumOps) return bad_argument("unknown codecOp");
+    if (!op_known(codecOp)) return bad_argument("unknown codecOp");
     if (!srcOff || !srcLen || !dstOff || !dstCap || !outLen || !status) return bad_argument("null metadata array");
     return host_batch(ctx, codecOp, nullptr, nullptr, srcBase, srcOff, srcLen, dstBase, dstOff, dstCap, outLen, status, errOffset, nBlocks);
 }
@@ -389,7 +389,7 @@ int32_t achip_mixed_batch_host(achip_ctx* ctx, const int32_t* codecOp, const voi
     std::vector<int32_t> order((size_t)nBlocks);
     int64_t start[kNumOps + 1] = {0};
     for (int32_t i = 0; i < nBlocks; i++) {
-        if (codecOp[i] < 0 || codecOp[i] >= kNumOps) return bad_argument("codecOp out of range");
+        if (!op_known(codecOp[i])) return bad_argument("codecOp out of range");
         start[codecOp[i] + 1]++;
     }
     for (int k = 0; k < kNumOps; k++) start[k + 1] += start[k];
@@ -430,6 +430,8 @@ ACHIP_DEFINE_SINGLE(achip_lz4hadoop_compress, ACHIP_OP_LZ4HADOOP_COMPRESS)
 ACHIP_DEFINE_SINGLE(achip_snappyhadoop_decompress, ACHIP_OP_SNAPPYHADOOP_DECOMPRESS)
 ACHIP_DEFINE_SINGLE(achip_snappyhadoop_compress, ACHIP_OP_SNAPPYHADOOP_COMPRESS)
 ACHIP_DEFINE_SINGLE(achip_zstdstream_compress, ACHIP_OP_ZSTDSTREAM_COMPRESS)
+ACHIP_DEFINE_SINGLE(achip_lzo_decompress, ACHIP_OP_LZO_DECOMPRESS)
+ACHIP_DEFINE_SINGLE(achip_lzo_compress, ACHIP_OP_LZO_COMPRESS)
 
 // ---- one process, several contexts (normally one per device), one host thread each -------------------------------------------
 // The native twin of java/.../HipBatchCodec.run: the batch is cut into nCtx contiguous slices balanced by srcLen + dstCap (the rule of
@@ -448,7 +450,7 @@ int32_t achip_multi_batch_host(achip_ctx* const* ctxs, int32_t nCtx, int32_t cod
         }
     }
     if (nBlocks < 0) return bad_argument("nBlocks < 0");
-    if (!codecOps && (codecOp < 0 || codecOp >= kNumOps)) return bad_argument("unknown codecOp");
+    if (!codecOps && !op_known(codecOp)) return bad_argument("unknown codecOp");
     std::vector<int32_t> starts((size_t)nCtx + 1, 0);
     if (nBlocks > 0) {
         if (!srcOff || !srcLen || !dstOff || !dstCap || !outLen || !status) return bad_argument("null metadata array");

@@ -1,4 +1,4 @@
-// achip_bounds.h -- what the eight compress ops ask of dstCap, stated once: the host functions achip_*_max_compressed_length (abi_context.cpp) and the bound
+// achip_bounds.h -- what the nine compress ops ask of dstCap, stated once: the host functions achip_*_max_compressed_length (abi_context.cpp) and the bound
 // kernel of achip_compress_bound_batch (pack_outputs.hip) call these, so the two cannot drift.  Every helper takes a length n >= 0 and computes in 64 bits:
 // a result above INT32_MAX is the caller's to refuse (the host functions with their message, the kernel with a status).
 #pragma once
@@ -10,6 +10,8 @@ namespace bound {
 
 // Lz4RawCompressor.maxCompressedLength  M/lz4/Lz4RawCompressor.java:56-59
 __host__ __device__ inline int64_t lz4(int64_t n) { return n + n / 255 + 16; }
+// LzoRawCompressor.maxCompressedLength  M/lzo/LzoRawCompressor.java:65-68
+__host__ __device__ inline int64_t lzo(int64_t n) { return n + n / 255 + 16; }
 // SnappyRawCompressor.maxCompressedLength  M/snappy/SnappyRawCompressor.java:47-70
 __host__ __device__ inline int64_t snappy(int64_t n) { return 32 + n + n / 6; }
 // ZstdFrameCompressor's compressBound as ZstdJavaCompressor.maxCompressedLength states it (the shifts are those of the Java ints: for 0 <= n <= INT32_MAX

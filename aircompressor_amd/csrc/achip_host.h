@@ -94,6 +94,7 @@ struct achip_ctx : achip::Settings {
     int lastZstddVariant = 0;
     int32_t lastAutoBlocks = 0;  // ... and this many blocks
     int lastAutoFam = 0;         // ... of this codec family (kBlockCodecs)
+    int lastLzod = 0;           // the last launch was an LZO decode: 1 the two passes (their arena header leads the scratch), 2 a wavefront per item (0: it was not)
     bool lastTwopass = false;   // the last decode was a two-pass one: its arena header leads the scratch
     bool lastLz4dAuto = false;  // the last LZ4 decode ran in auto mode: its probe count leads the scratch
     // Auto mode remembers (round 6): a call's probe statistics come back to pinned memory behind its kernels, without a wait; while the batches that follow have its
@@ -168,7 +169,9 @@ BatchArgs make_args(const void* srcBase, const int64_t* srcOff, const int32_t* s
         }                                                      \
     } while (0)
 
-constexpr int kNumOps = 15;  // aircompressor_hip.h: ACHIP_OP_*
+constexpr int kNumOps = 18;  // aircompressor_hip.h: ACHIP_OP_* (one above the largest)
+// ... of which 15 is no op: the odd-even rule of the ops (even ops decode, odd ops encode) left it out
+inline bool op_known(int32_t op) { return op >= 0 && op < kNumOps && op != 15; }
 
 // abi_dispatch.cpp
 int32_t ensure_scratch(achip_ctx* ctx, int64_t bytes);            // frees what is there first

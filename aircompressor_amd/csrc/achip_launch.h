@@ -65,6 +65,13 @@ struct ListedWant {
 hipError_t launch_listed_decode(const BatchArgs& listed, int fam, hipStream_t stream, const int32_t* counters, int32_t* stats, const AuxScratch* aux, const KernelSettings& ks,
                                 const ListedWant& want, bool* decoded);
 
+// ---- LZO (lzo_decompress.hip, lzo_compress.hip) ----
+// a wavefront per item (honours a.only); and the two passes: the lane parser, the record executor, the wavefront decoder for what the parser handed over
+hipError_t launch_lzo_decompress_wave(const BatchArgs& a, hipStream_t stream);
+// (maxChunks > 0: no more than that many 4 KiB chunks of the arena are used -- option "lzo.decompress.max_chunks", a test's way to an exhausted arena)
+hipError_t launch_lzo_decompress_twopass(const BatchArgs& a, hipStream_t stream, void* scratch, int64_t scratchBytes, int32_t maxChunks);
+hipError_t launch_lzo_compress(const BatchArgs& a, hipStream_t stream);
+
 // ---- LZ4 / Snappy block encoders ----
 // the two-tier LZ4 kernel runs only with at least lz4_compress_scratch_bytes() of scratch (scratchBytes); with less, the one-wavefront kernel writes the same bytes
 hipError_t launch_lz4_compress(const BatchArgs& a, hipStream_t stream, int variant, int maxSrcLenHint, void* scratch, int64_t scratchBytes, const KernelSettings& ks);

@@ -139,6 +139,9 @@ inline SnfRefusal set_snf_verify(KernelSettings& ks, int32_t verify)
 struct Settings {
     int lz4dGroup = 0;       // ring decoder, lanes per block: 0 = by the batch size (4 from 32 768 blocks on -- the headline's form --, 16 below, 64 up to 4 096: lz4_ring_group_for), else 1 .. 64
     int snappydGroup = 0;    // likewise (64 up to 2 048 blocks, 16 below 16 384, 4 above: snappy_ring_group_for)
+    int lzodVariant = 0;           // LZO decode: 0 auto (by the batch size: lzodAutoMinBlocks), 1 two passes (lzo_parse2_kernel + the record executor), 2 a wavefront per item (lzo_decompress.hip)
+    int lzodAutoMinBlocks = 8192;  // ... auto runs the two passes from this many items on (provisional -- one run, profiles/lzo_rate.txt: on text the two decoders cross between 4 096 and 16 384 blocks)
+    int lzodMaxChunks = 0;         // ... the two passes use at most this many 4 KiB chunks of the record arena (0: all the scratch has; a test aid, not a tuning knob)
     int lz4dAutoMinBlocks = 4096;  // auto mode probes batches from this size on (smaller ones always take the rings)
     int lz4dVariant = 5;     // 5 = chosen on the device per batch (default: DESIGN 4c), 1 = LDS rings, a lane group per block (lz4_decompress_v2.hip), 7 = two passes: parse to records + a wavefront per block (lz4_decompress_v7.hip).  (4 / 6, a lane per block, lost to 7 on every batch they were built for -- 300 .. 330 GiB/s against 515 on corpus -- and were removed in round 4.)
     int snappydVariant = 5;  // 5 auto, 1 rings (snappy_decompress_v2.hip), 7 two passes (snappy_decompress_v5.hip), as for LZ4
@@ -292,6 +295,9 @@ inline const Option kOptions[] = {
 // Options that came after that table was frozen against the parser it replaced (tests/test_options.py holds kOptions to that parser's names and values); DESIGN.md 8b
 // documents them below its table.
 inline const Option kLaterOptions[] = {
+    {"lzo.decompress.variant", &Settings::lzodVariant, range(0, 2), "lzo.decompress.variant: 0 auto, 1 two passes, 2 a wavefront per item"},
+    {"lzo.decompress.auto_min_blocks", &Settings::lzodAutoMinBlocks, range(1, 0x7FFFFFFF), "lzo.decompress.auto_min_blocks must be at least 1"},
+    {"lzo.decompress.max_chunks", &Settings::lzodMaxChunks, range(0, 0x7FFFFFFF), "lzo.decompress.max_chunks must not be negative"},
     {"lz4frame.compress.variant", &KernelSettings::lz4fCompressVariant, range(0, 1), "lz4frame.compress.variant: 0 the writer the context's frame settings ask for (a wavefront per frame at the defaults), 1 the block-list writer at the default settings too"},
 };
 

@@ -15,6 +15,7 @@
 //                     assumed -- is walked by the lane itself.
 //   planner           reduce, scan of the partial sums by one workgroup, scan: three launches, no workgroup waits for another.
 #include "achip_waveparse.h"
+#include "lzo_decode_body.h"
 #include "lz4_frame_head.h"
 #include "zstd_default_tables.h"
 #include "achip_launch.h"
@@ -146,6 +147,23 @@ __global__ __launch_bounds__(64) void lz4_size_lane_kernel(SizeArgs s)
     int32_t st = 0, eo = 0;
     ds::lz4_size_serial(s.srcBase + s.srcOff[block], s.srcLen[block], size, st, eo);
     ds::put_result(s, block, size, st, eo);
+}
+
+// LZO: the decoder's own walk (lzo_decode_body.h) with a capacity of INT32_MAX, a lane per item -- no record, no byte written
+__global__ __launch_bounds__(64) void lzo_size_kernel(SizeArgs s)
+{
+    const int64_t item = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (item >= ds::item_count(s)) {
+        return;
+    }
+    const uint8_t* __restrict__ in = s.srcBase + s.srcOff[item];
+    const int32_t inLimit = s.srcLen[item];
+    lzod::Walk w;
+    w.begin();
+    int32_t ml, off, lit, litPos;
+    while (lzod::step(in, inLimit, 0x7FFFFFFF, w, ml, off, lit, litPos) != lzod::STEP_DONE) {
+    }
+    ds::put_result(s, item, w.op, w.st, w.eo);
 }
 
 // A wavefront per block, the blocks of a launch dealt round over its workgroups (a batch listed on the device has a count the host does not know).  Lane p reads the
@@ -1035,6 +1053,7 @@ hipError_t launch_decoded_size(int32_t op, const SizeArgs& s, hipStream_t stream
         case ACHIP_OP_SNAPPYFRAMED_DECOMPRESS: return launch_container_size<ds::KIND_SNAPPYFRAMED>(s, stream, scratch);
         case ACHIP_OP_LZ4HADOOP_DECOMPRESS: return launch_container_size<ds::KIND_LZ4HADOOP>(s, stream, scratch);
         case ACHIP_OP_SNAPPYHADOOP_DECOMPRESS: return launch_container_size<ds::KIND_SNAPPYHADOOP>(s, stream, scratch);
+        case ACHIP_OP_LZO_DECOMPRESS: hipLaunchKernelGGL(lzo_size_kernel, perLane, wg, 0, stream, s); return hipGetLastError();
         default: return hipErrorUnknown;  // (achip_decoded_size_batch has refused any other op)
     }
 }

@@ -180,7 +180,8 @@ struct Lz4ProbeStep {
     int32_t cand;      // ... and its candidate
 };
 
-template <typename TableT, bool ACCEL>
+// (MAXD: the farthest candidate a probe accepts -- the LZO encoder, lzo_compress.hip, runs the same step with its own MAX_DISTANCE)
+template <typename TableT, bool ACCEL, int MAXD = lz4c::MAX_DISTANCE>
 __device__ __forceinline__ Lz4ProbeStep lz4_probe_step(const uint8_t* in, TableT* table, int32_t mask, int hashBits, int32_t matchFindLimit, int32_t scanStart, int32_t accel,
                                                        int role, int32_t pos, int32_t k, int lane)
 {
@@ -221,7 +222,7 @@ __device__ __forceinline__ Lz4ProbeStep lz4_probe_step(const uint8_t* in, TableT
     }
     bool hit = false;
     if (active && role == 2) {
-        hit = ld4(in + cand) == (uint32_t)x && cand + MAX_DISTANCE >= pos;
+        hit = ld4(in + cand) == (uint32_t)x && cand + MAXD >= pos;
     }
     const unsigned long long hitMask = __ballot(hit);
     const int winner = hitMask ? __builtin_ctzll(hitMask) : -1;
@@ -257,92 +258,24 @@ __device__ int32_t lz4_compress_block(const uint8_t* __restrict__ in, int32_t in
         int32_t anchor = 0;
 
         if (inLen >= MIN_LENGTH) {
-            // mode 0: block start (lane 0 inserts position 0, search starts at 1); mode 1: after a match; mode 2: search continues
-            int mode = 0;
-            int32_t input = 0;      // mode 1: position right after the last match
-            int32_t scanStart = 1;  // position of probe 0 of the current search
-            int32_t k0 = 0;         // first probe index of this batch (mode 2)
-            int width = 64;          // lanes used by a batch (a narrow first batch of 8 was measured slower on MI355X: profiles/r01_notes.md)
-            for (;;) {
-                // ---- roles and positions ----
-                int role = 0;  // 0 idle, 1 insert only, 2 probe
-                int32_t pos = 0;
-                int32_t k = -1;  // search probe index (>= 0 for search probes; -1 for the insert / re-probe lanes)
-                if (mode == 0) {
-                    if (lane == 0) {
-                        role = 1;
-                        pos = 0;
-                    }
-                    else {
-                        role = 2;
-                        k = lane - 1;
-                    }
-                }
-                else if (mode == 1) {
-                    if (lane == 0) {
-                        role = 1;
-                        pos = input - 2;
-                    }
-                    else if (lane == 1) {
-                        role = 2;
-                        pos = input;
-                    }
-                    else {
-                        role = 2;
-                        k = lane - 2;
-                    }
-                }
-                else {
-                    role = 2;
-                    k = k0 + lane;
-                }
-                if (lane >= width) {
-                    role = 0;
-                    k = -1;
-                }
-                const Lz4ProbeStep s = lz4_probe_step<TableT, ACCEL>(in, table, mask, hashBits, matchFindLimit, scanStart, accel, role, pos, k, lane);
-                __syncthreads();
-
-                if (s.winner < 0) {
-                    if (s.firstInvalid < 64) {
-                        break;  // search ran off the end: last literals from anchor
-                    }
-                    // no match in this batch: the search goes on
-                    const int32_t probes = mode == 0 ? width - 1 : (mode == 1 ? width - 2 : width);
-                    k0 = (mode == 2 ? k0 : 0) + probes;
-                    mode = 2;
-                    width = 64;
-                    continue;
-                }
-                input = __shfl(s.pos, s.winner);
-                int32_t matchIndex = __shfl(s.cand, s.winner);
-                const bool reprobe = mode == 1 && s.winner == 1;
-
-                int32_t literalLength = 0;
-                int32_t tokenPos;
-                if (!reprobe) {
-                    lz4_catch_up_mem(in, input, matchIndex, input - anchor < matchIndex ? input - anchor : matchIndex, lane);
-                    literalLength = input - anchor;
-                    tokenPos = output;
-                    const int32_t litPos = tokenPos + lz4_run_length_size(literalLength);
-                    group_copy<64>(out + litPos, in + anchor, literalLength, lane);  // emitLiteral :194-207
-                    output = litPos + literalLength;
-                }
-                else {
-                    tokenPos = output++;  // zero-literal token :181-183
-                }
-                const int32_t matchLength = wave_count(in, input + MIN_MATCH, matchIndex + MIN_MATCH, matchLimit, lane);
-                output = lz4_emit_match(out, tokenPos, literalLength, input - matchIndex, matchLength, output, lane);
-                input += matchLength + MIN_MATCH;
-                anchor = input;
-                if (input > matchFindLimit) {
-                    break;  // :152-155
-                }
-                mode = 1;
-                scanStart = input + 1;
-                k0 = 0;
-                width = 64;
-            }
+#define BATCH_SEARCH_PROBE(role, pos, k) lz4_probe_step<TableT, ACCEL>(in, table, mask, hashBits, matchFindLimit, scanStart, accel, role, pos, k, lane)
+#define BATCH_SEARCH_EMIT_STATE     \
+    int32_t literalLength = 0;      \
+    int32_t tokenPos;
+#define BATCH_SEARCH_EMIT_LITERALS                                                                         \
+    literalLength = input - anchor;                                                                        \
+    tokenPos = output;                                                                                     \
+    const int32_t litPos = tokenPos + lz4_run_length_size(literalLength);                                  \
+    group_copy<64>(out + litPos, in + anchor, literalLength, lane); /* emitLiteral :194-207 */            \
+    output = litPos + literalLength;
+#define BATCH_SEARCH_EMIT_NO_LITERALS tokenPos = output++; /* zero-literal token :181-183 */
+#define BATCH_SEARCH_EMIT_MATCH output = lz4_emit_match(out, tokenPos, literalLength, input - matchIndex, matchLength, output, lane);
+#include "lz4_batch_search.h"
+#undef BATCH_SEARCH_PROBE
+#undef BATCH_SEARCH_EMIT_STATE
+#undef BATCH_SEARCH_EMIT_LITERALS
+#undef BATCH_SEARCH_EMIT_NO_LITERALS
+#undef BATCH_SEARCH_EMIT_MATCH
         }
         output = lz4_emit_last_literals(in, out, output, anchor, inputLimit, lane);
     }

@@ -41,6 +41,7 @@ __device__ __forceinline__ int64_t compress_bound(int32_t op, int32_t n, int32_t
         case ACHIP_OP_LZ4HADOOP_COMPRESS: return bound::hadoop(false, n, hadoopBufferSize);
         case ACHIP_OP_SNAPPYHADOOP_COMPRESS: return bound::hadoop(true, n, hadoopBufferSize);
         case ACHIP_OP_ZSTDSTREAM_COMPRESS: return bound::zstdstream(n);
+        case ACHIP_OP_LZO_COMPRESS: return bound::lzo(n);
         default: return -1;
     }
 }

@@ -13,6 +13,7 @@ LIBRARY_PATH = os.path.join(_HERE, "libaircompressor_hip.so")
 
 CLASS_MALFORMED, CLASS_OUTPUT_TOO_SMALL, CLASS_INVALID_ARGUMENT, CLASS_DEVICE = 1, 2, 3, 4
 DETAIL_LZ4_EMPTY_OUTPUT = 7
+DETAIL_LZO_MALFORMED, DETAIL_LZO_MAX_INPUT, DETAIL_LZO_MAX_OUTPUT = 111, 112, 113
 # achip_window_*: a window's flags and why a call stopped (include/aircompressor_hip.h)
 WINDOW_FIRST, WINDOW_LAST = 1, 2
 STOP_END, STOP_NEED_INPUT, STOP_NEED_ROOM, STOP_FAILED = 0, 1, 2, 3
@@ -29,6 +30,7 @@ SIGNATURES = {
     "achip_device_count": (_i32, []),
     "achip_last_error": (ctypes.c_char_p, []),
     "achip_lz4_max_compressed_length": (_i32, [_i32]),
+    "achip_lzo_max_compressed_length": (_i32, [_i32]),
     "achip_snappy_max_compressed_length": (_i32, [_i32]),
     "achip_zstd_max_compressed_length": (_i32, [_i32]),
     "achip_snappy_uncompressed_length": (_i64, [_vp, _i64, ctypes.POINTER(_i64)]),
@@ -109,6 +111,10 @@ SIGNATURES = {
     "achip_snappy_compress_batch": (_i32, _BATCH),
     "achip_zstd_decompress_batch": (_i32, _BATCH),
     "achip_zstd_compress_batch": (_i32, _BATCH),
+    "achip_lzo_decompress_batch": (_i32, _BATCH),
+    "achip_lzo_compress_batch": (_i32, _BATCH),
+    "achip_lzo_compress": (_i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64)]),
+    "achip_lzo_decompress": (_i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64)]),
     "achip_lz4_compress": (_i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64)]),
     "achip_lz4_decompress": (_i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64)]),
     "achip_snappy_compress": (_i32, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64)]),

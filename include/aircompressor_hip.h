@@ -133,6 +133,14 @@ enum achip_detail {
     ACHIP_D_HDP_NOT_CONSUMED = 108,       /* T/HadoopCodecDecompressor.java:52 "All input was not consumed": the destination cannot hold the stream */
     ACHIP_D_HDP_NEGATIVE_LENGTH = 109,    /* this API: a negative chunk length (Java: the block codec's range check throws)           */
     ACHIP_D_HDP_MAX_OUTPUT = 110,         /* this API (encoder): dstCap < achip_hadoop_max_compressed_length                          */
+    /* LZO decode -- M/lzo/LzoRawDecompressor.java */
+    ACHIP_D_LZO_MALFORMED = 111,          /* :57,112,133,169,210,236,252,262,298,324,329 "Malformed input": every throw of the decoder, "output too small"
+                                             included.  (Its "Invalid LZO command" branch :245-248 cannot be reached: the four tests in front of it --
+                                             (c & 0xF0) == 0, == 0x10, (c & 0xE0) == 0x20, (c & 0xC0) != 0 -- cover every byte.) */
+    /* LZO encode -- M/lzo/LzoRawCompressor.java */
+    ACHIP_D_LZO_MAX_INPUT = 112,          /* :84-86 "Max input length exceeded"                        */
+    ACHIP_D_LZO_MAX_OUTPUT = 113,         /* :88-90 "Max output length must be larger than N" (checked before "nothing compresses to nothing": an empty input
+                                             with dstCap < 16 is this, not 0) */
     /* runtime */
     ACHIP_D_NO_DEVICE = 100,
     ACHIP_D_HIP_ERROR = 101,
@@ -162,6 +170,8 @@ int32_t achip_lz4_max_compressed_length(int32_t uncompressedSize);
 int32_t achip_snappy_max_compressed_length(int32_t uncompressedSize);
 /* replaces ZstdJavaCompressor.maxCompressedLength    M/zstd/ZstdJavaCompressor.java:31-40 (ZSTD_compressBound, M/zstd/ZstdNative.java:28) */
 int32_t achip_zstd_max_compressed_length(int32_t uncompressedSize);
+/* replaces LzoRawCompressor.maxCompressedLength      M/lzo/LzoRawCompressor.java:65-68: n + n / 255 + 16 */
+int32_t achip_lzo_max_compressed_length(int32_t uncompressedSize);
 /* replaces SnappyRawDecompressor.getUncompressedLength  M/snappy/SnappyRawDecompressor.java:30-33,277-321; negative = status, *errOffset set */
 int64_t achip_snappy_uncompressed_length(const void* src, int64_t srcLen, int64_t* errOffset);
 /* replaces ZstdFrameDecompressor.getDecompressedSize    M/zstd/ZstdFrameDecompressor.java:942-947; -1 = unknown, < -1 = status */
@@ -295,6 +305,8 @@ int32_t achip_snappyframed_max_compressed_length_for(int32_t uncompressedSize, i
  *   items (capacity >= 80 bytes per sequence): a tile of more than 16 384 items with at least 24 576 of them runs those on the ring executor,
  *   everything else runs on the record executor (-1: the one-kernel decoder ran);
  * "lz4.decompress.mixed_groups": auto mode's count of mixed 16-block groups of the last LZ4 / Snappy decode (-1: no probe ran);
+ * "lzo.decompress.fallback_blocks": items of the last LZO decode whose records did not fit the two passes' arena (or cannot be expressed as
+ *   records): the wavefront-per-item decoder took them (0 when that decoder ran alone; -1: the last launch was no LZO decode);
  * "decompress.choice": the decoder auto mode ran (0 LDS rings, 3 two passes; -1: no probe ran).  DESIGN.md 8b lists every option and
  *   statistic. */
 int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name);
@@ -346,6 +358,12 @@ int32_t achip_snappy_compress_batch(ACHIP_BATCH_ARGS);
 int32_t achip_zstd_decompress_batch(ACHIP_BATCH_ARGS);
 /* replaces ZstdFrameCompressor.compress(level 3) M/zstd/ZstdFrameCompressor.java:136-150 (a11-a14) */
 int32_t achip_zstd_compress_batch(ACHIP_BATCH_ARGS);
+/* replaces LzoRawDecompressor.decompress    M/lzo/LzoRawDecompressor.java:32-352: an item is any number of concatenated LZO1X blocks (decoded until the
+ * input is consumed); an empty item is 0 bytes, status 0.  Every failure is MALFORMED / ACHIP_D_LZO_MALFORMED with the Java `input - inputAddress` in
+ * errOffset -- a destination that is too small included.  Context option "lzo.decompress.variant"  */
+int32_t achip_lzo_decompress_batch(ACHIP_BATCH_ARGS);
+/* replaces LzoRawCompressor.compress        M/lzo/LzoRawCompressor.java:70-201: byte for byte; wants dstCap >= achip_lzo_max_compressed_length(srcLen) */
+int32_t achip_lzo_compress_batch(ACHIP_BATCH_ARGS);
 
 /* ------------------------------------------------------------------------- */
 /* Single-block host-pointer API: what Compressor.compress(MemorySegment,     */
@@ -361,6 +379,9 @@ int32_t achip_snappy_compress(achip_ctx* ctx, const void* src, void* dst, int32_
 int32_t achip_snappy_decompress(achip_ctx* ctx, const void* src, void* dst, int32_t srcLen, int32_t dstCap, int64_t* errOffset);
 int32_t achip_zstd_compress(achip_ctx* ctx, const void* src, void* dst, int32_t srcLen, int32_t dstCap, int64_t* errOffset);
 int32_t achip_zstd_decompress(achip_ctx* ctx, const void* src, void* dst, int32_t srcLen, int32_t dstCap, int64_t* errOffset);
+/* LzoCompressor.compress / LzoDecompressor.decompress  M/lzo/LzoCompressor.java, M/lzo/LzoDecompressor.java */
+int32_t achip_lzo_compress(achip_ctx* ctx, const void* src, void* dst, int32_t srcLen, int32_t dstCap, int64_t* errOffset);
+int32_t achip_lzo_decompress(achip_ctx* ctx, const void* src, void* dst, int32_t srcLen, int32_t dstCap, int64_t* errOffset);
 
 /* ---- LZ4 frame container ----
  * Replace Lz4FrameCompression.maxCompressedLength / compress / decompress    M/lz4/Lz4FrameCompression.java:70-83, 96-140, 145-343
@@ -500,6 +521,9 @@ int32_t achip_hasher_destroy(void* hasher);
 #define ACHIP_OP_SNAPPYHADOOP_DECOMPRESS 12
 #define ACHIP_OP_SNAPPYHADOOP_COMPRESS 13
 #define ACHIP_OP_ZSTDSTREAM_COMPRESS 14
+/* (15 is no op, and every entry point refuses it: even ops decode, odd ops encode, and 14 had taken the Zstd stream writer's place out of turn) */
+#define ACHIP_OP_LZO_DECOMPRESS 16
+#define ACHIP_OP_LZO_COMPRESS 17
 int32_t achip_batch_host(int32_t codecOp, ACHIP_BATCH_ARGS);
 /* (Staging is chunked and pipelined over up to four pinned slots: this thread gathers chunk c+1 into pinned memory while chunk c
  * is uploaded / run / downloaded on three streams and a finalizer thread scatters chunk c-1 to dstBase -- each side with a few
@@ -522,15 +546,16 @@ int32_t achip_mixed_batch_host(achip_ctx* ctx, const int32_t* codecOp, const voi
                                const int64_t* dstOff, const int32_t* dstCap, int32_t* outLen, int32_t* status, int64_t* errOffset, int32_t nBlocks);
 
 /* ---- Sizing a batch on the device: for a caller that holds compressed items in device memory and knows nothing else ----
- * achip_decoded_size_batch: outSize[i] = the bytes item i decodes to under `codecOp`, one of the seven decode ops (LZ4, SNAPPY, ZSTD, LZ4FRAME, SNAPPYFRAMED,
- *   LZ4HADOOP, SNAPPYHADOOP _DECOMPRESS; any other op is INVALID_ARGUMENT), found without decoding: what a Java caller asks
+ * achip_decoded_size_batch: outSize[i] = the bytes item i decodes to under `codecOp`, one of the eight decode ops (LZ4, SNAPPY, ZSTD, LZ4FRAME, SNAPPYFRAMED,
+ *   LZ4HADOOP, SNAPPYHADOOP, LZO _DECOMPRESS; any other op is INVALID_ARGUMENT), found without decoding: what a Java caller asks
  *     SnappyJavaDecompressor.getUncompressedLength   M/snappy/SnappyJavaDecompressor.java (-> SnappyRawDecompressor.java:30-33,277-321)      Snappy: the preamble
  *     ZstdJavaDecompressor.getDecompressedSize       M/zstd/ZstdJavaDecompressor.java   (-> ZstdFrameDecompressor.java:942-947)              Zstd: here the walk of
  *         the frames' blocks (block headers, literals headers, the match lengths of the sequence sections): frames without a content size are sized too, and the
  *         header's field, which the decoder never checks, is not trusted
  *   for, one buffer at a time on the host; for LZ4 raw blocks there is no counterpart: the Java caller must know (here: the token walk of
  *   M/lz4/Lz4RawDecompressor.java:59-195).  Containers: the reader's loop over the stream's headers, the LZ4 walk / the Snappy preamble per chunk where the
- *   loop needs it (an LZ4 frame that announces its content size is that size).
+ *   loop needs it (an LZ4 frame that announces its content size is that size).  LZO blocks carry no length: the command walk of
+ *   M/lzo/LzoRawDecompressor.java:52-349 with a capacity of INT32_MAX (status and offset are the decoder's for that capacity).
  *   R1  if the op's decoder, given dstCap = the item's true plaintext length, succeeds, then status[i] == 0 and outSize[i] is that length;
  *   R2  if status[i] == 0, the decoder run with dstCap = outSize[i] returns exactly outSize[i] or fails -- it never succeeds with another length.
  *   status[i] != 0 (errOffset[i] set, outSize[i] = 0): the walk met a structural fault, reported as the op's reader reports it.  Faults only the payload decode
@@ -547,8 +572,8 @@ int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t
                            int64_t* dstOff, int32_t* dstCap, int64_t* total /* [2] */);
 
 /* ---- The compress side of the same: bound -> plan -> compress -> pack, for a caller whose plaintexts and their lengths live in device memory ----
- * achip_compress_bound_batch: outSize[i] = what `codecOp`, one of the eight compress ops (LZ4, SNAPPY, ZSTD, LZ4FRAME, SNAPPYFRAMED, LZ4HADOOP, SNAPPYHADOOP,
- *   ZSTDSTREAM _COMPRESS; any other op is INVALID_ARGUMENT), asks of dstCap for srcLen[i] bytes: the op's achip_*_max_compressed_length(srcLen[i]), computed in
+ * achip_compress_bound_batch: outSize[i] = what `codecOp`, one of the nine compress ops (LZ4, SNAPPY, ZSTD, LZ4FRAME, SNAPPYFRAMED, LZ4HADOOP, SNAPPYHADOOP,
+ *   ZSTDSTREAM, LZO _COMPRESS; any other op is INVALID_ARGUMENT), asks of dstCap for srcLen[i] bytes: the op's achip_*_max_compressed_length(srcLen[i]), computed in
  *   64-bit arithmetic -- what a Java caller asks Compressor.maxCompressedLength (M/Compressor.java:20) for, one int at a time on the host.  The Hadoop ops use
  *   the context's "hadoop.buffer_size", as their compress call does.  A negative srcLen[i], or a bound above INT32_MAX, gives status[i] of class
  *   INVALID_ARGUMENT and outSize[i] = 0; else status[i] = 0.  outSize / status feed achip_plan_outputs unchanged: its dstOff[] / dstCap[] / total are the

@@ -74,6 +74,8 @@ public final class HipNative
     public static final int STOP_NEED_INPUT = 1;
     public static final int STOP_NEED_ROOM = 2;
     public static final int STOP_FAILED = 3;
+    public static final int OP_LZO_DECOMPRESS = 16;          // achip_lzo_decompress (15 is no op: even ops decode, odd ops encode)
+    public static final int OP_LZO_COMPRESS = 17;
     public static final int OP_ZSTDSTREAM_COMPRESS = 14;     // achip_zstdstream_compress (SURVEY 8f row 3: what a ZstdOutputStream puts on its sink)
 
     private record MethodHandles(
@@ -85,6 +87,18 @@ public final class HipNative
             MethodHandle lastError,
             @NativeSignature(name = "achip_lz4_max_compressed_length", returnType = int.class, argumentTypes = int.class)
             MethodHandle lz4MaxCompressedLength,
+            @NativeSignature(name = "achip_lzo_max_compressed_length", returnType = int.class, argumentTypes = int.class)
+            MethodHandle lzoMaxCompressedLength,
+            @NativeSignature(name = "achip_lzo_compress", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class})
+            MethodHandle lzoCompress,
+            @NativeSignature(name = "achip_lzo_decompress", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class, int.class, MemorySegment.class})
+            MethodHandle lzoDecompress,
+            @NativeSignature(name = "achip_lzo_decompress_batch", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class,
+                    MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
+            MethodHandle lzoDecompressBatch,
+            @NativeSignature(name = "achip_lzo_compress_batch", returnType = int.class, argumentTypes = {MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class,
+                    MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, MemorySegment.class, int.class})
+            MethodHandle lzoCompressBatch,
             @NativeSignature(name = "achip_snappy_max_compressed_length", returnType = int.class, argumentTypes = int.class)
             MethodHandle snappyMaxCompressedLength,
             @NativeSignature(name = "achip_zstd_max_compressed_length", returnType = int.class, argumentTypes = int.class)
@@ -601,6 +615,16 @@ public final class HipNative
     {
         try {
             return (int) HANDLES.lz4MaxCompressedLength().invokeExact(n);
+        }
+        catch (Throwable e) {
+            throw new AssertionError("should not reach here", e);
+        }
+    }
+
+    public static int lzoMaxCompressedLength(int n)
+    {
+        try {
+            return (int) HANDLES.lzoMaxCompressedLength().invokeExact(n);
         }
         catch (Throwable e) {
             throw new AssertionError("should not reach here", e);
@@ -1283,6 +1307,8 @@ public final class HipNative
                     case OP_LZ4HADOOP_DECOMPRESS -> HANDLES.lz4HadoopDecompress();
                     case OP_SNAPPYHADOOP_COMPRESS -> HANDLES.snappyHadoopCompress();
                     case OP_ZSTDSTREAM_COMPRESS -> HANDLES.zstdStreamCompress();
+                    case OP_LZO_COMPRESS -> HANDLES.lzoCompress();
+                    case OP_LZO_DECOMPRESS -> HANDLES.lzoDecompress();
                     case OP_SNAPPYHADOOP_DECOMPRESS -> HANDLES.snappyHadoopDecompress();
                     default -> throw new IllegalArgumentException("unknown op " + op);
                 };
@@ -1324,6 +1350,8 @@ public final class HipNative
                     case OP_LZ4HADOOP_DECOMPRESS -> HANDLES.lz4HadoopDecompressBatch();
                     case OP_SNAPPYHADOOP_COMPRESS -> HANDLES.snappyHadoopCompressBatch();
                     case OP_ZSTDSTREAM_COMPRESS -> HANDLES.zstdStreamCompressBatch();
+                    case OP_LZO_COMPRESS -> HANDLES.lzoCompressBatch();
+                    case OP_LZO_DECOMPRESS -> HANDLES.lzoDecompressBatch();
                     case OP_SNAPPYHADOOP_DECOMPRESS -> HANDLES.snappyHadoopDecompressBatch();
                     default -> throw new IllegalArgumentException("unknown op " + op);
                 };

@@ -36,13 +36,15 @@ TARGETS = {
     "snf_params_w":    ("emu_snf_params.cpp",   "libemu_snf_params_w.so", 2, True,  ("SNF_PARAMS_WRITERS",)),
     "snf_params_r":    ("emu_snf_params.cpp",   "libemu_snf_params_r.so", 1, False, ()),
     "lz4f_writer":     ("emu_lz4f_writer.cpp",  "libemu_lz4f_writer.so",  2, True,  ()),
+    "lzo_w":           ("emu_lzo.cpp",          "libemu_lzo_w.so",        2, True,  ("LZO_ENCODER",)),  # the encoder; lzo_r: the decoders and the sizing kernel
+    "lzo_r":           ("emu_lzo.cpp",          "libemu_lzo_r.so",        1, False, ()),
     "enc_stats":       ("emu_enc.cpp",          "libemu_enc_stats.so",    2, True,  ("ACHIP_HOST_STATS",)),  # the counting build: enc_paths.py, zc_stats.py
     "lockstep":        ("emu_lockstep.cpp",     "libemu_lockstep.so",     2, True,  ()),  # HOSTEMU_LIB=libemu_lockstep.so check_v3.py
     "entropy_unit":    ("emu_entropy_unit.cpp", "libemu_entropy_unit.so", 2, True,  ()),
     "unit_oracle_enc": ("unit_oracle_enc.c",    "libunit_oracle_enc.so",  2, False, ()),  # a C unit over oracle/*.c: check_entropy_unit.py's reference
 }
-GROUPS = {"snf_params": ("snf_params_w", "snf_params_r")}  # (a name of build.sh that stands for two libraries)
-DEFAULT = ("zstd", "enc", "all", "serial", "emu", "xxh3", "size", "pack", "xxh_stream", "window", "lz4_accel", "snf_params", "lz4f_writer")  # what build.sh builds when nothing is named
+GROUPS = {"snf_params": ("snf_params_w", "snf_params_r"), "lzo": ("lzo_w", "lzo_r")}  # (a name of build.sh that stands for two libraries)
+DEFAULT = ("zstd", "enc", "all", "serial", "emu", "xxh3", "size", "pack", "xxh_stream", "window", "lz4_accel", "snf_params", "lz4f_writer", "lzo")  # what build.sh builds when nothing is named
 
 
 def compiler():
