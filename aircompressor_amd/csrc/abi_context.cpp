@@ -504,12 +504,8 @@ static bool read_scratch(achip_ctx* ctx, int64_t offset, int32_t* v, int n)
 int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name)
 {
     if (!ctx || !name) return -1;
-    std::string k(name);
-    if (k == "lz4.decompress.mixed_groups") {  // auto mode's probe result of the last LZ4 decode (-1: it did not run)
-        if (!ctx->lastLz4dAuto || ctx->scratch.get() == nullptr) return -1;
-        int32_t v = 0;
-        return read_scratch(ctx, 0, &v, 1) ? v : -1;
-    }
+    const std::string k(name);
+    // what the context itself knows
     if (k == "pack.tile_bytes") return achip::PACK_TILE_BYTES;  // the unit of achip_pack_outputs' copy (a constant of the build)
     if (k == "host.gather_us") return ctx->hostGatherUs;          // the gather thread copying the caller's inputs into pinned slots
     if (k == "host.scatter_us") return ctx->hostScatterUs;        // the finalizer thread copying outputs to the caller's buffers
@@ -517,54 +513,15 @@ int64_t achip_ctx_get_stat(achip_ctx* ctx, const char* name)
     if (k == "host.wait_download_us") return ctx->hostWaitDownloadUs;  // the finalizer waiting for a chunk's download (the device side / the gather is the limit)
     if (k == "host.chunks") return ctx->hostChunks;
     if (k == "host.total_us") return ctx->hostTotalUs;
-    if (k == "decompress.choice") {  // which decoder auto mode ran last: 0 rings, 3 two passes; -1: no probe ran
-        if (ctx->lastRemembered >= 0) return ctx->lastRemembered;  // (a remembered choice: decompress.auto_reprobe)
-        if (!ctx->lastLz4dAuto || ctx->scratch.get() == nullptr) return -1;
-        int32_t v[6] = {0, 0, 0, 0, 0, 0};
-        if (!read_scratch(ctx, 0, v, 6)) return -1;
-        return achip::plan::auto_pick(v, ctx->lastAutoBlocks, achip::kBlockCodecs[ctx->lastAutoFam].shortLimit);
-    }
     if (k == "decompress.scratch_bytes") {  // the context's decode scratch as granted (the two-pass decoders' record arena is what lies behind its fixed part): a smaller grant than a batch asked for shows here and in decompress.twopass_fallback_blocks
         return ctx->scratchBytes;
     }
-    if (k == "decompress.twopass_fallback_blocks") {  // blocks the last two-pass LZ4 / Snappy decode handed to the ring decoder (-1: none ran)
-        if (!ctx->lastTwopass || ctx->scratch.get() == nullptr) return -1;
-        int32_t v[3] = {0, 0, 0};
-        return read_scratch(ctx, ctx->lastLz4dAuto ? 4096 : 0, v, 3) ? v[2] : -1;
-    }
-    if (k == "lzo.decompress.fallback_blocks") {  // items of the last LZO decode whose records did not fit the arena: the wavefront decoder took them (-1: the last launch was no LZO decode)
-        if (ctx->lastLzod == 0) return -1;
-        if (ctx->lastLzod == 2 || ctx->scratch.get() == nullptr) return 0;
-        int32_t v[3] = {0, 0, 0};
-        return read_scratch(ctx, 0, v, 3) ? v[2] : -1;
-    }
-    if (k == "zstd.decompress.multiblock_items" || k == "zstd.decompress.multiblock_blocks" || k == "zstd.decompress.multiblock_fast_items") {
-        // the last Zstd decode: items K1 handed to the multi-block stages, their blocks, items those stages finished
-        if (ctx->lastZstddBlocks <= 0 || ctx->scratch.get() == nullptr || ctx->lastZstddVariant == 0) return -1;
-        int32_t v = 0;
-        const int word = k == "zstd.decompress.multiblock_items" ? 40 : (k == "zstd.decompress.multiblock_blocks" ? 41 : 42);
-        return read_scratch(ctx, 4 * word, &v, 1) ? v : -1;
-    }
-    if (k == "zstd.decompress.long_items") {
-        // the last Zstd decode's last tile: items the sequence stage counted as long-sequence items (what the execute stage's per-item choice goes by)
-        if (ctx->lastZstddBlocks <= 0 || ctx->scratch.get() == nullptr || ctx->lastZstddVariant == 0) return -1;
-        int32_t v = 0;
-        return read_scratch(ctx, 4 * 18, &v, 1) ? v : -1;
-    }
-    const std::string prefix = "zstd.decompress.fallback_";
-    if (k.compare(0, prefix.size(), prefix) == 0) {
-        // "items": all items handed to the one-kernel decoder; "stage1".."stage5": by the stage that handed them over
-        const std::string what = k.substr(prefix.size());
-        int word = -1;
-        if (what == "items") word = 0;
-        else if (what.size() == 6 && what.compare(0, 5, "stage") == 0 && what[5] >= '1' && what[5] <= '6') word = 32 + (what[5] - '0');  // (6: the multi-block stages' walk)
-        if (word < 0) return -1;
-        if (ctx->lastZstddBlocks <= 0 || ctx->scratch.get() == nullptr) return -1;
-        if (ctx->lastZstddVariant == 0) return word == 0 ? ctx->lastZstddBlocks : 0;
-        int32_t v = 0;
-        return read_scratch(ctx, 4 * word, &v, 1) ? v : -1;  // the pipeline's counters lead its scratch
-    }
-    return -1;
+    // what the last launch left at the head of the scratch (achip_stats.h: the names, the layouts and the rule; -1: that launch left no such statistic)
+    const achip::stats::Located at = achip::stats::locate(ctx->last, name);
+    if (at.words == 0) return at.value;
+    int32_t v[achip::stats::PROBE_WORDS] = {};
+    if (ctx->scratch.get() == nullptr || !read_scratch(ctx, at.byteOffset, v, at.words)) return -1;
+    return at.pick ? achip::plan::auto_pick(v, at.pickBlocks, at.pickShortLimit) : v[at.word];
 }
 
 // ---- memory helpers ----------------------------------------------------

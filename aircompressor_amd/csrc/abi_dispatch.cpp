@@ -55,6 +55,15 @@ int32_t grow_scratch_keeping_old(achip_ctx* ctx, int64_t bytes)
     return 0;
 }
 
+// The one way to the context's scratch for a launch.  The launch will write over what the last one left at the scratch's head, so the record of that
+// (ctx->last: what achip_ctx_get_stat goes by) ends here and nowhere else; a launcher that leaves statistics of its own sets it afterwards.  Grows by
+// ensure_scratch (bytes 0: as it is -- launch_op, whose cases grow it by their own policies).
+int32_t take_scratch(achip_ctx* ctx, int64_t bytes)
+{
+    ctx->last = {};
+    return ensure_scratch(ctx, bytes);
+}
+
 // scratch of the Zstd pipeline's multi-block stages (achip::ZstdMbProvider::get; the stream is idle when the stages ask)
 void* zstd_mb_scratch(void* user, int64_t bytes)
 {
@@ -81,7 +90,7 @@ namespace {
 
 // LZ4 and Snappy block decoding: one policy (launch_block_decode) over the row of its codec family in achip::kBlockCodecs (achip_launch.h) -- 0 LZ4, 1 Snappy.
 
-// Auto mode's memory (achip_ctx::autoPinned ...).  auto_remembered: the decoder to launch alone for this batch (0 rings, 3 two passes), or -1: launch both.  First takes
+// Auto mode's memory (achip_ctx::autoPinned ...).  auto_remembered: the decoder to launch alone for this batch (LZ4_PICK_RINGS or LZ4_PICK_TWOPASS), or -1: launch both.  First takes
 // in what an earlier call sent home, if it has arrived (an event query, never a wait).
 int auto_remembered(achip_ctx* ctx, int fam, const achip::BatchArgs& a)
 {
@@ -98,7 +107,6 @@ int auto_remembered(achip_ctx* ctx, int fam, const achip::BatchArgs& a)
     }
     if (ctx->autoRemember == 0 || ctx->autoChoice[fam] < 0 || a.nBlocksDev != nullptr || a.only != nullptr) return -1;
     if (ctx->autoBlocks[fam] != a.nBlocks || ctx->autoSrc[fam] != (const void*)a.srcBase || ctx->autoDst[fam] != (const void*)a.dstBase) return -1;
-    ctx->lastRemembered = ctx->autoChoice[fam];
     return ctx->autoChoice[fam];
 }
 // behind a call's kernels: its probe statistics on their way to pinned memory (nothing waits for them; one set in flight at a time)
@@ -179,26 +187,24 @@ int32_t launch_block_decode(achip_ctx* ctx, const achip::BatchArgs& a, int fam, 
         // auto: the choice is made on the device (no host round trip): probes count the mixed 16-block groups and sample the
         // sequence lengths, every candidate decoder is launched and the ones not chosen return at once.  Mixed or short-sequence
         // batches go to the two-pass decoder (parse to records + a wavefront per block), the rest to the rings.
-        // scratch: [probe statistics: the first 4 KiB][two-pass header, meta, arena]
-        const int32_t r = ensure_twopass_scratch(ctx, 4096, a.nBlocks, c.recordBytes, c.recordBytesMin);
+        // scratch: [probe statistics: the first PROBE_LEAD_BYTES][two-pass header, meta, arena]
+        constexpr int64_t lead = achip::stats::PROBE_LEAD_BYTES;
+        const int32_t r = ensure_twopass_scratch(ctx, lead, a.nBlocks, c.recordBytes, c.recordBytesMin);
         if (r < 0) return r;
         if (r == 0) {  // no room for records on this device right now: the rings alone
             return launched(c.rings(a, ctx->stream.get(), groupSize, ctx->ringClass, nullptr));
         }
         int32_t* stats = (int32_t*)ctx->scratch.get();
-        ctx->lastZstddBlocks = 0;
         const int remembered = auto_remembered(ctx, fam, a);
-        ctx->lastLz4dAuto = true;
-        ctx->lastAutoBlocks = a.nBlocks;
-        ctx->lastAutoFam = fam;
+        const bool rings = remembered != achip::LZ4_PICK_TWOPASS, twopass = remembered != achip::LZ4_PICK_RINGS;
+        ctx->last = achip::stats::LastLaunch::block_decode(a.nBlocks, c.shortLimit, true, twopass, remembered);
         hipError_t e = achip::launch_lz4_mixed_groups(a, ctx->stream.get(), stats, 0);
-        if (e == hipSuccess) e = hipMemsetAsync(stats + 3, 1, 1, ctx->stream.get());  // stats[3] = 1: the two-pass scheme (achip_device.h lz4_pick)
+        if (e == hipSuccess) e = hipMemsetAsync(stats + achip::stats::PROBE_HAS_RECORDS, 1, 1, ctx->stream.get());  // = 1: the two-pass scheme (achip_device.h lz4_pick)
         if (e == hipSuccess) e = c.sample(a, ctx->stream.get(), stats, 0, c.shortLimit);
         // (remembered: that decoder alone and whatever this call's probes say -- they are for the calls to come)
-        if (e == hipSuccess && remembered != 3) e = c.rings(a, ctx->stream.get(), groupSize, ctx->ringClass, remembered == 0 ? nullptr : stats);
-        if (remembered != 0) {
-            ctx->lastTwopass = true;
-            if (e == hipSuccess) e = c.twopass(a, ctx->stream.get(), (uint8_t*)ctx->scratch.get() + 4096, ctx->scratchBytes - 4096, groupSize, ctx->ringClass, remembered == 3 ? nullptr : stats, ctx->kernel);
+        if (e == hipSuccess && rings) e = c.rings(a, ctx->stream.get(), groupSize, ctx->ringClass, twopass ? stats : nullptr);
+        if (e == hipSuccess && twopass) {
+            e = c.twopass(a, ctx->stream.get(), (uint8_t*)ctx->scratch.get() + lead, ctx->scratchBytes - lead, groupSize, ctx->ringClass, rings ? stats : nullptr, ctx->kernel);
         }
         if (e == hipSuccess) auto_send_home(ctx, fam, a, stats);
         return launched(e);
@@ -219,7 +225,7 @@ int32_t launch_block_decode(achip_ctx* ctx, const achip::BatchArgs& a, int fam, 
         if (r == 0) {
             return launched(c.rings(a, ctx->stream.get(), groupSize, ctx->ringClass, nullptr));
         }
-        ctx->lastTwopass = true;
+        ctx->last = achip::stats::LastLaunch::block_decode(a.nBlocks, c.shortLimit, false, true, -1);
         return launched(c.twopass(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes, groupSize, ctx->ringClass, nullptr, ctx->kernel));
     }
     return launched(c.rings(a, ctx->stream.get(), groupSize, ctx->ringClass == 0 && a.nBlocks <= ctx->latencyMaxBlocks ? 3 : ctx->ringClass, nullptr));
@@ -246,10 +252,9 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
     }
     HIP_TRY(hipSetDevice(ctx->device));
     hipError_t e = hipSuccess;
-    ctx->lastLz4dAuto = false;
-    ctx->lastTwopass = false;
-    ctx->lastRemembered = -1;
-    ctx->lastLzod = 0;
+    // Whatever the op: this launch is the context's last one now, and the scratch is its to write (the cases grow it by their own policies -- ensure_scratch,
+    // grow_scratch_keeping_old, ensure_twopass_scratch over the two).  The four launchers that leave statistics say so once they have it.
+    if (const int32_t r = take_scratch(ctx, 0); r < 0) return r;
     switch (op) {
         case ACHIP_OP_LZ4_DECOMPRESS: return launch_block_decode(ctx, a, 0, ctx->lz4dVariant, ctx->lz4dGroup);
         case ACHIP_OP_SNAPPY_DECOMPRESS: return launch_block_decode(ctx, a, 1, ctx->snappydVariant, ctx->snappydGroup);
@@ -280,9 +285,8 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
             }
             if (r < 0) return r;
             const achip::ZstdMbProvider mbp{zstd_mb_scratch, ctx, ctx->zstdStreamBlocks};
+            ctx->last = achip::stats::LastLaunch::zstd_decode(a.nBlocks, ctx->zstddVariant);
             e = achip::launch_zstd_decompress(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes, ctx->zstddVariant, ctx->zstdTile, ctx->zstdStreamBlocks >= 16 ? &mbp : nullptr, ctx->kernel);
-            ctx->lastZstddBlocks = a.nBlocks;
-            ctx->lastZstddVariant = ctx->zstddVariant;
             break;
         }
         case ACHIP_OP_LZ4FRAME_DECOMPRESS: {
@@ -351,12 +355,12 @@ int32_t launch_op(int32_t op, achip_ctx* ctx, const achip::BatchArgs& args)
                 const int32_t r = ensure_twopass_scratch(ctx, 0, a.nBlocks, achip::LZ4_RECORD_BYTES_PER_BLOCK, achip::LZ4_RECORD_BYTES_PER_BLOCK_MIN);
                 if (r < 0) return r;
                 if (r > 0) {
-                    ctx->lastLzod = 1;
+                    ctx->last = achip::stats::LastLaunch::lzo_decode(true);
                     e = achip::launch_lzo_decompress_twopass(a, ctx->stream.get(), ctx->scratch.get(), ctx->scratchBytes, ctx->lzodMaxChunks);
                     break;
                 }
             }
-            ctx->lastLzod = 2;
+            ctx->last = achip::stats::LastLaunch::lzo_decode(false);
             e = achip::launch_lzo_decompress_wave(a, ctx->stream.get());
             break;
         }
@@ -415,14 +419,7 @@ int32_t ensure_mix(achip_ctx* ctx, int64_t n)
     ctx->mixItems = want;
     return 0;
 }
-constexpr int kMixFamilies = 3;
-// LZ4 (block, frame, Hadoop), Snappy (block, framed, Hadoop), Zstd (frame, stream): aircompressor_hip.h's ACHIP_OP_* in pairs
-int op_family(int op)
-{
-    static const int family[9] = {0, 1, 2, 0, 1, 0, 1, 2, 0};  // LZ4, Snappy, Zstd, LZ4 frame, x-snappy-framed, LZ4 Hadoop, Snappy Hadoop, Zstd stream, LZO (rides with LZ4's)
-    return family[op >> 1];
-}
-bool op_is_encoder(int op) { return (op & 1) != 0 || op == ACHIP_OP_ZSTDSTREAM_COMPRESS; }  // (aircompressor_hip.h: ACHIP_OP_*_COMPRESS are the odd ops, and the last one)
+constexpr int kMixFamilies = 3;  // LZ4 (block, frame, Hadoop; LZO), Snappy (block, framed, Hadoop), Zstd (frame, stream): op_family, achip_host.h
 // the helper context codec family `op` (1, 2) of a mixed batch runs on: made at first use, this context's options at every use
 int32_t mix_lane(achip_ctx* ctx, int op, achip_ctx** out)
 {
@@ -532,20 +529,6 @@ int32_t achip_mixed_batch(achip_ctx* ctx, const int32_t* codecOp, const void* sr
 }
 
 // ---- decoded sizes and the output planner (decoded_size.hip) ----
-namespace {
-// the context's scratch for a sizing or planning call; the statistics the last decode left at its head are gone with it (achip_ctx_get_stat: -1)
-int32_t sizing_scratch(achip_ctx* ctx, int64_t bytes)
-{
-    if (bytes <= 0) return 0;
-    ctx->lastTwopass = false;
-    ctx->lastLz4dAuto = false;
-    ctx->lastRemembered = -1;
-    ctx->lastZstddBlocks = 0;
-    ctx->lastLzod = 0;
-    return ensure_scratch(ctx, bytes);
-}
-}  // namespace
-
 // (the value arguments are checked before the context is looked at: a caller's mistake is reported the same with and without a device)
 int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* srcBase, const int64_t* srcOff, const int32_t* srcLen, int64_t* outSize, int32_t* status,
                                  int64_t* errOffset, int32_t nBlocks)
@@ -556,7 +539,10 @@ int32_t achip_decoded_size_batch(achip_ctx* ctx, int32_t codecOp, const void* sr
     if (!ctx) return bad_argument("ctx is null");
     if (!srcOff || !srcLen || !outSize || !status || !errOffset) return bad_argument("null array");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (const int32_t r = sizing_scratch(ctx, achip::decoded_size_scratch_bytes(codecOp, nBlocks)); r < 0) return r;
+    // (the block codecs' size kernels use no scratch -- 0 bytes --: such a call does not take it, and the last decode's statistics stay readable)
+    if (const int64_t bytes = achip::decoded_size_scratch_bytes(codecOp, nBlocks); bytes > 0) {
+        if (const int32_t r = take_scratch(ctx, bytes); r < 0) return r;
+    }
     achip::SizeArgs s{(const uint8_t*)srcBase, srcOff, srcLen, outSize, status, errOffset, nBlocks};
     s.lz4fLinked = ctx->kernel.lz4fLinkedBlocks;
     HIP_TRY(achip::launch_decoded_size(codecOp, s, ctx->stream.get(), ctx->scratch.get()));
@@ -571,7 +557,7 @@ int32_t achip_plan_outputs(achip_ctx* ctx, const int64_t* outSize, const int32_t
     if (!ctx) return bad_argument("ctx is null");
     if (!outSize || !status || !dstOff || !dstCap || !total) return bad_argument("null array");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (const int32_t r = sizing_scratch(ctx, achip::plan_outputs_scratch_bytes(nBlocks)); r < 0) return r;
+    if (const int32_t r = take_scratch(ctx, achip::plan_outputs_scratch_bytes(nBlocks)); r < 0) return r;
     HIP_TRY(achip::launch_plan_outputs(outSize, status, nBlocks, align, dstOff, dstCap, total, ctx->scratch.get(), ctx->stream.get()));
     return 0;
 }
@@ -607,7 +593,7 @@ int32_t achip_pack_outputs(achip_ctx* ctx, const void* srcBase, const int64_t* s
     if (!ctx) return bad_argument("ctx is null");
     if (!srcOff || !outLen || !status || !packedOff || !packedLen || !total) return bad_argument("null array");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (const int32_t r = sizing_scratch(ctx, achip::pack_outputs_scratch_bytes(nBlocks)); r < 0) return r;
+    if (const int32_t r = take_scratch(ctx, achip::pack_outputs_scratch_bytes(nBlocks)); r < 0) return r;
     const achip::PackArgs p{(const uint8_t*)srcBase, srcOff, outLen, status, (const uint8_t*)rawBase, rawOff, rawLen, nBlocks, align, (uint8_t*)packedBase, packedCap,
                             packedOff, packedLen, stored, total};
     HIP_TRY(achip::launch_pack_outputs(p, ctx->scratch.get(), ctx->stream.get()));

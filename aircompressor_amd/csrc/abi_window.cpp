@@ -13,16 +13,6 @@ bool is_window_op(int32_t op, bool compress)
     return op == ACHIP_OP_SNAPPYFRAMED_DECOMPRESS || op == ACHIP_OP_LZ4HADOOP_DECOMPRESS || op == ACHIP_OP_SNAPPYHADOOP_DECOMPRESS;
 }
 
-// the context's scratch for a window call; the statistics the last decode left at its head are gone with it (achip_ctx_get_stat: -1)
-int32_t window_scratch(achip_ctx* ctx, int64_t bytes)
-{
-    ctx->lastTwopass = false;
-    ctx->lastLz4dAuto = false;
-    ctx->lastRemembered = -1;
-    ctx->lastZstddBlocks = 0;
-    return ensure_scratch(ctx, bytes);
-}
-
 int32_t launch_window(achip_ctx* ctx, int32_t op, const achip::BatchArgs& args, const achip::WindowArgs& w)
 {
     achip::BatchArgs a = args;
@@ -32,21 +22,21 @@ int32_t launch_window(achip_ctx* ctx, int32_t op, const achip::BatchArgs& args, 
     hipError_t e = hipSuccess;
     switch (op) {
         case ACHIP_OP_SNAPPYFRAMED_DECOMPRESS:
-            if (const int32_t r = window_scratch(ctx, achip::snappyframed_window_decompress_scratch_bytes(a.nBlocks)); r < 0) return r;
+            if (const int32_t r = take_scratch(ctx, achip::snappyframed_window_decompress_scratch_bytes(a.nBlocks)); r < 0) return r;
             e = achip::launch_snappyframed_window_decompress(a, w, ctx->stream.get(), ctx->scratch.get(), ctx->snappyFramedVariant == 0 ? 3 : ctx->snappyFramedVariant, &aux, ctx->kernel);
             break;
         case ACHIP_OP_LZ4HADOOP_DECOMPRESS:
         case ACHIP_OP_SNAPPYHADOOP_DECOMPRESS:
-            if (const int32_t r = window_scratch(ctx, achip::hadoop_window_decompress_scratch_bytes(a.nBlocks, ctx->hadoopBufferSize)); r < 0) return r;
+            if (const int32_t r = take_scratch(ctx, achip::hadoop_window_decompress_scratch_bytes(a.nBlocks, ctx->hadoopBufferSize)); r < 0) return r;
             e = achip::launch_hadoop_window_decompress(a, w, ctx->stream.get(), ctx->scratch.get(), op == ACHIP_OP_SNAPPYHADOOP_DECOMPRESS, ctx->hadoopBufferSize,
                                                        ctx->hadoopDecompressVariant == 0 ? 3 : ctx->hadoopDecompressVariant, &aux, ctx->kernel);
             break;
         case ACHIP_OP_SNAPPYFRAMED_COMPRESS:
-            if (const int32_t r = window_scratch(ctx, achip::snappyframed_window_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
+            if (const int32_t r = take_scratch(ctx, achip::snappyframed_window_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
             e = achip::launch_snappyframed_window_compress(a, w, ctx->stream.get(), ctx->scratch.get(), ctx->kernel);
             break;
         default:
-            if (const int32_t r = window_scratch(ctx, achip::hadoop_window_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
+            if (const int32_t r = take_scratch(ctx, achip::hadoop_window_compress_scratch_bytes(a.nBlocks)); r < 0) return r;
             e = achip::launch_hadoop_window_compress(a, w, ctx->stream.get(), ctx->scratch.get(), op == ACHIP_OP_SNAPPYHADOOP_COMPRESS, ctx->hadoopBufferSize);
             break;
     }

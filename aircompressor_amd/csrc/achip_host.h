@@ -14,6 +14,7 @@
 
 #include "achip_host_plan.h"
 #include "achip_launch.h"
+#include "achip_stats.h"
 
 #define ACHIP_HIDDEN __attribute__((visibility("hidden")))  // what crosses the host units and is no part of the C ABI stays out of the dynamic symbol table
 
@@ -90,13 +91,7 @@ struct achip_ctx : achip::Settings {
     int device = 0;
     achip::host::Stream stream;  // (declared in front of everything that is freed: destroyed last)
     int smallBatchHint = 0;      // set by the host-pointer path for ONE launch: what a look at the first block's tokens says -- 1 short sequences, 2 long ones (0: nobody looked)
-    int32_t lastZstddBlocks = 0;  // achip_ctx_get_stat
-    int lastZstddVariant = 0;
-    int32_t lastAutoBlocks = 0;  // ... and this many blocks
-    int lastAutoFam = 0;         // ... of this codec family (kBlockCodecs)
-    int lastLzod = 0;           // the last launch was an LZO decode: 1 the two passes (their arena header leads the scratch), 2 a wavefront per item (0: it was not)
-    bool lastTwopass = false;   // the last decode was a two-pass one: its arena header leads the scratch
-    bool lastLz4dAuto = false;  // the last LZ4 decode ran in auto mode: its probe count leads the scratch
+    achip::stats::LastLaunch last;  // what the last launch that took the scratch left at its head (achip_ctx_get_stat; cleared by take_scratch alone)
     // Auto mode remembers (round 6): a call's probe statistics come back to pinned memory behind its kernels, without a wait; while the batches that follow have its
     // shape (codec, block count, the same source and destination buffers) the decoder the LAST ARRIVED statistics chose is the only one launched -- the other
     // decoder's kernels, launched to return at once, were ~65 us of a 8.2 ms headline call.  The probes still run in every call and go home, so a context whose
@@ -111,12 +106,13 @@ struct achip_ctx : achip::Settings {
     int32_t autoPendingBlocks = 0;
     const void* autoPendingSrc = nullptr;
     const void* autoPendingDst = nullptr;
-    int autoChoice[2] = {-1, -1};      // per codec family (0 LZ4, 1 Snappy): -1 unknown, 0 rings, 3 two passes
+    int autoChoice[2] = {-1, -1};      // per codec family (0 LZ4, 1 Snappy): -1 unknown, else LZ4_PICK_RINGS or LZ4_PICK_TWOPASS
     int32_t autoBlocks[2] = {0, 0};
     const void* autoSrc[2] = {nullptr, nullptr};
     const void* autoDst[2] = {nullptr, nullptr};
-    int lastRemembered = -1;           // the last decode ran on a remembered choice: that choice (decompress.choice reports it)
-    // scratch for the zstd pipeline (grown on demand)
+    // The one device buffer every launch works in that needs working memory: the Zstd pipeline's stages, the two-pass decoders' records, the encoders' tables,
+    // the containers' lists, the sizing / planning / packing calls' scans.  Grown on demand and never shrunk; a launch owns it until the next one on this
+    // context takes it (take_scratch), which is also when the statistics at its head (`last`) end.
     achip::host::DeviceBuffer<> scratch;
     int64_t scratchBytes = 0;
     achip::host::DeviceBuffer<> zstdMbScratch;
@@ -169,11 +165,38 @@ BatchArgs make_args(const void* srcBase, const int64_t* srcOff, const int32_t* s
         }                                                      \
     } while (0)
 
-constexpr int kNumOps = 18;  // aircompressor_hip.h: ACHIP_OP_* (one above the largest)
-// ... of which 15 is no op: the odd-even rule of the ops (even ops decode, odd ops encode) left it out
-inline bool op_known(int32_t op) { return op >= 0 && op < kNumOps && op != 15; }
+// aircompressor_hip.h's ACHIP_OP_*, a row per value: is it an op, does it encode, and which codec family's lane of a mixed batch runs it (0 LZ4's, 1 Snappy's, 2 Zstd's)
+struct OpRow {
+    bool known, encoder;
+    int family;
+};
+constexpr OpRow kOps[] = {
+    {true, false, 0}, {true, true, 0},  // LZ4 block
+    {true, false, 1}, {true, true, 1},  // Snappy block
+    {true, false, 2}, {true, true, 2},  // Zstd frame
+    {true, false, 0}, {true, true, 0},  // LZ4 frame
+    {true, false, 1}, {true, true, 1},  // x-snappy-framed
+    {true, false, 0}, {true, true, 0},  // Hadoop LZ4
+    {true, false, 1}, {true, true, 1},  // Hadoop Snappy
+    {true, true, 2}, {false, false, 2},  // Zstd stream: a writer only (its reader is achip_zstdstream_decompress_*), so 15 is no op
+    {true, false, 0}, {true, true, 0},  // LZO (rides with LZ4's)
+};
+constexpr int kNumOps = (int)(sizeof(kOps) / sizeof(kOps[0]));
+static_assert(ACHIP_OP_LZ4_DECOMPRESS == 0 && ACHIP_OP_LZ4_COMPRESS == 1 && ACHIP_OP_SNAPPY_DECOMPRESS == 2 && ACHIP_OP_SNAPPY_COMPRESS == 3 && ACHIP_OP_ZSTD_DECOMPRESS == 4 &&
+                  ACHIP_OP_ZSTD_COMPRESS == 5 && ACHIP_OP_LZ4FRAME_DECOMPRESS == 6 && ACHIP_OP_LZ4FRAME_COMPRESS == 7 && ACHIP_OP_SNAPPYFRAMED_DECOMPRESS == 8 &&
+                  ACHIP_OP_SNAPPYFRAMED_COMPRESS == 9 && ACHIP_OP_LZ4HADOOP_DECOMPRESS == 10 && ACHIP_OP_LZ4HADOOP_COMPRESS == 11 && ACHIP_OP_SNAPPYHADOOP_DECOMPRESS == 12 &&
+                  ACHIP_OP_SNAPPYHADOOP_COMPRESS == 13 && ACHIP_OP_ZSTDSTREAM_COMPRESS == 14 && ACHIP_OP_LZO_DECOMPRESS == 16 && ACHIP_OP_LZO_COMPRESS == 17 && kNumOps == 18,
+              "kOps has its rows in the order of ACHIP_OP_*");
+static_assert(kOps[ACHIP_OP_ZSTDSTREAM_COMPRESS].encoder && kOps[ACHIP_OP_ZSTDSTREAM_COMPRESS].family == kOps[ACHIP_OP_ZSTD_COMPRESS].family && !kOps[15].known &&
+                  !kOps[ACHIP_OP_LZO_DECOMPRESS].encoder && kOps[ACHIP_OP_LZO_COMPRESS].encoder && kOps[ACHIP_OP_LZO_COMPRESS].family == kOps[ACHIP_OP_LZ4_COMPRESS].family,
+              "the rows that break the even-decodes, odd-encodes pattern");
+inline bool op_known(int32_t op) { return op >= 0 && op < kNumOps && kOps[op].known; }
+inline bool op_is_encoder(int32_t op) { return kOps[op].encoder; }  // (of a known op)
+inline int op_family(int32_t op) { return kOps[op].family; }
 
 // abi_dispatch.cpp
+int32_t take_scratch(achip_ctx* ctx, int64_t bytes);  // the one way to the scratch for a launch: forgets what the last launch left in it (ctx->last), then ensure_scratch
+// ... the two growth policies underneath it
 int32_t ensure_scratch(achip_ctx* ctx, int64_t bytes);            // frees what is there first
 int32_t grow_scratch_keeping_old(achip_ctx* ctx, int64_t bytes);  // allocates first, frees the old scratch only when that worked
 void* zstd_mb_scratch(void* user, int64_t bytes);                 // the context's second, lazily grown buffer (ZstdMbProvider::get, AuxScratch)

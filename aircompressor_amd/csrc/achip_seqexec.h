@@ -12,6 +12,8 @@
 // Cross-lane operations are only used in wave-uniform control flow and lanes exchange data through memory only across wave_sync():
 // the kernels built on this header run unchanged under tools/hostemu (fibers) on a CPU.
 #pragma once
+#include <stddef.h>
+
 #include "achip_device.h"
 
 namespace achip {
@@ -51,6 +53,7 @@ struct ArenaHeader {  // leads the scratch
     int32_t fallbackBlocks;  // blocks whose records did not fit: decoded by the ring decoder afterwards
     int32_t pad[61];
 };
+static_assert(offsetof(ArenaHeader, fallbackBlocks) == 4 * stats::ARENA_FALLBACK_BLOCKS, "achip_ctx_get_stat reads the word by that index (achip_stats.h)");
 
 // the two-pass decoders' scratch: [header, 4 KiB][meta n x 8][only n x 4][arena, 4 KiB aligned]
 struct TwoPassLayout {

@@ -113,7 +113,7 @@ struct Pipe {
     int32_t count;  // items in this tile (multi-block stages: block slots of this pass)
     // multi-block stages (K1 only appends to mbList; nullptr there: multi-block frames go to the fallback list)
     int32_t* mbList;
-    int32_t* mbCount;     // (= counters + 40; + 41: blocks of all listed items)
+    int32_t* mbCount;     // (= counters + stats::ZSTD_MB_ITEMS; the words behind it: blocks of all listed items, items finished)
     MbItem* mbItem;
     MbBlock* mb;
     int32_t passFirst;    // this pass: the first block of its first item (slot 0) ...
@@ -125,6 +125,7 @@ struct Pipe {
     int32_t* order;
     int32_t* orderHist;
 };
+constexpr int MB_BLOCKS = stats::ZSTD_MB_BLOCKS - stats::ZSTD_MB_ITEMS, MB_FAST_ITEMS = stats::ZSTD_MB_FAST_ITEMS - stats::ZSTD_MB_ITEMS;  // mbCount[MB_*]
 constexpr int ORDER_BUCKETS = 256;  // by sequence count / 256, descending (a block holds at most 128 KiB / 3 = 43 691 sequences: bucket 170)
 
 // K4's choice per item: at least 80 output bytes per sequence (capacity as the stand-in for the output size) ...
@@ -139,7 +140,7 @@ __device__ __forceinline__ bool item_takes_rings(const Pipe& p, int32_t capacity
 __device__ __forceinline__ void to_fallback(const Pipe& p, int32_t slot, int stage)
 {
     p.desc[slot].state = 0;
-    atomicAdd(p.fallbackCount + 32 + stage, 1);  // per-stage diagnostics (achip_ctx_get_stat)
+    atomicAdd(p.fallbackCount + stats::ZSTD_STAGE + stage, 1);  // per-stage diagnostics (achip_ctx_get_stat)
     const int32_t k = atomicAdd(p.fallbackCount, 1);
     p.fallback[k] = p.first + slot;
 }
@@ -147,7 +148,7 @@ __device__ __forceinline__ void to_fallback(const Pipe& p, int32_t slot, int sta
 __device__ __forceinline__ void mb_to_fallback(const Pipe& p, int32_t j, int stage)
 {
     if (atomicExch(&p.mbItem[j].state, 0) == 1) {
-        atomicAdd(p.fallbackCount + 32 + stage, 1);
+        atomicAdd(p.fallbackCount + stats::ZSTD_STAGE + stage, 1);
         const int32_t k = atomicAdd(p.fallbackCount, 1);
         p.fallback[k] = p.mbItem[j].item;
     }
@@ -477,7 +478,7 @@ __global__ __launch_bounds__(64) void zstd_pipe_parse_kernel(BatchArgs a, zp::Pi
         else if (r == 0) {
             const int32_t k = atomicAdd(p.fallbackCount, 1);
             p.fallback[k] = block;
-            atomicAdd(p.fallbackCount + 32 + 1, 1);
+            atomicAdd(p.fallbackCount + stats::ZSTD_STAGE + 1, 1);
         }
     }
 }
@@ -1579,7 +1580,7 @@ __global__ __launch_bounds__(64) void zstd_mb_count_kernel(BatchArgs a, zp::Pipe
     it.pad[0] = it.pad[1] = it.pad[2] = 0;
     p.mbItem[j] = it;
     if (!w.ok) {
-        atomicAdd(p.fallbackCount + 32 + 6, 1);
+        atomicAdd(p.fallbackCount + stats::ZSTD_STAGE + 6, 1);
         p.fallback[atomicAdd(p.fallbackCount, 1)] = item;
     }
 }
@@ -1601,7 +1602,7 @@ __global__ __launch_bounds__(64) void zstd_mb_scan_kernel(zp::Pipe p)
         base += sx::wave_bcast(incl, 63);
     }
     if (lane == 0) {
-        p.mbCount[1] = base;
+        p.mbCount[MB_BLOCKS] = base;
     }
 }
 
@@ -1750,7 +1751,7 @@ __global__ __launch_bounds__(64) void zstd_mb_execute_kernel(BatchArgs a, zp::Pi
             a.outLen[it.item] = output;
             a.status[it.item] = 0;
             a.errOffset[it.item] = 0;
-            atomicAdd(p.mbCount + 2, 1);
+            atomicAdd(p.mbCount + MB_FAST_ITEMS, 1);
         }
     }
 }
@@ -1776,7 +1777,7 @@ __global__ __launch_bounds__(64) void zstd_mb_checksum_kernel(BatchArgs a, zp::P
             a.outLen[it.item] = it.outSize;
             a.status[it.item] = 0;
             a.errOffset[it.item] = 0;
-            atomicAdd(p.mbCount + 2, 1);
+            atomicAdd(p.mbCount + MB_FAST_ITEMS, 1);
         }
         else {
             mb_to_fallback(p, j, 5);
@@ -1801,8 +1802,8 @@ PipeLayout pipe_layout(int32_t nBlocks, int32_t tileMax)
     L.tile = nBlocks < PIPE_TILE ? nBlocks : PIPE_TILE;
     auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
     int64_t o = 0;
-    L.counters = o;
-    o = up(o + 256);
+    L.counters = o;  // (at 0: achip_ctx_get_stat reads the words of stats::ZSTD_* from the head of the scratch)
+    o = up(o + stats::ZSTD_COUNTER_BYTES);
     L.fallback = o;
     o = up(o + (int64_t)nBlocks * 4);
     L.mbList = o;
@@ -2016,15 +2017,16 @@ hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, v
     p.lit = base + L.lit;
     p.seq = (uint64_t*)(base + L.seq);
     p.seqCap = (uint32_t)L.tile * PIPE_SEQ_PER_ITEM + PIPE_SEQ_FLOOR;
-    p.fallbackCount = (int32_t*)(base + L.counters);
-    p.seqCursor = (uint32_t*)(base + L.counters + 64);
-    p.litCursor = (uint32_t*)(base + L.counters + 68);
-    p.longCount = (int32_t*)(base + L.counters + 72);
+    int32_t* const counters = (int32_t*)(base + L.counters);  // (the words of stats::ZSTD_*, achip_stats.h)
+    p.fallbackCount = counters + stats::ZSTD_FALLBACK_ITEMS;
+    p.seqCursor = (uint32_t*)(counters + stats::ZSTD_SEQ_CURSOR);
+    p.litCursor = (uint32_t*)(counters + stats::ZSTD_LIT_CURSOR);
+    p.longCount = counters + stats::ZSTD_LONG_ITEMS;
     p.litCap = (uint32_t)L.tile * PIPE_LIT_PER_ITEM + PIPE_LIT_FLOOR;
     p.fallback = (int32_t*)(base + L.fallback);
     const bool mbOn = mbp != nullptr && mbp->get != nullptr && mbp->passBlocks >= 16;
     p.mbList = mbOn ? (int32_t*)(base + L.mbList) : nullptr;
-    p.mbCount = (int32_t*)(base + L.counters) + 40;
+    p.mbCount = counters + stats::ZSTD_MB_ITEMS;
     p.mbItem = (zp::MbItem*)(base + L.mbItem);
     p.mb = nullptr;
     p.passFirst = 0;
@@ -2033,12 +2035,13 @@ hipError_t launch_zstd_decompress_pipe(const BatchArgs& a, hipStream_t stream, v
     p.mbLitCap = p.mbSeqCap = 0;
     p.order = nullptr;
     p.orderHist = nullptr;
-    hipError_t e = hipMemsetAsync(base + L.counters, 0, 256, stream);
+    hipError_t e = hipMemsetAsync(counters, 0, stats::ZSTD_COUNTER_BYTES, stream);
     if (e != hipSuccess) return e;
     for (int32_t first = 0; first < a.nBlocks; first += L.tile) {
         p.first = first;
         p.count = a.nBlocks - first < L.tile ? a.nBlocks - first : L.tile;
         if (first != 0) {
+            static_assert(stats::ZSTD_LIT_CURSOR == stats::ZSTD_SEQ_CURSOR + 1 && stats::ZSTD_LONG_ITEMS == stats::ZSTD_SEQ_CURSOR + 2, "the three words are cleared as one");
             e = hipMemsetAsync(p.seqCursor, 0, 12, stream);  // sequence and literal cursors, the count of long-sequence items
             if (e != hipSuccess) return e;
         }
@@ -2343,7 +2346,7 @@ StepLayout step_layout(int32_t slots, uint32_t litUnits, uint32_t seqs)
     L.seqCap = seqs + 64;
     auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
     int64_t o = 0;
-    L.counters = o; o = up(o + 512);           // [0, 256) the pipeline's counters (fallbackCount, mbCount at + 40 words); [256, 512) the pass's cursors
+    L.counters = o; o = up(o + 512);           // [0, 256) the pipeline's counters (stats::ZSTD_*: fallbackCount, mbCount); [256, 512) the pass's cursors (stats::ZSTD_STEP_CURSORS_AT)
     L.fallback = o; o = up(o + (int64_t)L.slots * 4 + 64);
     L.mbList = o; o = up(o + 64);
     L.mbItem = o; o = up(o + (int64_t)L.slots * sizeof(zp::MbItem));
@@ -2388,14 +2391,15 @@ hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t sc
         int32_t srcLen, dstCap, outLen, status;
     } args = {0, 0, 0, srcLen, outLimit, 0, 0};
     int32_t one[2] = {0, 0};
-    e = hipMemsetAsync(base + L.counters, 0, 512, stream);
+    int32_t* const counters = (int32_t*)(base + L.counters);
+    e = hipMemsetAsync(counters, 0, 512, stream);
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(base + L.args, &args, sizeof(args), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(base + L.mbList, one, 4, hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
     one[0] = 1;
-    e = hipMemcpyAsync(base + L.counters + 160, one, 4, hipMemcpyHostToDevice, stream);  // mbCount[0] = 1 listed item
+    e = hipMemcpyAsync(counters + stats::ZSTD_MB_ITEMS, one, 4, hipMemcpyHostToDevice, stream);  // mbCount[0] = 1 listed item
     if (e != hipSuccess) return e;
     BatchArgs a = BatchArgs();
     a.srcBase = dSrc;
@@ -2409,10 +2413,10 @@ hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t sc
     a.dstBase = dOut;
     a.nBlocks = 1;
     zp::Pipe p = zp::Pipe();
-    p.fallbackCount = (int32_t*)(base + L.counters);
+    p.fallbackCount = counters + stats::ZSTD_FALLBACK_ITEMS;
     p.fallback = (int32_t*)(base + L.fallback);
     p.mbList = (int32_t*)(base + L.mbList);
-    p.mbCount = (int32_t*)(base + L.counters) + 40;
+    p.mbCount = counters + stats::ZSTD_MB_ITEMS;
     p.mbItem = (zp::MbItem*)(base + L.mbItem);
     p.mb = (zp::MbBlock*)(base + L.mb);
     p.desc = (zp::Desc*)(base + L.desc);
@@ -2422,8 +2426,8 @@ hipError_t launch_zstd_stream_step(hipStream_t stream, void* scratch, int64_t sc
     p.seq = (uint64_t*)(base + L.seq);
     p.seqCap = L.seqCap;
     p.litCap = L.litCap;
-    p.seqCursor = (uint32_t*)(base + L.counters + 256);
-    p.litCursor = (uint32_t*)(base + L.counters + 260);
+    p.seqCursor = (uint32_t*)(base + L.counters + stats::ZSTD_STEP_CURSORS_AT);
+    p.litCursor = p.seqCursor + 1;
     p.first = 0;
     p.count = blocks + 1;
     p.passFirst = -1;  // (block i of the item sits in slot 1 + i: slot 0 is the ghost)
